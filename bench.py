@@ -3,6 +3,7 @@
 (7x7x(144+1), 15 classes, alg_param_hypelcnn.json), batch 1024 per GPU, fp32 -- BASELINE.json configs[1].
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR              (also write what the last timed step computed to DIR/*.npy)
 
 A "step" = next resident batch -> nhwc->pixel-major -> forward -> loss -> backward -> (RCCL all-reduce)
 -> TF1-Adam.  Inputs are synthetic (U[0,1) patches, uniform labels) and already resident in HBM.
@@ -33,6 +34,30 @@ CLASSIFIER_WORKLOADS = {
     "hypelcnn": ("HYPELCNNModel", "alg_param_hypelcnn.json", 7, 145, 15, 1024, 78579058),
     "dualcnn": ("DUALCNNModel", "alg_param_dualcnn.json", 11, 49, 20, 512, None),
 }
+
+# --dump-outputs: the pre-warm is this fixed number of steps instead of one derived from a timing, so that the state the
+# timed steps start from (weights, optimiser moments, step count, dropout draws) depends on the arguments only.  Each covers
+# the 50 ms of work the shader clock needs to ramp at the workload's default batch (step times of DESIGN.md 5).
+DUMP_PREWARM_STEPS = {"hypelcnn": 12, "dualcnn": 2, "cyclegan": 250, "cut": 45}
+DUMP_MAX_ELEMENTS = 4 << 20  # per array (16 MB of float32): larger outputs are written as a fixed, seeded sample
+
+
+def dump_outputs(directory, arrays):
+    """Write {name: array} as DIR/<name>.npy (float32, or float64 for the float64 scalars): arrays above DUMP_MAX_ELEMENTS
+    are flattened and sampled at positions drawn by a fixed seed from their size alone, the same in every run and build.
+    Returns {name: [shape written, shape computed]}."""
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        shape = list(a.shape)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = [list(a.shape), shape]
+    return written
 
 
 def build_model(batch, backend, workload="hypelcnn"):
@@ -497,6 +522,27 @@ def run_gan_workload(args, be, world, rank):
     return nb, bands, kind, (lambda: ops.run_step(x, y)), (lambda: float(sum(ops.losses().values()))), ops
 
 
+def prewarm_by_time(one_step, use_dist, note_collective):
+    """Run at least 50 ms of steps; returns how many ran.  Every rank must run the SAME number of steps -- a step ends in
+    collectives -- so the count is derived from three timed steps and, under data parallelism, agreed on by a MAX
+    all-reduce."""
+    import torch.distributed as dist
+    tw = time.perf_counter()
+    for _ in range(3):
+        one_step()
+    torch.cuda.synchronize()
+    est = (time.perf_counter() - tw) / 3
+    n_prewarm = max(2, min(500, int(0.05 / max(est, 1e-6)) + 1))
+    if use_dist:
+        t = torch.tensor([n_prewarm], device="cuda", dtype=torch.int32)
+        note_collective()  # a later HIP-graph capture must wait this collective out (backend.settle_before_capture)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        n_prewarm = int(t[0])
+    for _ in range(n_prewarm):
+        one_step()
+    return n_prewarm + 3
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -512,6 +558,10 @@ def main():
                          "direction; default: per-rank statistics)")
     ap.add_argument("--no-input-pipeline", action="store_true",
                     help="skip the second measurement (step fed by the device BatchIterator + augmentation kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, logits / per-phase losses, "
+                         "updated weights, gradients) to DIR/<name>.npy; the pre-warm becomes a fixed step count so "
+                         "that runs with the same arguments compute the same outputs")
     args = ap.parse_args()
     if args.sync_bn:
         os.environ["HYPEL_SYNC_BN"] = "1"  # read by Session.init_data_parallel
@@ -585,22 +635,12 @@ def main():
     # the shader clock needs 30-40 ms of uninterrupted work to ramp: pre-warm at least 50 ms of steps
     # whatever --warmup says (untimed, like the W warm-up steps)
     torch.cuda.synchronize()
-    # (every rank must run the SAME number of steps -- a step ends in collectives -- so the count is derived from
-    # three timed steps and, under data parallelism, agreed on by a MAX all-reduce)
-    tw = time.perf_counter()
-    for _ in range(3):
-        one_step()
-    torch.cuda.synchronize()
-    est = (time.perf_counter() - tw) / 3
-    n_prewarm = max(2, min(500, int(0.05 / max(est, 1e-6)) + 1))
-    if use_dist:
-        t = torch.tensor([n_prewarm], device="cuda", dtype=torch.int32)
-        note_collective()  # a later HIP-graph capture must wait this collective out (backend.settle_before_capture)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        n_prewarm = int(t[0])
-    for _ in range(n_prewarm):
-        one_step()
-    n_prewarm += 3
+    if args.dump_outputs:
+        n_prewarm = DUMP_PREWARM_STEPS[args.workload]
+        for _ in range(n_prewarm):
+            one_step()
+    else:
+        n_prewarm = prewarm_by_time(one_step, use_dist, note_collective)
     if use_dist:
         note_collective()
         dist.barrier()
@@ -617,6 +657,19 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step, read before anything else runs a step
+        if classifier:
+            outs = {"loss": np.float64([ct.loss_value()]),
+                    "logits": ct.value(train_step.loss.per_sample.logits).cpu().numpy()}
+            step_sess = sess
+        else:
+            outs = {"loss_" + k.replace("/", "_"): np.float64([v]) for k, v in gan_ops.losses().items()}
+            step_sess = gan_ops.ctx.session()
+        outs["params"] = step_sess.params.cpu().numpy()
+        outs["gradients"] = step_sess.grads.cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, outs)
     median_ms = step_ms[len(step_ms) // 2]
     if use_dist:
         t = torch.tensor([dt], device="cuda")
@@ -801,6 +854,8 @@ def main():
                "data": "synthetic", "config": cfg_d, "roofline": roof, "cpu_baseline": cpu}
         if pipeline is not None:
             out["with_input_pipeline"] = pipeline
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         out["commit"], note = commit_label()
         if note:
             out["commit_note"] = note

@@ -14,10 +14,10 @@ schedule, tensor-pool use, float64 losses and gradients.  Held to it here:
     trained variable groups, which LR each phase runs at, which phases feed the tensor pool;
   * the product's numbers on the kernel emulation against the reference-executed float64 values (5e-5).
 
-In the build container the fixture is re-derived from the reference (a stale fixture would pin nothing)."""
+`tests/golden/make_reference_facade.py` also recorded the phases the reference's wrapper files define through the
+product's tensorflow_gan facade (reference_facade.json); the product's wrappers are held to those as well."""
 import json
 import os
-import subprocess
 import sys
 from types import SimpleNamespace
 
@@ -34,7 +34,8 @@ GOLD = os.path.join(HERE, "golden")
 FIX = json.load(open(os.path.join(GOLD, "reference_gan_wiring.json")))
 ARR = np.load(os.path.join(GOLD, "reference_gan_wiring.npz"))
 CASES = sorted(FIX)
-HAVE_REF = os.path.isdir("/root/reference")
+FACADE = json.load(open(os.path.join(GOLD, "reference_facade.json")))["gan_phases"]
+sys.path.insert(0, GOLD)
 
 
 def _arrays(case, prefix):
@@ -238,33 +239,6 @@ def test_product_numbers_on_the_emulation_equal_the_executed_reference(case):
     assert worst < 5e-5
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="the reference is only present in the build container")
-def test_gan_fixture_is_what_the_reference_wrappers_produce_today():
-    code = r"""
-import json, os, sys
-import numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-import make_reference_gan_wiring as M
-M.W.install()
-orig_new = M.W.WiringEngine.new
-def new(self, var, op, inputs=(), **attrs):
-    t = orig_new(self, var, op, inputs, **attrs)
-    self.__dict__.setdefault("_tensors", []).append(t)
-    return t
-M.W.WiringEngine.new = new
-fix = json.load(open(os.path.join(%r, "reference_gan_wiring.json")))
-arr = np.load(os.path.join(%r, "reference_gan_wiring.npz"))
-for i, (name, gan_type, bands, batch, over) in enumerate(M.CASES):
-    case, a = M.run_case(gan_type, bands, batch, over, seed=100 + i)
-    assert json.loads(json.dumps(case)) == fix[name], name
-    for k, v in a.items():
-        assert np.array_equal(arr[name + "/" + k], v), (name, k)
-print("ok")
-""" % (ROOT, GOLD, GOLD, GOLD)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-3000:]
-
-
 # ------------------------------------------------------------------------------------------------ the facade, end to end
 def _canonical_phases(loss, ops, c):
     out = []
@@ -282,42 +256,28 @@ def _canonical_phases(loss, ops, c):
     return out, sorted((n, list(v.shape), round(v.l2_scale, 12)) for n, v in by_name.items())
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="the reference checkout exists in the build container only")
 @pytest.mark.parametrize("case", CASES)
 def test_reference_wrapper_files_build_the_products_phases(case):
     """`hypelcnn_amd.tfgan_facade.reference_wrapper`: the reference's UNCHANGED gan/wrapper_registry.py + gan/wrappers/*.py in
     the place of the product's wrapper -- define_model -> define_loss -> define_train_ops through the tensorflow_gan facade
-    onto the product's graph -- give the product wrapper's phases (names, terms with operands by provenance, weights, trained
-    groups, LR schedule, tensor-pool feeds, variables with shapes and regulariser scales), the oracle's numbers on the kernel
-    emulation, and leave nothing behind in the import system."""
-    from hypelcnn_amd import tfgan_facade
-    from hypelcnn_amd.gan.wrappers import gan_common as C
+    onto the product's graph -- as recorded by tests/golden/make_reference_facade.py: the product wrapper gives the same
+    phases (names, terms with operands by provenance, weights, trained groups, LR schedule, tensor-pool feeds, variables
+    with shapes and regulariser scales), and with them the oracle's numbers on the kernel emulation."""
+    import make_reference_facade as MF
     from tests import gan_util as U
     from tests.emu_backend import EmuBackend
     c = FIX[case]
-    f = c["flags"]
-    before_path = list(sys.path)
-    wrapper = tfgan_facade.reference_wrapper(c["gan_type"], "/root/reference", SimpleNamespace(**f))
-    wrapper.backend = EmuBackend()
-    tower, x, y = C.new_gan_tower(c["bands"])
-    model = wrapper.define_model(x, y)
-    loss_ref = wrapper.define_loss(model)
-    ops = wrapper.define_train_ops(model, loss_ref, max_number_of_steps=c["max_steps"], generator_lr=f["generator_lr"],
-                                   discriminator_lr=f["discriminator_lr"], gen_discriminator_lr=f["gen_discriminator_lr"])
-    ops.capture_graphs = False
-    assert sys.path == before_path and not any(isinstance(m, tfgan_facade.F._Finder) for m in sys.meta_path)
-    assert not any(n in sys.modules for n in ("tensorflow", "tensorflow_gan", "tf_slim", "gan.wrapper_registry", "gan"))
     _, _, loss_p, ops_p = _build_product(case, EmuBackend())
-    got, vars_got = _canonical_phases(ops.loss, ops, c)
-    want, vars_want = _canonical_phases(loss_p, ops_p, c)
-    assert vars_got == vars_want
-    assert got == want, (case, [(g["name"], w["name"]) for g, w in zip(got, want) if g != w])
-    assert ops.use_pool == ops_p.use_pool
+    got = MF.gan_phases_jsonable(_canonical_phases(loss_p, ops_p, c), bool(ops_p.use_pool))
+    want = FACADE[case]
+    assert got["variables"] == want["variables"]
+    assert got["phases"] == want["phases"], (case, [(g["name"], w["name"]) for g, w in zip(got["phases"], want["phases"]) if g != w])
+    assert got["use_pool"] == want["use_pool"]
     # ... and the numbers: every phase's loss and gradients against the oracle, through planner + kernel emulation
     cfg = _cfg(case)
     params = U.fp32(_arrays(case, "param/"))
     xv = ARR[f"{case}/x"].astype(np.float32).astype(np.float64)
     yv = ARR[f"{case}/y"].astype(np.float32).astype(np.float64)
-    sess = ops.ctx.session()
+    sess = ops_p.ctx.session()
     U.inject(sess, params)
-    assert U.check_phase_gradients(cfg, ops, params, xv, yv, tol=5e-5) < 5e-5
+    assert U.check_phase_gradients(cfg, ops_p, params, xv, yv, tol=5e-5) < 5e-5
