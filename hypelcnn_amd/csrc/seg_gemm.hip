@@ -562,7 +562,8 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
         // k-tile than rebuilding base + offset + k * ld (the scalar port issues one instruction per SIMD and 4 cycles;
         // at ~95 per wave and k-tile it was as busy as the matrix pipe).
         // (a group without segments -- a filter-gradient split with no reduction rows still owns its slab -- has s_end ==
-        // seg_begin: the clamp must not step in front of the table)
+        // seg_begin: the clamp must not step in front of the table.  When that group is the last one, seg_begin is one past
+        // its real records: the planner ends every segment table with a zero sentinel record for this read)
         hypel_seg_t nseg = segs[max(grp.seg_begin, min(ls + 1, s_end - 1))];
         int n_fetched = 0;  // real k-tiles requested so far: tile t + 1 exists iff t + 1 < n_fetched
         const uint64_t a_base0 = (uint64_t)(A + (!TA ? (int64_t)m0 * lda : (int64_t)m0));

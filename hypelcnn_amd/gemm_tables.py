@@ -109,7 +109,9 @@ class GemmTables:
                 recs += [record(g, m0) for (_, g, m0, _) in sh] + [empty] * (L - len(sh))
         else:
             recs = [record(g, m0) for (_, g, m0, _) in tiles]
-        sarr = np.array(segs, SEG_DTYPE) if segs else np.zeros(1, SEG_DTYPE)
+        # + one zero sentinel record: the kernel's look-ahead clamp (seg_gemm.hip) reads segs[seg_begin] also for a group
+        # without segments, which for the last group is one record past the real ones
+        sarr = np.array(segs + [(0, 0, 0, 0)], SEG_DTYPE)
         tarr = np.array(recs, TILE_DTYPE) if recs else np.zeros(0, TILE_DTYPE)
         return garr, sarr, tarr, macs
 

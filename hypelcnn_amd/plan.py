@@ -36,34 +36,21 @@ WGRAD_ROW_CHUNK = 512
 TARGET_BLOCKS = 1536  # blocks a filter-gradient product is split towards
 WGRAD_MAX_SPLITS = 64
 WGRAD_MIN_SPLITS = 0  # 0 = one split per 64 batch rows once a launch fills the device unsplit
-SPLIT_BIASED = True  # tap / channel-part splitting also for biased convs
 DGRAD_MAX_SEGS = 18  # segments per data-gradient tile (0 = never split)
 MAX_TAPS_PER_TILE = 9  # taps per forward tile of a multi-kernel level
 L2_CHUNK_BYTES = int(3.5 * (1 << 20))  # X working set an XCD's L2 keeps
-FWD_HINT_R2 = True  # round-2 forward tile-width rule (incl. 128x96 tiles)
 SPLITK_BELOW = 400    # FC-shaped products with fewer 128x64 blocks are cut along K
 SPLITK_TARGET = 768  # ... into slices that give about this many blocks
 TAP_SPLIT_MIN_BATCH = 64  # below this a pixel block has too few rows for splitting to pay
 
 
-# layers without batch norm: the bias-gradient reduction also writes dY (no separate activation-backward launch)
-ACT_BIAS_BWD = True
 # bias + leaky-ReLU of a normaliser-less fully-connected layer in the product's epilogue (HYPEL_GEMM_ACT_*): no post-op launch
 ACT_IN_GEMM = True
-# GAN loss terms and regularisers leave weighted partials in slots; one finaliser launch per train op sums them
-LOSS_SLOTS = True
-GEN_KEEP = True  # generator backward starts from the forward pass's kept activations
-TILE_HINTS = True
-SMALL_BN = True
 SMALL_BN_ROWS = 1024  # hypel_bn_act_small_*: rows kept in registers (32 row lanes x 32 rows)
-FOLD_RESIDUAL_GRAD = True
 # Filter gradients have no consumer before the optimiser: instead of one launch (+ one reduce) per layer they are
 # collected and go out as ONE hypel_seg_gemm_multi_f32 per tile width (+ ONE hypel_reduce_splits_multi_f32) at the end
 # of the backward pass (and at every data-parallel sync point).  A step's twenty ~25 us launch ramps/drains become three.
 MERGE_WGRAD = True
-# Batch-norm statistics of a 1x1 convolution's output in the GEMM epilogue (hypel_seg_gemm_stats_f32) instead of a
-# separate pass over Y (hypel_col_stats_partial)
-STATS_EPILOGUE = True
 
 
 class Storage:
@@ -106,7 +93,6 @@ def valid_taps(h, w, k, oy, ox):
     return out
 
 
-LOSS_TAIL = True  # xent / MSE sums, non-finite flag, step counter: one finaliser
 MSE_PARTIALS = 1024  # include/hypel.h HYPEL_MSE_PARTIALS
 DP_SYNC_WORK = 0.5  # share of the filter-gradient work before the sync point
 # Gradient buckets of the data-parallel exchange: two by default (one sync point: >= 60 % of the bytes leave under the
@@ -121,7 +107,6 @@ DP_MAX_BUCKETS = 8
 HINT_OVERRIDE = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("HYPEL_HINT_OVERRIDE", "").split(",") if kv)}
 RESIDENT_BLOCKS_64 = 6 * 256  # 128x64 (and multi-segment 128x32) blocks the device holds at once
 GEMM_SINGLE_SEG = 0x800  # include/hypel.h HYPEL_GEMM_SINGLE_SEG
-SINGLE_SEG_HINT = True
 GEMM_PAIRED_SEGS = 0x400    # ... HYPEL_GEMM_PAIRED_SEGS (bit of `accumulate`)
 GEMM_BK = 32  # reduction columns per k-tile of the kernel
 # fp32 products on the bf16 matrix cores with three-way split operands and six partial products (include/hypel.h
@@ -140,7 +125,6 @@ SPLIT_NOMINAL_BATCH_GAN = 4096  # ... and a GAN train op's (PhasePlan: the pair 
 # (H13 level 1, 30 filters per branch: 382 -> 397 us forward, 103 -> 95 TFLOP/s filter gradient; per-launch A/B, round 5)
 GEMM_SPLIT_MIN_N = 32
 SPLIT_OVERRIDE = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("HYPEL_SPLIT_OVERRIDE", "").split(",") if kv)}
-PAIR_SEGS = True  # short data-gradient segments (k <= 16) share k-tiles
 # K-slice records for the split-operand kernels (include/hypel.h HYPEL_TILE_PLAIN; round-5 verdict item 1).  The 128-wide
 # split blocks have 512 resident slots (two per CU), a third of what the fp32 kernels had: a data gradient of 392 x 4 = 1 568
 # equal blocks runs 3.06 rounds and pays for 4, and the 392 blocks of a multi-kernel level's data gradient are all resident
@@ -148,8 +132,7 @@ PAIR_SEGS = True  # short data-gradient segments (k <= 16) share k-tiles
 # launch -- list scheduling of the blocks in table order on 64 slots per XCD -- for a few slicings (every tile above a K
 # threshold cut into equal slices; the tiles of each XCD's last, partly filled round cut into s slices) and takes the best
 # one if it beats the unsliced launch by KSLICE_MIN_GAIN.  Slices >= 1 write plain partials to scratch, one
-# hypel_reduce_splits_multi_f32 adds them in slice order.
-KSLICE = True
+# hypel_reduce_splits_multi_sized_f32 adds them in slice order.
 KSLICE_MIN_GAIN = 0.10
 KSLICE_OVERHEAD_K = 24   # fixed cost of a block in reduction columns (prologue, pipeline fill, epilogue)
 KSLICE_MIN_K = 48        # shortest slice (reduction columns)
@@ -164,13 +147,18 @@ GEMM_MFMA16X4 = 0x2000  # include/hypel.h HYPEL_GEMM_MFMA16X4: 128x64 blocks on 
 GEMM_VAR_N = 0x4000     # ... HYPEL_GEMM_VAR_N: tile records carry their group's column count
 # Merged multi-kernel levels (include/hypel.h): the nested branches of a level share one packed weight image
 # W_pack[offset][Cin][C]; per output pixel and ring of input offsets ONE product on the column range of the branches
-# that contain the ring.  HYPEL_MERGE_LEVELS: comma list of the passes that use it -- "fwd", "dgrad" -- or "0".
-# Measured on MI355X (round 4, NOTES 4.A; per-launch and step-level A/B on one box): the merged FORWARD pays only for
-# levels with <= 16 filters per branch (128x64 blocks on the 16x16x4 MFMA instead of 128x16: 146 -> 128 us); with 30 / 60
-# filters a branch already fills a 32- / 64-column tile, the A stagings per FLOP do not change and the mixed-width launch
-# loses 50 - 60 % (380 -> 583 us, 430 -> 687 us).  The merged DATA GRADIENT (49 instead of 84 segments per pixel) gains
-# 2 - 7 % per launch.  The merged FILTER GRADIENT moved work between the three tile-width launches without shortening
-# their sum (1584 -> 1593 us): removed in round 5 (NOTES 4.A keeps the numbers).  Step: 6.51 -> 6.49 ms, i.e. neutral.
+# that contain the ring.  HYPEL_MERGE_LEVELS: comma list of the passes that use it -- "fwd", "dgrad", "wgrad"; default all
+# three -- or "0".  A level qualifies with up to MERGE_LEVELS_MAX_COUT filters per branch; per pass:
+#   fwd    <= 16 filters on the fp32 kernels (16x16x4 MFMA), <= MERGE_FWD_MAX_COUT_SPLIT on the split-operand kernels;
+#          a biased level keeps the unmerged forward
+#   dgrad  every qualifying level
+#   wgrad  split-operand kernels only, MERGE_WGRAD_MIN_COUT .. MERGE_WGRAD_MAX_COUT filters
+# Measured on MI355X (round 4, NOTES 4.A; per-launch and step-level A/B on one box, fp32 kernels): the merged FORWARD pays
+# only for levels with <= 16 filters per branch (128x64 blocks on the 16x16x4 MFMA instead of 128x16: 146 -> 128 us); with
+# 30 / 60 filters a branch already fills a 32- / 64-column tile, the A stagings per FLOP do not change and the mixed-width
+# launch loses 50 - 60 % (380 -> 583 us, 430 -> 687 us).  The merged DATA GRADIENT (49 instead of 84 segments per pixel)
+# gains 2 - 7 % per launch.  The merged FILTER GRADIENT moved work between the three tile-width launches without shortening
+# their sum (1584 -> 1593 us): removed in round 5, back in round 6 for the split kernels (below).
 MERGE_LEVELS = set(x for x in os.environ.get("HYPEL_MERGE_LEVELS", "fwd,dgrad,wgrad").split(",") if x and x != "0")
 MERGE_LEVELS_MAX_COUT = 64
 # per pass: widest branch (filters) the pass is merged for, taps per merged forward tile, forward tile-width hint
@@ -195,7 +183,6 @@ MERGE_FWD_MAX_COUT_SPLIT = 32
 MERGE_MAX_TAPS = 0  # 0 = MAX_TAPS_PER_TILE
 MERGE_SPLIT_MAX_TAPS = 16  # ... of a merged forward that runs on the split kernels
 MERGE_SPLIT_KPARTS = False  # channel parts (L2_CHUNK_BYTES) for a merged forward on the split kernels
-MERGE_FWD_SPLIT_NARROW = 0  # 1: the merged forward of a <= 16-filter level on the split kernels (128x64 blocks) instead of 16x16x4
 MERGE_FWD_HINT = 2
 
 
@@ -210,6 +197,8 @@ for _kv in filter(None, os.environ.get("HYPEL_PLAN_SET", "").split(",")):
 
 class TowerPlan:
     """Buffers + launch lists of one tower at one batch size."""
+
+    _defer_bias_sums = False  # PhasePlan: bias-gradient chunk sums wait for its one slab-reduction launch
 
     def __init__(self, tower, nb, session, loss=None, labels_c=None, external_masks=False, seed=1234, global_nb=None,
                  sync_bn=False):
@@ -236,10 +225,14 @@ class TowerPlan:
         self.bwd = []
         self.node_aux = {}
         self.mask_bufs = {}
-        self.scratch_sizes = {"scratch_partial": 1, "scratch_wgrad": 1, "scratch_red": 2048, "sums": 2}
+        self.scratch_sizes = {"scratch_partial": 1, "scratch_wgrad": 1, "sums": 2}
         self._pending_scratch = []
         self.param_written = set()  # variables whose gradient was already written in this plan (shared weights)
         self.sync_points = []  # (index into bwd, lo, hi): grads[lo:hi] are final there (data-parallel overlap)
+        self._level_layouts = {}  # node index -> packed layout of a merged multi-kernel level, or None
+        self._pending_wgrads = []  # filter-gradient products waiting for the next merged launch (_flush_wgrads)
+        self._wgrad_flushes = 0  # merged filter-gradient flushes so far (numbers their partials buffers)
+        self._kslice_bufs = 0  # K-sliced launches so far (numbers their partials buffers)
         self._build()
 
     # ---- which variables does this plan train / which tensors need a gradient (overridden by PhasePlan) ----
@@ -399,7 +392,7 @@ class TowerPlan:
         # tiles 5 x 96 without padding and whose 392 x 5 blocks are just under two resident rounds of the 128x96
         # variant (conv_dec_0 218 vs 227 (32) vs 244 (64) us; conv_enc_2 129 vs 134 vs 138) -- multi-segment levels
         # and the very wide dense layers on 128x64.
-        if n <= 512 and FWD_HINT_R2 and all(len(segs) == 1 for _, segs, _ in tables.groups):
+        if n <= 512 and all(len(segs) == 1 for _, segs, _ in tables.groups):
             if n >= 480 and n % 96 == 0:
                 return 3
             return 1
@@ -468,8 +461,8 @@ class TowerPlan:
         return worst
 
     def _kslice(self, tables, n, ta, tb, lda, ldb, width_hint):
-        """Choose K-slices for a launch on the split kernels (see KSLICE above).  Returns None (leave the launch alone) or
-        {group index: number of slices}."""
+        """Choose K-slices for a launch on the split kernels (see KSLICE_MIN_GAIN above).  Returns None (leave the launch
+        alone) or {group index: number of slices}."""
         groups = tables.groups
         bn = {1: 32, 2: 64, 3: 128}[width_hint]
         slots = KSLICE_SLOTS[width_hint]
@@ -588,20 +581,19 @@ class TowerPlan:
             self._scratch(l2, 0, "scratch_wgrad", S * count)
             lst.append(l2)
             return
-        pair = bool(pair and PAIR_SEGS and not ta and tb and n > 16 and stats is None)
+        pair = bool(pair and not ta and tb and n > 16 and stats is None)
         if hint is None:
-            hint = self._tile_hint(tables, n, ta, tb, res is not None) if TILE_HINTS else 0
+            hint = self._tile_hint(tables, n, ta, tb, res is not None)
         if HINT_OVERRIDE and tag in HINT_OVERRIDE:  # per-launch A/B: HYPEL_HINT_OVERRIDE="fwd:conv_enc_2=1,dgrad:fc_0=2"
             hint = HINT_OVERRIDE[tag]
-        single_seg = bool(SINGLE_SEG_HINT and not ta and
-                          all(len(segs) == 1 for _, segs, _ in tables.groups))
+        single_seg = bool(not ta and all(len(segs) == 1 for _, segs, _ in tables.groups))
         sp6 = self._split6(tag, tables, n, ta, tb, flags,
                            pair and any(k <= 16 for _, gs, _ in tables.groups for _, _, k in gs))
         if sp6:
             pair, hint, single_seg = False, sp6, False
             accumulate = int(accumulate) | GEMM_SPLIT6
         reduce_after = None
-        if (sp6 and kslice and KSLICE and stats is None and not flags and int(ldc) == int(n) and not (ta and tb)
+        if (sp6 and kslice and stats is None and not flags and int(ldc) == int(n) and not (ta and tb)
                 and tables.groups and not any(tables.ns)):
             # (one group per 128-row tile record first: a 1x1 convolution's data gradient is ONE group of 50 176 rows)
             per_tile = tables if ta or all(rows <= GEMM_BM for _, _, rows in tables.groups) else self._group_per_tile(tables, lda, ldc)
@@ -641,8 +633,8 @@ class TowerPlan:
         from .backend import TILE_PLAIN
         a_ks = int(lda) if ta else 1
         b_ks = 1 if tb else int(ldb)
-        kid = self.__dict__.setdefault("_kslice_bufs", 0)
-        self._kslice_bufs = kid + 1
+        kid = self._kslice_bufs
+        self._kslice_bufs += 1
         need = sum((s_ - 1) * tables.groups[gi][2] * int(ldc) for gi, s_ in slices.items())
         sname = f"kslice:{kid}"
         self._alloc(sname, need)
@@ -794,8 +786,6 @@ class TowerPlan:
                     self._flush_wgrads()
                     self.sync_points.append((len(self.bwd), sync_at[1], sync_at[2]))
             self._flush_wgrads()
-            if tw.n_dropout and not self.external_masks and not getattr(self, "_step_in_loss", False):
-                self.bwd.append(Launch("step_inc", (self._ref("step_ctr"),), tag="rng"))
         # shared scratch (stream order makes reuse safe)
         self._finish_scratch()
 
@@ -839,9 +829,8 @@ class TowerPlan:
         source (HYPELCNNModel.py:167-183), or None.  An input offset (dy, dx) at ring r = max(|dy|, |dx|) belongs to the
         branches with (k - 1) / 2 >= r -- a suffix of the concat order -- i.e. to the output columns [col0[r], C).
         Offsets are numbered ring-major; W_pack[d] is [Cin x C] (columns below col0 are never touched)."""
-        cache = self.__dict__.setdefault("_level_layouts", {})
-        if idx in cache:
-            return cache[idx]
+        if idx in self._level_layouts:
+            return self._level_layouts[idx]
         lay = None
         brs = node.branches
         # (a biased level -- DUALCNN -- keeps its unmerged forward: the bias rides in the GEMM epilogue / the tap-split
@@ -875,7 +864,7 @@ class TowerPlan:
                     # these passes read the packed image (the filter gradient does not)
                     lay["packed"] = True
                     self._alloc(lay["buf"], len(offs) * src.c * C)
-        cache[idx] = lay
+        self._level_layouts[idx] = lay
         return lay
 
     def _level_pass(self, idx, node, what):
@@ -898,7 +887,7 @@ class TowerPlan:
         base = Ref(self.sess.params)
         ents = []
         for idx, node in enumerate(self.tower.nodes):
-            lay = self.__dict__.get("_level_layouts", {}).get(idx)
+            lay = self._level_layouts.get(idx)
             if lay is None or not lay.get("packed"):
                 continue
             dst0 = (self._ref(lay["buf"]).ptr() - base.ptr()) // 4
@@ -927,7 +916,7 @@ class TowerPlan:
         src = node.sources[0]
         rows_all = node.out.npix * nb
         C, cin = lay["C"], lay["cin"]
-        narrow16 = lay["co"] <= 16 and C <= 64 and not (MERGE_FWD_SPLIT_NARROW and GEMM_SPLIT == 6)
+        narrow16 = lay["co"] <= 16 and C <= 64
         on_split = GEMM_SPLIT == 6 and not narrow16 and C > GEMM_SPLIT_MIN_N  # (the size rule of _split6 may still say fp32)
         ring_sizes = [sum(1 for o in lay["offs"] if o[2] == r) for r in range(lay["rmax"] + 1)]
         max_taps = MERGE_MAX_TAPS or (MERGE_SPLIT_MAX_TAPS if on_split else MAX_TAPS_PER_TILE)
@@ -999,7 +988,7 @@ class TowerPlan:
             # stored behind Y in the same buffer) and a strided reduce adds Y_1.. into Y.
             splits = {}
             kparts = 1
-            if lay is None and (bias_ref is None or SPLIT_BIASED) and nb >= TAP_SPLIT_MIN_BATCH:
+            if lay is None and nb >= TAP_SPLIT_MIN_BATCH:
                 for b in node.branches:
                     taps = min(b.k, h) * min(b.k, w)
                     if taps > MAX_TAPS_PER_TILE:
@@ -1027,7 +1016,7 @@ class TowerPlan:
                 by_cout.setdefault(key, []).append((b, choff))
                 choff += b.cout
             # batch-norm statistics in the epilogue: a lone 1x1 branch on contiguous input writes ONE [rows x c] matrix
-            fuse_stats = (STATS_EPILOGUE and node.has_bn and node.training and len(node.branches) == 1
+            fuse_stats = (node.has_bn and node.training and len(node.branches) == 1
                           and node.branches[0].k == 1 and s_st.contiguous and s_max == 1 and c > 16
                           and not self._small_bn(node, rows_all) and lay is None)
             aux["stats_in_gemm"] = fuse_stats
@@ -1211,7 +1200,7 @@ class TowerPlan:
     def _small_bn(self, node, rows):
         """Batch norm over a short matrix (the fully-connected tail: rows = batch) with no shortcut to add: one block
         per channel stripe covers every row, so the whole BN + activation is one launch per direction."""
-        return (SMALL_BN and rows <= SMALL_BN_ROWS and not node.residuals and node.has_post
+        return (rows <= SMALL_BN_ROWS and not node.residuals and node.has_post
                 and not (self.sync_bn and node.has_bn))
 
     def _emit_post_fwd(self, idx, node, y_ref, ldy, rows, c, aux, z_ref):
@@ -1284,9 +1273,8 @@ class TowerPlan:
         # the dropout step counter advances once per training step, after the last mask of the step was drawn (masks
         # are drawn in the forward pass): it rides in the loss finaliser
         step = None
-        if LOSS_TAIL and self.training and self.tower.n_dropout and not self.external_masks:
+        if self.training and self.tower.n_dropout and not self.external_masks:
             step = self._ref("step_ctr")
-            self._step_in_loss = True
         mse_args = None
         if ps.extra_mse is not None:
             m = ps.extra_mse
@@ -1301,31 +1289,16 @@ class TowerPlan:
                 assert acc == 0
                 da, ldda = self._ref(gst.buf), gst.ld
             mse_args = (self._ref(a_st.buf), a_st.ld, self._ref("in:" + src.name), feat, nb, feat)
-        if LOSS_TAIL:
-            # xent rows + MSE block partials -> ONE finaliser (means, non-finite flag, step counter)
-            ws = None
-            if mse_args is not None:
-                self._alloc("mse_ws", MSE_PARTIALS)
-                ws = self._ref("mse_ws")
-                self.fwd.append(Launch("mse_partial_f32", mse_args + (da, ldda, gworld, ws), nbytes=12 * nb * feat,
-                                       tag="loss"))
-            self.fwd.append(Launch("loss_finalize_f32", (
-                self._ref("loss_ps"), nb, ws, 1.0 / (nb * feat) if mse_args is not None else 0.0, self._ref("loss_ce"),
-                self._ref("loss_mse") if mse_args is not None else None, guard, step), tag="loss"))
-            return
-        l2 = Launch("sum_f32", (self._ref("loss_ps"), nb, 1.0 / nb, self._ref("loss_ce"), None), tag="loss")
-        self._scratch(l2, 4, "scratch_red")
-        self.fwd.append(l2)
+        # xent rows + MSE block partials -> ONE finaliser (means, non-finite flag, step counter)
+        ws = None
         if mse_args is not None:
-            l3 = Launch("mse", mse_args + (self._ref("loss_mse"), da, ldda, gworld, None), nbytes=12 * nb * feat,
-                        tag="loss")
-            self._scratch(l3, 10, "scratch_red")
-            self.fwd.append(l3)
-        if guard is not None:
-            # NanTensorHook / check_numerics on the device: flag behind the gradient buffer, read by the optimiser
-            self.fwd.append(Launch("loss_guard_f32", (self._ref("loss_ce"),
-                                                      self._ref("loss_mse") if ps.extra_mse is not None else None,
-                                                      guard), tag="loss-guard"))
+            self._alloc("mse_ws", MSE_PARTIALS)
+            ws = self._ref("mse_ws")
+            self.fwd.append(Launch("mse_partial_f32", mse_args + (da, ldda, gworld, ws), nbytes=12 * nb * feat,
+                                   tag="loss"))
+        self.fwd.append(Launch("loss_finalize_f32", (
+            self._ref("loss_ps"), nb, ws, 1.0 / (nb * feat) if mse_args is not None else 0.0, self._ref("loss_ce"),
+            self._ref("loss_mse") if mse_args is not None else None, guard, step), tag="loss"))
 
     # ------------------------------------------------------------------ backward
     @staticmethod
@@ -1339,7 +1312,7 @@ class TowerPlan:
         """Index of a shortcut of `node` whose gradient can ride in the epilogue of the node's own data-gradient
         GEMM: the shortcut source IS the convolution input (net = f(conv(net)) + map(net)), same pixel grid, plain
         (un-cropped) storage on both sides."""
-        if not FOLD_RESIDUAL_GRAD or node.kind != "conv" or not node.has_post:
+        if node.kind != "conv" or not node.has_post:
             return None
         src = node.sources[0]
         if not self._needs_grad(src) or src.npix != node.out.npix:
@@ -1558,8 +1531,7 @@ class TowerPlan:
             pacc = 0
             if dparam is not None:
                 pacc = self._param_acc(aux["beta"] if has_bn else aux["bias"])
-            if (ACT_BIAS_BWD and not has_bn and dy is not None and (code != 0 or mask is not None)
-                  and not self.sync_bn):
+            if not has_bn and dy is not None and (code != 0 or mask is not None) and not self.sync_bn:
                 # no batch norm: dY = dZ * act'(y) needs no column sum -- the bias-gradient reduction writes it too
                 l1 = Launch("act_bias_bwd_reduce", (dz, c, y_ref, c, rows, c, code, alpha, mask, c, chunk, None, dy, c),
                             nbytes=12 * rows * c, tag="post-bwd-reduce+apply")
@@ -1568,19 +1540,18 @@ class TowerPlan:
                     self._scratch(l1, 11, "scratch_partial", n_chunks * 2 * c)
                     self.bwd.append(l1)
                     return
-                if getattr(self, "_defer_bias_sums", False):
+                if self._defer_bias_sums:
                     # GAN train op: the chunk sums of every such layer stay in a buffer of their own and ONE launch at the end
                     # of the backward pass turns them all into bias gradients (PhasePlan._flush_slab_reduces)
-                    k = self.__dict__.setdefault("_bias_sum_bufs", 0)
-                    self._bias_sum_bufs = k + 1
+                    k = self._bias_sum_bufs
+                    self._bias_sum_bufs += 1
                     name = f"bias_sums:{k}"
                     self._alloc(name, n_chunks * 2 * c)
                     args = list(l1.args)
                     args[11] = self._ref(name)
                     l1.args = tuple(args)
                     self.bwd.append(l1)
-                    self.__dict__.setdefault("_bias_sum_entries", []).append((self._ref(name), dparam, 2 * c, c, n_chunks,
-                                                                             pacc))
+                    self._bias_sum_entries.append((self._ref(name), dparam, 2 * c, c, n_chunks, pacc))
                     return
                 self._scratch(l1, 11, "scratch_partial", n_chunks * 2 * c)
                 l2 = Launch("bwd_reduce_finalize", (None, n_chunks, c, None, dparam, pacc), tag="post-bwd-finalize")
@@ -1657,13 +1628,11 @@ class TowerPlan:
         S = s_pix * s_row
         tb = tables_by_split_builder((s_pix, s_row))
         if MERGE_WGRAD:
-            pend = self.__dict__.setdefault("_pending_wgrads", [])
-            if (acc or (unpack and any(e[6] for e in unpack["entries"]))) and pend:
+            if (acc or (unpack and any(e[6] for e in unpack["entries"]))) and self._pending_wgrads:
                 # a second application of shared weights adds to what an earlier pending product writes: keep the order
                 self._flush_wgrads()
-                pend = self._pending_wgrads
-            pend.append(dict(tb=tb, S=S, slab=int(slab), w0=int(w0_offset), n=int(n), a_ref=a_ref, lda=int(lda),
-                             b_ref=b_ref, ldb=int(ldb), tag=tag, acc=int(acc), unpack=unpack))
+            self._pending_wgrads.append(dict(tb=tb, S=S, slab=int(slab), w0=int(w0_offset), n=int(n), a_ref=a_ref,
+                                             lda=int(lda), b_ref=b_ref, ldb=int(ldb), tag=tag, acc=int(acc), unpack=unpack))
             return
         assert unpack is None, "merged-level filter gradients need the merged launch (MERGE_WGRAD)"
         if S == 1:
@@ -1689,8 +1658,7 @@ class TowerPlan:
         loaded XCD (each XCD's L2 then streams a row range once for all its taps, and the XCDs finish together), and
         the record array is laid out so that the kernel's XCD remap (block b runs on XCD b % 8 and takes record
         (b % 8) * L + b / 8) hands XCD x exactly its list; short lists are padded with empty records."""
-        pend = self.__dict__.get("_pending_wgrads") or []
-        self._pending_wgrads = []
+        pend, self._pending_wgrads = self._pending_wgrads, []
         if not pend:
             return
         base = Ref(self.sess.params)
@@ -1703,8 +1671,8 @@ class TowerPlan:
 
         # scratch for the split slabs of this flush
         need = sum(e["S"] * e["slab"] for e in pend if e["S"] > 1)
-        fid = self.__dict__.setdefault("_wgrad_flushes", 0)
-        self._wgrad_flushes = fid + 1
+        fid = self._wgrad_flushes
+        self._wgrad_flushes += 1
         sname = f"wgrad_partials:{fid}"
         self._alloc(sname, max(need, 1))
         spos = 0
@@ -1792,7 +1760,7 @@ class TowerPlan:
             for x in range(8):
                 if xcd_recs[x]:
                     arr[x * L:x * L + len(xcd_recs[x])] = np.array(xcd_recs[x], MTILE_DTYPE)
-            sarr = np.array(segs, SEG_DTYPE) if segs else np.zeros(1, SEG_DTYPE)
+            sarr = np.array(segs + [(0, 0, 0, 0)], SEG_DTYPE)  # + the zero sentinel record (GemmTables.finalize)
             s_t, r_t = self.be.upload(sarr), self.be.upload(arr)
             self.tables += [s_t, r_t]
             l = Launch("seg_gemm_multi_f32", (base, 1, 0, width, Ref(s_t), Ref(r_t), int(len(arr))),

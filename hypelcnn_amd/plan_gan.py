@@ -8,7 +8,7 @@ import numpy as np
 from . import graph as G
 from .backend import REDUCE_ENTRY_DTYPE, Ref
 from .gemm_tables import GemmTables, Launch
-from .plan import GEN_KEEP, LOSS_SLOTS, Storage, TowerPlan, stat_chunk_rows
+from .plan import Storage, TowerPlan, stat_chunk_rows
 
 
 def gen_kernel_sizes(bands):
@@ -22,11 +22,6 @@ BATCH_APPS = True
 BATCH_APPS_MAX = 8
 # the per-block gradient slabs of every fused generator / dense-stack application of a train op in ONE reduction launch
 SLAB_REDUCE_MULTI = True
-# An encoder-only generator application on a tensor that the FULL generator of the same train op (same variables) also
-# consumes is that application's n_4 (cut_wrapper.py:301-339: gen(x) and gen(x, only_encoder), gen(y) and gen(y, only_encoder)):
-# the full launch writes it too (hypel_gan_generator_fwd_tap) and its backward takes the gradient that reached it
-# (hypel_gan_generator_bwd_tap) -- the encoder-only launches of those tensors disappear.
-GEN_TAP = True
 # Two same-shaped networks with DIFFERENT variables (CycleGAN's G_x2y / G_y2x and D_x / D_y, cycle_gan_wrapper.py:82-124) whose
 # applications can run side by side share one launch: each takes its own share of the blocks (hypel_*_apps).  At the
 # Gulfport sizes every one of those applications is a latency chain on a fraction of the chip.
@@ -46,7 +41,20 @@ class PhasePlan(TowerPlan):
         self.terms = list(terms)
         self.train_groups = set(train_groups)
         self.outputs = list(outputs)
-        self._defer_bias_sums = SLAB_REDUCE_MULTI
+        # GAN-only state (set before TowerPlan.__init__, which runs _build)
+        self._defer_bias_sums = SLAB_REDUCE_MULTI  # bias-gradient chunk sums wait for the one slab-reduction launch
+        self._bias_sum_entries = []  # reduce entries of those deferred bias gradients
+        self._bias_sum_bufs = 0  # deferred chunk-sum buffers so far (numbers them)
+        self._slab_sets = {}  # id(first weight) -> the per-block gradient slabs of one weight set (_defer_slab_reduce)
+        self._slab_apps = []  # *_apps launches whose slab arguments are resolved in _flush_slab_reduces
+        self._slab_bufs = 0  # slab buffers so far (numbers them)
+        self._groups = {}  # first member's node index -> the row-concatenated application of a unit (_fwd_group)
+        self._gen_fwd = {}  # node index -> generator forward launch (the backward pass may make it keep activations)
+        self._term_batch = []  # deferred loss terms of the next loss_terms_slots launch
+        self._term_list = None  # the launch list that batch goes to
+        self._n_loss_slots = 0  # loss slots handed out so far
+        self._slot_launches = []  # (launch, argument index) that take the slot buffer (_finish_loss_slots)
+        self._loss_written = False  # a term has written the op's loss value: later ones accumulate
         super().__init__(tower, nb, session, loss=None, external_masks=True, seed=seed)
 
     # ---- analysis ----
@@ -91,10 +99,14 @@ class PhasePlan(TowerPlan):
             needed.add(id(t.node))
             stack += [i.owner for i in self._node_inputs(t.node)]
         self.needed = [n for n in self.tower.nodes if id(n) in needed]
+        # An encoder-only generator application on a tensor that the FULL generator of the same train op (same variables)
+        # also consumes is that application's n_4 (cut_wrapper.py:301-339: gen(x) and gen(x, only_encoder), gen(y) and
+        # gen(y, only_encoder)): the full launch writes it too (hypel_gan_generator_fwd_tap) and its backward takes the
+        # gradient that reached it (hypel_gan_generator_bwd_tap) -- the encoder-only launches of those tensors disappear.
         self._taps, self._tapped = {}, {}  # id(full generator node) -> the encoder output it also produces; id(enc node) -> full node
         # (only with the dependency-driven schedule of _schedule_units: in tower order an encoder application may precede the
         # full one it would be read from)
-        if GEN_TAP and BATCH_APPS and hasattr(self.be, "gan_generator_tap_supported"):
+        if BATCH_APPS and hasattr(self.be, "gan_generator_tap_supported"):
             fulls = {(id(n.weights[0]), id(n.src)): n for n in self.needed
                      if isinstance(n, G.GeneratorNode) and not n.only_encoder}
             for e in self.needed:
@@ -424,7 +436,6 @@ class PhasePlan(TowerPlan):
                 self.storage[id(t)] = Storage(t_st.buf, nb0, t_st.ld, None, t_st.ch_off + g * nb0 * t_st.ld, t.c, 1)
             if id(syn_tap) in self._grad_needed and self.terms and "g:" + t_st.buf not in self.buffers:
                 self._alloc("g:" + t_st.buf, G_ * nb0 * t_st.ld)
-        self._groups = getattr(self, "_groups", {})
         self._groups[idx0] = dict(rep=rep, syn_src=syn_src, srcs=srcs, gathered=gathered, cat=cat_st, taps=taps,
                                   syn_tap=syn_tap)
 
@@ -512,9 +523,8 @@ class PhasePlan(TowerPlan):
         one reduction launch per application, every application of one weight set appends its slabs to that set's
         region and ONE hypel_reduce_splits_wave_multi_f32 at the end of the backward pass sums each region (one entry per
         weight set and kind: two entries never write the same gradient)."""
-        sets = self.__dict__.setdefault("_slab_sets", {})
-        st = sets.setdefault(id(w0), dict(w0=w0, b0=b0, w=(w_stride, w_count), b=(b_stride, b_count), acc=acc, apps=[],
-                                         blocks=0))
+        st = self._slab_sets.setdefault(id(w0), dict(w0=w0, b0=b0, w=(w_stride, w_count), b=(b_stride, b_count), acc=acc,
+                                                     apps=[], blocks=0))
         st["apps"].append((launch, pos_w, pos_b, st["blocks"]))
         st["blocks"] += blocks
 
@@ -522,7 +532,7 @@ class PhasePlan(TowerPlan):
         """The *_apps form: `launch` leaves `bpa` slabs for each of its variable sets (`nodes`: one application node per
         set).  Every set's slabs still go to that set's own region; the launch reaches set g's first slab by a stride from
         set 0's (arguments pos_ws / pos_bs), known once the regions are laid out."""
-        sets = self.__dict__.setdefault("_slab_sets", {})
+        sets = self._slab_sets
         where = []
         for nd in nodes:
             w0, b0 = nd.weights[0], nd.biases[0]
@@ -533,13 +543,11 @@ class PhasePlan(TowerPlan):
                                              blocks=0))
             where.append((id(w0), st["blocks"]))
             st["blocks"] += bpa
-        self.__dict__.setdefault("_slab_apps", []).append((launch, pos_w, pos_b, pos_ws, pos_bs, where))
+        self._slab_apps.append((launch, pos_w, pos_b, pos_ws, pos_bs, where))
 
     def _flush_slab_reduces(self):
-        sets = self.__dict__.get("_slab_sets") or {}
-        self._slab_sets = {}
-        bias_entries = self.__dict__.get("_bias_sum_entries") or []
-        self._bias_sum_entries = []
+        sets, self._slab_sets = self._slab_sets, {}
+        bias_entries, self._bias_sum_entries = self._bias_sum_entries, []
         if not sets and not bias_entries:
             return
         base = Ref(self.sess.params)
@@ -564,8 +572,8 @@ class PhasePlan(TowerPlan):
                     later.append([])
                 later[r - 1].append(e)
         for k, st in enumerate(sets.values()):
-            fid = self.__dict__.setdefault("_slab_bufs", 0)
-            self._slab_bufs = fid + 1
+            fid = self._slab_bufs
+            self._slab_bufs += 1
             names = st["names"] = {}
             for kind, var in (("w", st["w0"]), ("b", st["b0"])):
                 stride, count = st[kind]
@@ -578,7 +586,7 @@ class PhasePlan(TowerPlan):
                 args[pos_w] = self._ref(names["w"], b0 * st["w"][0])
                 args[pos_b] = self._ref(names["b"], b0 * st["b"][0])
                 launch.args = tuple(args)
-        for launch, pos_w, pos_b, pos_ws, pos_bs, where in self.__dict__.get("_slab_apps") or []:
+        for launch, pos_w, pos_b, pos_ws, pos_bs, where in self._slab_apps:
             first = [(self._ref(sets[sid]["names"]["w"], b0 * sets[sid]["w"][0]),
                       self._ref(sets[sid]["names"]["b"], b0 * sets[sid]["b"][0])) for sid, b0 in where]
             args = list(launch.args)
@@ -631,7 +639,6 @@ class PhasePlan(TowerPlan):
                                              self._p(b0), int(node.only_encoder), self._ref(st.buf), st.ld),
                        nbytes=8 * self.nb * src.c, tag="gen-fwd")
         self.fwd.append(l)
-        self._gen_fwd = getattr(self, "_gen_fwd", {})
         self._gen_fwd[idx] = l  # _bwd_generator turns it into the activation-keeping form when a backward pass follows
 
     def _bwd_generator(self, idx, node):
@@ -649,7 +656,7 @@ class PhasePlan(TowerPlan):
             dx, lddx = self._ref(gst.buf, gst.ch_off), gst.ld
         tap = self._taps.get(id(node))
         tap_grad = tap is not None and self.grad_written.get(id(tap), False)
-        keep_n = n_apps * self.be.gan_generator_keep_floats(self.nb // n_apps, src.c, int(node.only_encoder)) if GEN_KEEP else 0
+        keep_n = n_apps * self.be.gan_generator_keep_floats(self.nb // n_apps, src.c, int(node.only_encoder))
         kref = None
         if keep_n > 0:
             # the forward pass of this application leaves its activations for this launch (hypel.h: bit-identical to
@@ -866,10 +873,9 @@ class PhasePlan(TowerPlan):
         a_st = self.storage_of(term.a)
         a_ref = self._ref(a_st.buf, a_st.ch_off)
         da, ldda, acc_a = self._grad_ref(term.a)
-        acc_loss = 1 if getattr(self, "_loss_written", False) else 0
-        if term.kind == "nce" or not LOSS_SLOTS:
-            self._loss_written = True
         if term.kind == "nce":
+            acc_loss = 1 if self._loss_written else 0
+            self._loss_written = True
             self._flush_loss_terms()  # the batched terms before it keep their place in the order of gradient writes
             b_st = self.storage_of(term.b)
             db, lddb, acc_b = self._grad_ref(term.b)
@@ -885,27 +891,19 @@ class PhasePlan(TowerPlan):
             b_st = self.storage_of(term.b)
             b_ref, ldb = self._ref(b_st.buf, b_st.ch_off), b_st.ld
             db, lddb, acc_b = self._grad_ref(term.b)
-        if LOSS_SLOTS:
-            # the term's weighted partial sums go to a slot of their own; ONE finaliser adds every slot of the op up, and
-            # terms that write different gradient buffers share ONE launch (_flush_loss_terms)
-            coef = float(term.weight) / (nb * term.a.c)
-            self._batch_loss_term(self.fwd, dict(mode=mode, a=a_ref, lda=a_st.ld, b=b_ref, ldb=ldb, rows=nb, c=term.a.c,
-                                                 target=float(term.target), gcoef=coef, pscale=coef, da=da, ldda=ldda,
-                                                 acc_da=acc_a, db=db, lddb=lddb, acc_db=acc_b))
-            return
-        l = Launch("gan_loss", (mode, a_ref, a_st.ld, b_ref, ldb, nb, term.a.c, float(term.target), float(term.weight),
-                                self._ref("loss"), acc_loss, da, ldda, acc_a, db, lddb, acc_b, None),
-                   tag="loss-" + term.kind)
-        self._scratch(l, 17, "scratch_red")
-        self.fwd.append(l)
+        # the term's weighted partial sums go to a slot of their own; ONE finaliser adds every slot of the op up, and
+        # terms that write different gradient buffers share ONE launch (_flush_loss_terms)
+        coef = float(term.weight) / (nb * term.a.c)
+        self._batch_loss_term(self.fwd, dict(mode=mode, a=a_ref, lda=a_st.ld, b=b_ref, ldb=ldb, rows=nb, c=term.a.c,
+                                             target=float(term.target), gcoef=coef, pscale=coef, da=da, ldda=ldda,
+                                             acc_da=acc_a, db=db, lddb=lddb, acc_db=acc_b))
 
     def _batch_loss_term(self, lst, t):
         """Collect a deferred loss term; terms of a batch run concurrently in one launch, so a term that writes a gradient
         buffer an earlier term of the batch writes (or reads) closes that batch first."""
-        batch = self.__dict__.setdefault("_term_batch", [])
-        if batch and self._term_list is not lst:
+        if self._term_batch and self._term_list is not lst:
             self._flush_loss_terms()
-            batch = self._term_batch
+
         def spans(u, keys):
             out = []
             for k, ldk in keys:
@@ -919,7 +917,7 @@ class PhasePlan(TowerPlan):
             return any(a[0] == b[0] and a[1] < b[2] and b[1] < a[2] for a in xs for b in ys)
 
         outs, ins = spans(t, (("da", "ldda"), ("db", "lddb"))), spans(t, (("a", "lda"), ("b", "ldb")))
-        for u in batch:
+        for u in self._term_batch:
             u_outs, u_ins = spans(u, (("da", "ldda"), ("db", "lddb"))), spans(u, (("a", "lda"), ("b", "ldb")))
             if hit(outs, u_outs + u_ins) or hit(ins, u_outs):
                 self._flush_loss_terms()
@@ -929,8 +927,7 @@ class PhasePlan(TowerPlan):
 
     def _flush_loss_terms(self):
         from .backend import LOSS_NONE, LOSS_TERM_DTYPE
-        batch = self.__dict__.get("_term_batch") or []
-        self._term_batch = []
+        batch, self._term_batch = self._term_batch, []
         if not batch:
             return
         base = Ref(self.sess.params)
@@ -943,8 +940,8 @@ class PhasePlan(TowerPlan):
             assert d % 4 == 0
             return d // 4
 
-        first = getattr(self, "_n_loss_slots", 0)
-        self._n_loss_slots = first + len(batch)
+        first = self._n_loss_slots
+        self._n_loss_slots += len(batch)
         arr = np.array([(rel(t["a"]), rel(t["b"]), rel(t["da"]), rel(t["db"]), t["lda"], t["ldb"], t["ldda"], t["lddb"],
                          t["rows"], t["mode"], t["c"], t["acc_da"], t["acc_db"], t["target"], t["gcoef"], t["pscale"],
                          first + k) for k, t in enumerate(batch)], LOSS_TERM_DTYPE)
@@ -956,13 +953,12 @@ class PhasePlan(TowerPlan):
 
     def _loss_slot(self, launch, pos):
         """Give a deferred loss term the next 1024-float slot of the op's slot buffer (allocated in _finish_loss_slots)."""
-        self._slot_launches = getattr(self, "_slot_launches", [])
         self._slot_launches.append((launch, pos))
 
     def _finish_loss_slots(self):
         self._flush_loss_terms()
-        pend = getattr(self, "_slot_launches", [])
-        n_slots = getattr(self, "_n_loss_slots", 0)
+        pend = self._slot_launches
+        n_slots = self._n_loss_slots
         if not pend or not n_slots:
             return
         self._alloc("loss_slots", 1024 * n_slots)
@@ -971,7 +967,7 @@ class PhasePlan(TowerPlan):
             args[pos] = self._ref("loss_slots")
             launch.args = tuple(args)
         self.bwd.append(Launch("loss_finalize_slots", (self._ref("loss_slots"), n_slots, self._ref("loss"),
-                                                       1 if getattr(self, "_loss_written", False) else 0),
+                                                       1 if self._loss_written else 0),
                                tag="loss-finalize"))
         self._slot_launches = []
 
@@ -992,14 +988,6 @@ class PhasePlan(TowerPlan):
             else:
                 runs.append([off, size, scale])
         for off, size, scale in runs:
-            if LOSS_SLOTS:
-                self._batch_loss_term(self.bwd, dict(mode=3, a=Ref(self.sess.params, off), lda=0, b=None, ldb=0, rows=size,
-                                                     c=1, target=0.0, gcoef=scale, pscale=0.5 * scale,
-                                                     da=Ref(self.sess.grads, off), ldda=0, acc_da=1, db=None, lddb=0,
-                                                     acc_db=0))
-                continue
-            else:
-                l = Launch("l2_reg", (Ref(self.sess.params, off), size, scale, self._ref("loss"), 1,
-                                      Ref(self.sess.grads, off), None), tag="l2-reg")
-                self._scratch(l, 6, "scratch_red")
-            self.bwd.append(l)
+            self._batch_loss_term(self.bwd, dict(mode=3, a=Ref(self.sess.params, off), lda=0, b=None, ldb=0, rows=size, c=1,
+                                                 target=0.0, gcoef=scale, pscale=0.5 * scale, da=Ref(self.sess.grads, off),
+                                                 ldda=0, acc_da=1, db=None, lddb=0, acc_db=0))

@@ -83,8 +83,8 @@ typedef struct {
  * ordinary record of the launch (bias, accumulate, shortcut gather apply to it); the other slices carry HYPEL_TILE_PLAIN:
  * their block writes its partial sum to its own c_off (a scratch region, addressed relative to `c` like every c_off)
  * and IGNORES the launch's bias / accumulate bit / shortcut operands.  The caller adds the partials to the output in a
- * fixed order afterwards (hypel_reduce_splits_multi_f32, accumulate flag set): deterministic, no atomics.  Not valid in
- * hypel_seg_gemm_stats_f32 launches and with HYPEL_GEMM_ACT_* (their epilogues need the whole sum). */
+ * fixed order afterwards (hypel_reduce_splits_multi_sized_f32, accumulate flag set): deterministic, no atomics.  Not
+ * valid in hypel_seg_gemm_stats_f32 launches and with HYPEL_GEMM_ACT_* (their epilogues need the whole sum). */
 #define HYPEL_TILE_PLAIN 1
 /* Short segments (data gradients through convolutions with <= 16 filters: K = 15 in the narrowest HYPELCNN level):
  * a segment whose `k` has HYPEL_SEG_PAIR_FLAG set (real k = k & ~flag, <= 16) shares ONE 32-column k-tile with the
