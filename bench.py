@@ -4,11 +4,15 @@
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR              (also write what the last timed step computed to DIR/*.npy)
+  python bench.py ... --full                          (also every secondary figure and check, see below)
 
 A "step" = next resident batch -> nhwc->pixel-major -> forward -> loss -> backward -> (RCCL all-reduce)
 -> TF1-Adam.  Inputs are synthetic (U[0,1) patches, uniform labels) and already resident in HBM.
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` for the dominant kernel
-(hypel_seg_gemm_f32: fp32 MFMA) and `cpu_baseline` (oracle restatement timed on the host cores).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps,
+dumps (if asked) and prints the line; `roofline` and `cpu_baseline` are null in it.  --full adds, after the timed
+steps: `roofline` for the dominant kernel (hypel_seg_gemm_f32: HIP events over an eager replay, clock / power over an
+untimed replay), `with_input_pipeline` (hypelcnn), the data-parallel weight check, and `cpu_baseline` (oracle
+restatement timed on the host cores).
 """
 import argparse
 import json
@@ -75,6 +79,19 @@ def build_model(batch, backend, workload="hypelcnn"):
     return ctx, train_step, lr, alg
 
 
+def is_split6(l):
+    """A seg_gemm launch on the split-operand kernels (include/hypel.h: HYPEL_GEMM_SPLIT6 in `accumulate` /
+    HYPEL_GEMM_MULTI_SPLIT6 in tile_width)."""
+    return bool(l.args[3] & 0x100) if l.name == "seg_gemm_multi_f32" else bool(l.args[14] & 0x8000)
+
+
+def split6_flop_share(ct):
+    """(share of the step's seg_gemm FLOP on the split-operand kernels, number of such launches) from the plan alone:
+    no launch runs."""
+    gl = [l for l in ct.plan.fwd + ct.plan.bwd if l.name.startswith("seg_gemm")]
+    return sum(l.flops for l in gl if is_split6(l)) / max(1, sum(l.flops for l in gl)), sum(1 for l in gl if is_split6(l))
+
+
 def measure_gemm_events(ct, sess, lr, steps):
     """Serial replay of the same step (every launch on the main stream, no graph) with a HIP event pair around
     every hypel_seg_gemm_f32 launch, recorded on the stream the kernels are launched on."""
@@ -98,11 +115,7 @@ def measure_gemm_events(ct, sess, lr, steps):
         total_ms += sum(a.elapsed_time(b) for a, b, _ in evs)
         n_launch += len(evs)
         total_flops += sum(fl for _, _, fl in evs)
-    def is_split(l):  # include/hypel.h: HYPEL_GEMM_SPLIT6 in `accumulate` / HYPEL_GEMM_MULTI_SPLIT6 in tile_width
-        return bool(l.args[3] & 0x100) if l.name == "seg_gemm_multi_f32" else bool(l.args[14] & 0x8000)
-    gl = [l for l, _ in launches if l.name.startswith("seg_gemm")]
-    measure_gemm_events.split_flop_share = sum(l.flops for l in gl if is_split(l)) / max(1, sum(l.flops for l in gl))
-    measure_gemm_events.split_launches = sum(1 for l in gl if is_split(l))
+    measure_gemm_events.split_flop_share, measure_gemm_events.split_launches = split6_flop_share(ct)
     return total_ms, total_flops, n_launch
 
 
@@ -551,13 +564,16 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU per step (0 = the workload's default)")
     ap.add_argument("--workload", default="hypelcnn", choices=["hypelcnn", "dualcnn", "cyclegan", "cut"],
                     help="hypelcnn = BASELINE.json headline (configs[1]); the others are extra evidence lines")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything the headline does not need: roofline "
+                         "(HIP-event replay, clock / power), input-pipeline step, data-parallel weight check, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--sync-bn", action="store_true",
                     help="N > 1: batch-norm statistics over the global batch (one small RCCL collective per BN layer and "
                          "direction; default: per-rank statistics)")
     ap.add_argument("--no-input-pipeline", action="store_true",
-                    help="skip the second measurement (step fed by the device BatchIterator + augmentation kernel)")
+                    help="--full without the second measurement (step fed by the device BatchIterator + augmentation kernel)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (loss, logits / per-phase losses, "
                          "updated weights, gradients) to DIR/<name>.npy; the pre-warm becomes a fixed step count so "
@@ -676,20 +692,22 @@ def main():
         note_collective()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
+    loss = loss_fn()
+    assert np.isfinite(loss), "non-finite loss"
+    # From here to the result line everything is --full only: a plain run goes straight to the line.
     # Shader clock / power of this rank's GPU: sampled over an UNTIMED replay of the same steps behind the timed region, never
     # inside it -- a host thread that reads sysfs (every read is a query to the GPU's power firmware) every 4 ms cost the
     # launch-bound CycleGAN step 15 %, CUT 1.3 % and the headline 0.6 % when it ran under the timer (round 6, NOTES 6.L).
-    clock = ClockSampler(torch.cuda.current_device())  # (the device this rank actually runs on, not LOCAL_RANK: ranks may share one)
-    if classifier and not use_dist:
-        n_clock = max(3, min(200, int(0.5 / max(dt / args.steps, 1e-6)) + 1))
-        with clock:
-            for _ in range(n_clock):
-                one_step()
-            torch.cuda.synchronize()
-    loss = loss_fn()
-    assert np.isfinite(loss), "non-finite loss"
+    if args.full:
+        clock = ClockSampler(torch.cuda.current_device())  # (the device this rank actually runs on, not LOCAL_RANK: ranks may share one)
+        if classifier and not use_dist:
+            n_clock = max(3, min(200, int(0.5 / max(dt / args.steps, 1e-6)) + 1))
+            with clock:
+                for _ in range(n_clock):
+                    one_step()
+                torch.cuda.synchronize()
     in_sync = None
-    if use_dist and classifier:
+    if args.full and use_dist and classifier:
         # data-parallel invariant: every rank holds bit-identical weights after the same all-reduced updates
         digest = torch.stack([sess.params.double().sum(), sess.params.double().abs().max()])
         lo, hi = digest.clone(), digest.clone()
@@ -700,7 +718,7 @@ def main():
         in_sync = bool(torch.equal(lo, hi))
 
     pipeline = None
-    if classifier and args.workload == "hypelcnn" and not args.no_input_pipeline:
+    if args.full and classifier and args.workload == "hypelcnn" and not args.no_input_pipeline:
         # second, clearly labelled measurement: the same step fed by the device-side input pipeline (row a10 of the
         # scope table): BatchIterator over a resident pool + fused gather/augmentation kernel inside every step
         it = input_pipeline_iterator(be, nb, patch, chans, classes, rank)
@@ -739,7 +757,7 @@ def main():
 
     roof = None
     cpu = None
-    if rank == 0 and classifier:
+    if args.full and rank == 0 and classifier:
         ev_steps = max(2, min(5, args.steps))
         ms, flops, n_launch = measure_gemm_events(ct, sess, lr, ev_steps)
         achieved = flops / (ms * 1e-3) / 1e12
@@ -776,7 +794,7 @@ def main():
             roof["committed_profiles"] = {"mfma_busy_pmc": busy["busy"], "mfma_useful_pmc": busy["useful"], "source": busy_source}
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(workload=args.workload)
-    if rank == 0 and not classifier:
+    if args.full and rank == 0 and not classifier:
         step_ms_mean = dt / args.steps * 1e3
         gen_ms, gen_flops, n_gen, n_launch = measure_gan_events(gan_ops, nb, bands, max(2, min(5, args.steps)))
         boundary_us = 1.7  # MI355X_MICROARCH.md price list, "boundary": 1.45-1.9 us per dependent kernel boundary
@@ -850,7 +868,7 @@ def main():
                "ms_per_step_p10_p90": [step_ms[len(step_ms) // 10], step_ms[(9 * len(step_ms)) // 10]],
                "prewarm_steps": n_prewarm, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": ("f32 (3 x bf16 split operands, 6 partial products, fp32 accumulate)"
-                         if classifier and roof and roof.get("split6_flop_share") else "f32"),
+                         if classifier and split6_flop_share(ct)[0] else "f32"),
                "data": "synthetic", "config": cfg_d, "roofline": roof, "cpu_baseline": cpu}
         if pipeline is not None:
             out["with_input_pipeline"] = pipeline

@@ -25,5 +25,5 @@ done; done
 # the headline step with the ablation library (its data gradients of the nt 128 x 128 form only; numbers wrong, timing only)
 for pass in 1 2; do for lib in default ablb; do
   if [ $lib = default ]; then unset HYPEL_LIB_PATH; else export HYPEL_LIB_PATH=$PWD/hypelcnn_amd/csrc/variants/$lib/libhypel_hip.so; fi
-  echo "step $lib pass $pass $(timeout 200 python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-input-pipeline 2>&1 | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["roofline"]["gemm_ms_per_step"] if "gemm_ms_per_step" in d["roofline"] else "")' 2>&1 | tail -1)"
+  echo "step $lib pass $pass $(timeout 200 python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-input-pipeline 2>&1 | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["roofline"]["gemm_ms_per_step"] if "gemm_ms_per_step" in d["roofline"] else "")' 2>&1 | tail -1)"
 done; done

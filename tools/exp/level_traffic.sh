@@ -12,5 +12,5 @@ for v in "$@"; do
   F=$(find /tmp/lt_f -name "*counter_collection.csv" | head -1); W=$(find /tmp/lt_w -name "*counter_collection.csv" | head -1)
   echo "== $VAR=$v"
   python tools/pmc_traffic_per_launch.py $F $W --workload hypelcnn | grep -E "connector_._conv1x1|^all"
-  python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-input-pipeline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', round(d['ms_per_step'],4), 'gemm ms', round(d['roofline']['gemm_ms_per_step'],4))"
+  python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-input-pipeline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', round(d['ms_per_step'],4), 'gemm ms', round(d['roofline']['gemm_ms_per_step'],4))"
 done
