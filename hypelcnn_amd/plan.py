@@ -78,21 +78,6 @@ class Storage:
         return self.npix * self.nb
 
 
-def valid_taps(h, w, k, oy, ox):
-    """Taps (i, j) of a kxk SAME kernel that read a real pixel for output (oy, ox); pad_before=(k-1)//2."""
-    pb = (k - 1) // 2
-    out = []
-    for i in range(k):
-        iy = oy + i - pb
-        if iy < 0 or iy >= h:
-            continue
-        for j in range(k):
-            ix = ox + j - pb
-            if 0 <= ix < w:
-                out.append((i, j, iy * w + ix))
-    return out
-
-
 MSE_PARTIALS = 1024  # include/hypel.h HYPEL_MSE_PARTIALS
 DP_SYNC_WORK = 0.5  # share of the filter-gradient work before the sync point
 # Gradient buckets of the data-parallel exchange: two by default (one sync point: >= 60 % of the bytes leave under the
@@ -565,10 +550,11 @@ class TowerPlan:
         return parts
 
     def _emit_gemm(self, lst, tables, n, a_ref, lda, ta, b_ref, ldb, tb, c_ref, ldc, bias_ref, accumulate, tag,
-                   allow_split=True, res=None, stats=None, pair=False, hint=None, flags=0, kslice=False):
+                   allow_split=True, res=None, stats=None, pair=False, hint=None, flags=0, kslice=False, sp6=None):
         """res = (ref, ld, start_ref or None): fold a shortcut gradient into the epilogue (hypel_seg_gemm_res_f32).
         stats = floats of the per-tile statistics scratch: hypel_seg_gemm_stats_f32 (single group, no accumulate).
-        kslice: the launch may be balanced with K-slice records (dense output, ldc = n)."""
+        kslice: the launch may be balanced with K-slice records (dense output, ldc = n).
+        sp6: the kernel family, when the caller already chose it (_split6) to shape the tables."""
         split = self._split_k(tables, n, lda, ta, ldb, tb, ldc) if allow_split and res is None else None
         if split is not None:
             stab, S, c_min, count = split
@@ -587,8 +573,9 @@ class TowerPlan:
         if HINT_OVERRIDE and tag in HINT_OVERRIDE:  # per-launch A/B: HYPEL_HINT_OVERRIDE="fwd:conv_enc_2=1,dgrad:fc_0=2"
             hint = HINT_OVERRIDE[tag]
         single_seg = bool(not ta and all(len(segs) == 1 for _, segs, _ in tables.groups))
-        sp6 = self._split6(tag, tables, n, ta, tb, flags,
-                           pair and any(k <= 16 for _, gs, _ in tables.groups for _, _, k in gs))
+        if sp6 is None:
+            sp6 = self._split6(tag, tables, n, ta, tb, flags,
+                               pair and any(k <= 16 for _, gs, _ in tables.groups for _, _, k in gs))
         if sp6:
             pair, hint, single_seg = False, sp6, False
             accumulate = int(accumulate) | GEMM_SPLIT6
@@ -859,12 +846,11 @@ class TowerPlan:
                     pos += src.c * (C - lay["col0"][r])
                 lay["dense_size"] = pos
                 assert pos == sum(b.w.size for b in brs)
-                if any(w_ in MERGE_LEVELS and co <= max(MERGE_PASS_MAX_COUT[w_], MERGE_FWD_MAX_COUT_SPLIT if GEMM_SPLIT == 6 else 0)
-                       and not (w_ == "fwd" and node.has_bias) for w_ in ("fwd", "dgrad")):
-                    # these passes read the packed image (the filter gradient does not)
-                    lay["packed"] = True
-                    self._alloc(lay["buf"], len(offs) * src.c * C)
         self._level_layouts[idx] = lay
+        if lay is not None and (self._level_pass(idx, node, "fwd") or self._level_pass(idx, node, "dgrad")):
+            # these passes read the packed image (the filter gradient does not)
+            lay["packed"] = True
+            self._alloc(lay["buf"], len(lay["offs"]) * lay["cin"] * lay["C"])
         return lay
 
     def _level_pass(self, idx, node, what):
@@ -891,14 +877,9 @@ class TowerPlan:
             if lay is None or not lay.get("packed"):
                 continue
             dst0 = (self._ref(lay["buf"]).ptr() - base.ptr()) // 4
-            for bi, b in enumerate(node.branches):
-                pb = (b.k - 1) // 2
-                for i in range(b.k):
-                    for j in range(b.k):
-                        d = lay["index"][(i - pb, j - pb)]
-                        ents.append((b.w.offset + (i * b.k + j) * lay["cin"] * lay["co"],
-                                     dst0 + d * lay["cin"] * lay["C"] + bi * lay["co"], lay["cin"], lay["co"], lay["co"],
-                                     lay["C"], 0, 0))
+            cin, co, C = lay["cin"], lay["co"], lay["C"]
+            ents += [(w_, dst0 + lay["index"][(dy, dx)] * cin * C + col, cin, co, co, C, 0, 0)
+                     for dy, dx, w_, col, _ in self._taps(self._columns(node), cin)]
         if not ents:
             return
         t = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
@@ -906,59 +887,159 @@ class TowerPlan:
         self.fwd.insert(pos, Launch("copy_blocks_f32", (base, Ref(t), len(ents), max(e[2] * e[3] for e in ents)),
                                     nbytes=8 * sum(e[2] * e[3] for e in ents), tag="level-pack"))
 
-    def _fwd_level_merged(self, idx, node, lay, s_st, ybuf, c, h, w):
+    # ------------------------------------------------------------------ convolution taps
+    @staticmethod
+    def _columns(node):
+        """[(branch, its first output column)] in concat order."""
+        cols, col = [], 0
+        for b in node.branches:
+            cols.append((b, col))
+            col += b.cout
+        return cols
+
+    @staticmethod
+    def _taps(branches, cin, lay=None):
+        """The taps of a convolution as (dy, dx, w, col, n): input offset, element offset of the tap's [cin x n] weight
+        block (at its first column) in the buffer the pass reads, and the output columns [col, col + n) of Y / dY it covers.
+        branches = [(branch, col)]: taps in branch order, (i, j) row-major, in the parameter buffer.  A merged level (lay):
+        its ring-major input offsets over the packed image W_pack[d] = [cin x C] (wpack:<idx>), columns [col0[ring], C)."""
+        if lay is not None:
+            C, col0 = lay["C"], lay["col0"]
+            return [(dy, dx, d * cin * C + col0[r], col0[r], C - col0[r]) for d, (dy, dx, r) in enumerate(lay["offs"])]
+        return [(i - (b.k - 1) // 2, j - (b.k - 1) // 2, b.w.offset + (i * b.k + j) * cin * b.cout, col, b.cout)
+                for b, col in branches for i in range(b.k) for j in range(b.k)]
+
+    @staticmethod
+    def _fwd_segs(taps, s_st, h, w, p):
+        """Forward segments of output pixel p: one per tap that reads a real input pixel, over all Cin reduction columns."""
+        py, px = divmod(p, w)
+        return [(s_st.pix_off((py + dy) * w + px + dx), w_, s_st.c) for dy, dx, w_, _, _ in taps
+                if 0 <= py + dy < h and 0 <= px + dx < w]
+
+    @staticmethod
+    def _partial_copies(segs, S, kp_n=1, ldb=0):
+        """One output group's segments [(a_off, b_off, k)] cut into kp_n channel parts -- every segment's reduction columns
+        cut at multiples of 16, B advancing ldb elements per column -- and each part into S contiguous chunks of segments.
+        Yields (kp, si, chunk), channel part major; each writes its own partial copy of the group's output."""
+        def cut(k, q):
+            return k if q == kp_n else min(k, (k * q // kp_n + 15) // 16 * 16)
+
+        for kp in range(kp_n):
+            part = [(a + cut(k, kp), b + cut(k, kp) * ldb, cut(k, kp + 1) - cut(k, kp)) for a, b, k in segs]
+            for si in range(S):
+                yield kp, si, part[len(part) * si // S:len(part) * (si + 1) // S]
+
+    @staticmethod
+    def _channel_parts(cin, h, w):
+        """L2 locality: the tiles of one 128-row chunk re-read the chunk's pixel blocks of X once per tap.  When those
+        blocks (pixels x 128 rows x Cin) exceed what an XCD's 4 MB L2 keeps, every tap goes back to HBM (measured: 1.56 GB
+        fetched for 117 MB of operands at Cin = 240).  The reduction dimension is then cut into this many channel parts,
+        processed one after the other inside a chunk (tile order key), each writing its own partial copy like a tap chunk."""
+        return max(1, min(4, -(-(h * w * GEMM_BM * cin * 4) // L2_CHUNK_BYTES), cin // 16))
+
+    def _reduce_tap_copies(self, ybuf, rows, c, col, n, copies, bias=None):
+        """Add partial copies 1 .. copies - 1 of the output columns [col, col + n) -- stored behind Y in `ybuf`, rows x c
+        each -- into copy 0 = Y (+ bias: every partial copy would have added it)."""
+        if copies > 1:
+            self.fwd.append(Launch("reduce_splits_f32", (self._ref(ybuf, rows * c + col), rows * c, copies - 1,
+                                                         self._ref(ybuf, col), rows * n, 1, bias, n, c),
+                                   nbytes=4 * rows * n * (copies + 1), tag="tap-split-reduce"))
+
+    def _fwd_level_merged(self, node, lay, s_st, ybuf, c, h, w):
         """Forward pass of a merged level: per output pixel and ring r the product
-        Y[p][:, col0[r]:] (+)= sum_{d in ring r, valid} X[p + d] . W_pack[d][:, col0[r]:], rings with more than
-        MAX_TAPS_PER_TILE offsets cut into chunks; every (ring chunk, channel part) writes its own copy of Y (copy 0 is Y
-        itself), summed per branch by hypel_reduce_splits_f32 as for the tap splits of the unmerged form.
-        Returns the number of copies."""
-        nb = self.nb
-        src = node.sources[0]
+        Y[p][:, col0[r]:] (+)= sum_{d in ring r, valid} X[p + d] . W_pack[d][:, col0[r]:].  The kernel family is chosen on
+        these products (their MACs do not depend on how they are cut); rings with more offsets than that family's taps per
+        tile are cut into chunks, and on the fp32 kernels the reduction into channel parts.  Every (ring chunk, channel
+        part) writes its own copy of Y (copy 0 is Y itself), summed per branch as for the tap splits of the unmerged form."""
+        nb, C = self.nb, lay["C"]
         rows_all = node.out.npix * nb
-        C, cin = lay["C"], lay["cin"]
-        narrow16 = lay["co"] <= 16 and C <= 64
-        on_split = GEMM_SPLIT == 6 and not narrow16 and C > GEMM_SPLIT_MIN_N  # (the size rule of _split6 may still say fp32)
-        ring_sizes = [sum(1 for o in lay["offs"] if o[2] == r) for r in range(lay["rmax"] + 1)]
-        max_taps = MERGE_MAX_TAPS or (MERGE_SPLIT_MAX_TAPS if on_split else MAX_TAPS_PER_TILE)
-        S_r = [max(1, -(-sz // max_taps)) for sz in ring_sizes]
-        ws = h * w * GEMM_BM * src.c * 4
-        kp_n = max(1, min(4, -(-ws // L2_CHUNK_BYTES), src.c // 16)) if not on_split or MERGE_SPLIT_KPARTS else 1
-        kcuts = [min(src.c, (src.c * q // kp_n + 15) // 16 * 16) for q in range(kp_n)] + [src.c]
-        chunk0 = [sum(S_r[:r]) for r in range(lay["rmax"] + 2)]  # first chunk index of ring r
-        n_copies = chunk0[-1] * kp_n
-        if n_copies > 1:
-            self._alloc(ybuf, rows_all * c * n_copies)
-        tb = GemmTables()
+        taps = self._taps(self._columns(node), lay["cin"], lay)
+        rings = [[t for t, o in zip(taps, lay["offs"]) if o[2] == r] for r in range(lay["rmax"] + 1)]
+        whole = GemmTables()  # one group per (pixel, ring), pixel major
         for p in range(h * w):
-            py, px = p // w, p % w
-            for r in range(lay["rmax"] + 1):
-                col0 = lay["col0"][r]
-                valid = [(d, (py + dy) * w + (px + dx)) for d, (dy, dx, rr) in enumerate(lay["offs"])
-                         if rr == r and 0 <= py + dy < h and 0 <= px + dx < w]
-                for kp in range(kp_n):
-                    k0, k1 = kcuts[kp], kcuts[kp + 1]
-                    segs = [(s_st.pix_off(pin) + k0, (d * cin + k0) * C + col0, k1 - k0) for d, pin in valid]
-                    for si in range(S_r[r]):
-                        chunk = segs[len(segs) * si // S_r[r]:len(segs) * (si + 1) // S_r[r]]
-                        copy = (chunk0[r] + si) * kp_n + kp
-                        tb.add_group(copy * rows_all * c + p * nb * c + col0, chunk, nb, subkey=kp, n=C - col0)
-        flags = GEMM_VAR_N | (GEMM_MFMA16X4 if narrow16 else 0)
+            for ring in rings:
+                whole.add_group(p * nb * c + ring[0][3], self._fwd_segs(ring, s_st, h, w, p), nb, n=ring[0][4])
+        flags = GEMM_VAR_N | (GEMM_MFMA16X4 if lay["co"] <= 16 and C <= 64 else 0)
+        tag = f"fwd:{node.branches[0].scope}/merged"
+        sp6 = self._split6(tag, whole, C, 0, 0, flags, False)
+        max_taps = MERGE_MAX_TAPS or (MERGE_SPLIT_MAX_TAPS if sp6 else MAX_TAPS_PER_TILE)
+        S_r = [max(1, -(-len(ring) // max_taps)) for ring in rings]
+        kp_n = self._channel_parts(lay["cin"], h, w) if not sp6 or MERGE_SPLIT_KPARTS else 1
+        chunk0 = [sum(S_r[:r]) for r in range(len(rings) + 1)]  # first chunk index of ring r
+        if chunk0[-1] * kp_n > 1:
+            self._alloc(ybuf, rows_all * c * chunk0[-1] * kp_n)
+        tb = GemmTables()
+        for gi, (c_off, segs, _) in enumerate(whole.groups):
+            r = gi % len(rings)
+            for kp, si, chunk in self._partial_copies(segs, S_r[r], kp_n, C):
+                tb.add_group(((chunk0[r] + si) * kp_n + kp) * rows_all * c + c_off, chunk, nb, subkey=kp, n=whole.ns[gi])
         pos = len(self.fwd)
         self._emit_gemm(self.fwd, tb, C, self._ref(s_st.buf), s_st.ld, 0, self._ref(lay["buf"]), C, 0, self._ref(ybuf), c,
-                        None, 0, f"fwd:{node.branches[0].scope}/merged", allow_split=False, hint=MERGE_FWD_HINT,
-                        flags=flags)  # (a split-operand launch takes its own width, _split6_width)
+                        None, 0, tag, allow_split=False, hint=MERGE_FWD_HINT, flags=flags,
+                        sp6=sp6)  # (a split-operand launch takes its own width, _split6_width)
         if len(self.fwd) > pos:
             self.fwd[pos].kparts = kp_n
-        choff = 0
-        for bi, b in enumerate(node.branches):
-            copies_b = chunk0[(b.k - 1) // 2 + 1] * kp_n  # the copies that hold columns of this branch: 0 .. copies_b - 1
-            if copies_b > 1:
-                self.fwd.append(Launch("reduce_splits_f32", (self._ref(ybuf, rows_all * c + choff), rows_all * c,
-                                                             copies_b - 1, self._ref(ybuf, choff), rows_all * b.cout, 1,
-                                                             None, b.cout, c),
-                                       nbytes=4 * rows_all * b.cout * (copies_b + 1), tag="tap-split-reduce"))
-            choff += b.cout
-        return n_copies
+        for b, col in self._columns(node):  # the copies that hold columns of branch b: 0 .. chunk0[ring of b + 1] * kp_n - 1
+            self._reduce_tap_copies(ybuf, rows_all, c, col, b.cout, chunk0[(b.k - 1) // 2 + 1] * kp_n)
+
+    def _fwd_conv(self, node, aux, s_st, ybuf, c, h, w, bias_ref):
+        """Forward pass of a convolution, per branch.  Tap splitting: a block that walks all 49 taps of a 7x7 branch runs
+        ~4x longer than the average tile and finishes alone at ~40 % MFMA utilisation.  Branches with more than
+        MAX_TAPS_PER_TILE taps have their tap list cut into S chunks (x the level's channel parts); chunk s writes a partial
+        copy Y_s of the output (same layout, stored behind Y in the same buffer) and a strided reduce adds Y_1.. into Y."""
+        nb, cin = self.nb, s_st.c
+        rows_all = node.out.npix * nb
+        splits = {}
+        kparts = 1
+        if nb >= TAP_SPLIT_MIN_BATCH:
+            for b in node.branches:
+                taps = min(b.k, h) * min(b.k, w)
+                if taps > MAX_TAPS_PER_TILE:
+                    splits[id(b)] = (taps + MAX_TAPS_PER_TILE - 1) // MAX_TAPS_PER_TILE
+            if splits:
+                kparts = self._channel_parts(cin, h, w)
+                if kparts > 1:
+                    for b in node.branches:
+                        if b.k > 1:
+                            splits[id(b)] = splits.get(id(b), 1) * kparts
+        s_max = max(splits.values()) if splits else 1
+        if s_max > 1:
+            self._alloc(ybuf, rows_all * c * s_max)
+        by_cout = {}
+        for b, col in self._columns(node):
+            # with a bias, split branches go into a launch of their own (no bias in the GEMM: the reduce adds it)
+            by_cout.setdefault((b.cout, bias_ref is not None and splits.get(id(b), 1) > 1), []).append((b, col))
+        # batch-norm statistics in the epilogue: a lone 1x1 branch on contiguous input writes ONE [rows x c] matrix
+        fuse_stats = (node.has_bn and node.training and len(node.branches) == 1
+                      and node.branches[0].k == 1 and s_st.contiguous and s_max == 1 and c > 16
+                      and not self._small_bn(node, rows_all))
+        aux["stats_in_gemm"] = fuse_stats
+        for (cout, split_launch), items in by_cout.items():
+            tb = GemmTables()
+            kp_used = 1
+            for b, col in items:
+                if b.k == 1 and s_st.contiguous:
+                    tb.add_group(col, [(s_st.pix_off(0), b.w.offset, cin)], rows_all)
+                    continue
+                S = splits.get(id(b), 1)
+                kp_n = kparts if S >= kparts and S % kparts == 0 and kparts > 1 else 1
+                kp_used = max(kp_used, kp_n)
+                S_tap = S // kp_n
+                taps = self._taps([(b, col)], cin)
+                for p in range(h * w):
+                    for kp, si, chunk in self._partial_copies(self._fwd_segs(taps, s_st, h, w, p), S_tap, kp_n, cout):
+                        tb.add_group((kp * S_tap + si) * rows_all * c + p * nb * c + col, chunk, nb, subkey=kp)
+            # the kernel indexes bias by (c_off % ldc) + column, so merged branches share one launch
+            pos = len(self.fwd)
+            self._emit_gemm(self.fwd, tb, cout, self._ref(s_st.buf), s_st.ld, 0, Ref(self.sess.params), cout, 0,
+                            self._ref(ybuf), c, None if split_launch else bias_ref, 0,
+                            f"fwd:{items[0][0].scope}" + ("/split" if split_launch else ""), allow_split=False,
+                            stats=((rows_all + GEMM_BM - 1) // GEMM_BM) * 2 * c if fuse_stats else None)
+            if len(self.fwd) > pos:
+                self.fwd[pos].kparts = kp_used
+            for b, col in items:
+                self._reduce_tap_copies(ybuf, rows_all, c, col, cout, splits.get(id(b), 1),
+                                        None if bias_ref is None else bias_ref + col)
 
     def _fwd_linear(self, idx, node):
         nb = self.nb
@@ -971,94 +1052,16 @@ class TowerPlan:
         y_st = Storage(ybuf, nb, c, None, 0, c, out.npix)
         aux["y"] = y_st
         bias_ref = self._p(aux["bias"]) if node.has_bias else None
-        w_base = aux["w0"].offset
 
         if node.kind == "conv":
-            src = node.sources[0]
-            s_st = self.storage_of(src)
-            h, w = src.hw
-            rows_all = out.npix * nb
+            s_st = self.storage_of(node.sources[0])
+            h, w = node.sources[0].hw
             lay = self._level_pass(idx, node, "fwd")
             if lay is not None:
                 aux["stats_in_gemm"] = False
-                self._fwd_level_merged(idx, node, lay, s_st, ybuf, c, h, w)
-            # Tap splitting: a block that walks all 49 taps of a 7x7 branch runs ~4x longer than the average tile
-            # and finishes alone at ~40 % MFMA utilisation.  Branches with more than MAX_TAPS_PER_TILE taps have
-            # their tap list cut into S chunks; chunk s writes a partial copy Y_s of the output (same layout,
-            # stored behind Y in the same buffer) and a strided reduce adds Y_1.. into Y.
-            splits = {}
-            kparts = 1
-            if lay is None and nb >= TAP_SPLIT_MIN_BATCH:
-                for b in node.branches:
-                    taps = min(b.k, h) * min(b.k, w)
-                    if taps > MAX_TAPS_PER_TILE:
-                        splits[id(b)] = (taps + MAX_TAPS_PER_TILE - 1) // MAX_TAPS_PER_TILE
-                # L2 locality: the tiles of one 128-row chunk re-read the chunk's pixel blocks of X once per tap.  When
-                # those blocks (pixels x 128 rows x Cin) exceed what an XCD's 4 MB L2 keeps, every tap goes back to
-                # HBM (measured: 1.56 GB fetched for 117 MB of operands at Cin = 240).  The reduction dimension is then
-                # cut into channel parts that are processed one after the other inside a chunk (tile order key), each
-                # writing its own partial copy like the tap chunks do.
-                if splits:
-                    ws = h * w * GEMM_BM * src.c * 4
-                    kparts = max(1, min(4, -(-ws // L2_CHUNK_BYTES), src.c // 16))
-                    if kparts > 1:
-                        for b in node.branches:
-                            if b.k > 1:
-                                splits[id(b)] = splits.get(id(b), 1) * kparts
-            s_max = max(splits.values()) if splits else 1
-            if s_max > 1:
-                self._alloc(ybuf, rows_all * c * s_max)
-            choff = 0
-            by_cout = {}
-            for b in (node.branches if lay is None else ()):
-                # with a bias, split branches go into a launch of their own (no bias in the GEMM: the reduce adds it)
-                key = (b.cout, bias_ref is not None and splits.get(id(b), 1) > 1)
-                by_cout.setdefault(key, []).append((b, choff))
-                choff += b.cout
-            # batch-norm statistics in the epilogue: a lone 1x1 branch on contiguous input writes ONE [rows x c] matrix
-            fuse_stats = (node.has_bn and node.training and len(node.branches) == 1
-                          and node.branches[0].k == 1 and s_st.contiguous and s_max == 1 and c > 16
-                          and not self._small_bn(node, rows_all) and lay is None)
-            aux["stats_in_gemm"] = fuse_stats
-            for (cout, split_launch), items in by_cout.items():
-                biased_launch = not split_launch
-                tb = GemmTables()
-                kp_used = 1
-                for b, off in items:
-                    if b.k == 1 and s_st.contiguous:
-                        tb.add_group(off, [(s_st.pix_off(0), b.w.offset, src.c)], out.npix * nb)
-                        continue
-                    S = splits.get(id(b), 1)
-                    kp_n = kparts if S >= kparts and S % kparts == 0 and kparts > 1 else 1
-                    kp_used = max(kp_used, kp_n)
-                    S_tap = S // kp_n
-                    kcuts = [min(src.c, (src.c * q // kp_n + 15) // 16 * 16) for q in range(kp_n)] + [src.c]
-                    for p in range(h * w):
-                        taps = valid_taps(h, w, b.k, p // w, p % w)
-                        for kp in range(kp_n):
-                            k0, k1 = kcuts[kp], kcuts[kp + 1]
-                            segs = [(s_st.pix_off(pin) + k0, b.w.offset + ((i * b.k + j) * src.c + k0) * cout, k1 - k0)
-                                    for (i, j, pin) in taps]
-                            for si in range(S_tap):
-                                chunk = segs[len(segs) * si // S_tap:len(segs) * (si + 1) // S_tap]
-                                tb.add_group((kp * S_tap + si) * rows_all * c + p * nb * c + off, chunk, nb, subkey=kp)
-                # the kernel indexes bias by (c_off % ldc) + column, so merged branches share one launch
-                pos = len(self.fwd)
-                self._emit_gemm(self.fwd, tb, cout, self._ref(s_st.buf), s_st.ld, 0, Ref(self.sess.params), cout, 0,
-                                self._ref(ybuf), c, bias_ref if biased_launch else None, 0,
-                                f"fwd:{items[0][0].scope}" + ("/split" if not biased_launch and bias_ref is not None else ""),
-                                allow_split=False,
-                                stats=((rows_all + GEMM_BM - 1) // GEMM_BM) * 2 * c if fuse_stats else None)
-                if len(self.fwd) > pos:
-                    self.fwd[pos].kparts = kp_used
-                for b, off in items:
-                    S = splits.get(id(b), 1)
-                    if S > 1:
-                        # a split branch of a biased convolution gets its bias here (every partial copy would add it)
-                        self.fwd.append(Launch("reduce_splits_f32", (self._ref(ybuf, rows_all * c + off), rows_all * c,
-                                                                     S - 1, self._ref(ybuf, off), rows_all * cout, 1,
-                                                                     None if bias_ref is None else bias_ref + off, cout, c),
-                                               nbytes=4 * rows_all * cout * (S + 1), tag="tap-split-reduce"))
+                self._fwd_level_merged(node, lay, s_st, ybuf, c, h, w)
+            else:
+                self._fwd_conv(node, aux, s_st, ybuf, c, h, w, bias_ref)
         elif node.kind == "blockdense":
             # P independent small dense maps (one per band slice) as ONE grouped GEMM: group p reads the source columns
             # of its slice, multiplies by its own weights and writes columns [p*cout, (p+1)*cout) of the output
@@ -1385,60 +1388,33 @@ class TowerPlan:
             h, w = src.hw
             if self._needs_grad(src):
                 gst, acc = self._grad_target(src)
-                choff = 0
                 by_cout = {}
-                for b in node.branches:
-                    by_cout.setdefault(b.cout, []).append((b, choff))
-                    choff += b.cout
-                lay = self._level_pass(idx, node, "dgrad")
-                if lay is not None:
-                    by_cout = {lay["co"]: [(b, None) for b in node.branches]}  # one launch over the packed image
+                for b, col in self._columns(node):
+                    by_cout.setdefault(b.cout, []).append((b, col))
                 w_ref, w_ld, mtag = Ref(self.sess.params), None, ""
+                lay = self._level_pass(idx, node, "dgrad")
+                if lay is not None:  # one launch over the packed image
+                    by_cout = {lay["co"]: self._columns(node)}
+                    w_ref, w_ld, mtag = self._ref(lay["buf"]), lay["C"], "/merged"
                 for cout, items in by_cout.items():
+                    taps = self._taps(items, src.c, lay)
                     tb = GemmTables()
-                    if lay is not None:
-                        # merged level: an input pixel sums, per input offset d (output pixel pin - d), ONE segment over the
-                        # columns [col0[ring], C) of dY against the same columns of W_pack[d] -- 49 instead of 84 segments
-                        # of 15 .. 60 columns at the centre of a 7x7 patch
-                        w_ref, w_ld, mtag = self._ref(lay["buf"]), lay["C"], "/merged"
-                        per_pixel = []
-                        for pin in range(h * w):
-                            iy, ix = pin // w, pin % w
-                            segs = []
-                            for d, (ofy, ofx, r) in enumerate(lay["offs"]):
-                                oy, ox = iy - ofy, ix - ofx
-                                if 0 <= oy < h and 0 <= ox < w:
-                                    col0 = lay["col0"][r]
-                                    segs.append(((oy * w + ox) * nb * c + col0, d * lay["cin"] * lay["C"] + col0,
-                                                 lay["C"] - col0))
-                            per_pixel.append(segs)
-                    elif len(items) == 1 and items[0][0].k == 1 and gst.contiguous:
-                        b, off = items[0]
-                        tb.add_group(gst.pix_off(0), [(off, b.w.offset, cout)], src.npix * nb)
-                        per_pixel = None
+                    per_pixel = []
+                    if len(taps) == 1 and gst.contiguous:  # a lone 1x1 branch: ONE group over all pixels
+                        _, _, w_, col, n = taps[0]
+                        tb.add_group(gst.pix_off(0), [(col, w_, n)], src.npix * nb)
                     else:
-                        per_pixel = []
-                        for pin in range(h * w):
-                            iy, ix = pin // w, pin % w
-                            segs = []
-                            for b, off in items:
-                                pb = (b.k - 1) // 2
-                                for i in range(b.k):
-                                    oy = iy - (i - pb)
-                                    if oy < 0 or oy >= h:
-                                        continue
-                                    for j in range(b.k):
-                                        ox = ix - (j - pb)
-                                        if 0 <= ox < w:
-                                            segs.append(((oy * w + ox) * nb * c + off,
-                                                         b.w.offset + (i * b.k + j) * src.c * cout, cout))
-                            per_pixel.append(segs)
+                        # input pixel (iy, ix) sums one segment per tap: the tap's columns of dY at output pixel
+                        # (iy - dy, ix - dx) -- merged level: 49 instead of 84 segments of 15 .. 60 columns at the centre
+                        # of a 7x7 patch
+                        per_pixel = [[(((iy - dy) * w + ix - dx) * nb * c + col, w_, n) for dy, dx, w_, col, n in taps
+                                      if 0 <= iy - dy < h and 0 <= ix - dx < w] for iy in range(h) for ix in range(w)]
                     # Segment splitting, the data-gradient twin of the forward tap splitting: an input pixel of a
                     # multi-kernel level sums up to sum(k^2) segments (165 for the five kernels of DUALCNN) and its
                     # block runs that much longer than a corner pixel's.  The segment list is cut into S chunks
                     # that write partial copies of dX (same layout, in scratch), processed chunk after chunk
                     # inside a row chunk, and a reduce adds them.  Not with a folded shortcut gradient (one epilogue).
-                    max_segs = max(len(sg) for sg in per_pixel) if per_pixel is not None else 0
+                    max_segs = max(map(len, per_pixel), default=0)
                     S = 1
                     if (DGRAD_MAX_SEGS > 0 and fold_res is None and nb >= TAP_SPLIT_MIN_BATCH and gst.contiguous
                             and gst.ch_off == 0 and gst.ld == src.c and max_segs > DGRAD_MAX_SEGS):
@@ -1446,8 +1422,7 @@ class TowerPlan:
                     if S > 1:
                         copy = h * w * nb * gst.ld
                         for pin, segs in enumerate(per_pixel):
-                            for si in range(S):
-                                chunk = segs[len(segs) * si // S:len(segs) * (si + 1) // S]
+                            for _, si, chunk in self._partial_copies(segs, S):
                                 tb.add_group(si * copy + gst.pix_off(pin), chunk, nb, subkey=si)
                         pos = len(self.bwd)
                         self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, w_ref, w_ld or cout, 1,
@@ -1461,7 +1436,7 @@ class TowerPlan:
                         self.bwd.append(l2)
                         acc = 1
                         continue
-                    for pin, segs in enumerate(per_pixel or ()):
+                    for pin, segs in enumerate(per_pixel):
                         tb.add_group(gst.pix_off(pin), segs, nb)
                     self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, w_ref, w_ld or cout, 1,
                                     self._ref(gst.buf), gst.ld, None, acc, f"dgrad:{items[0][0].scope}{mtag}",
@@ -1470,7 +1445,7 @@ class TowerPlan:
                     acc = 1
             # ---- filter gradient ----
             if trains:
-                self._wgrad_conv(idx, node, aux, s_st, src, dy, c, h, w)
+                self._wgrad_conv(idx, node, s_st, dy, c)
         elif node.kind == "blockdense":
             src = node.sources[0]
             s_st = self.storage_of(src)
@@ -1487,7 +1462,7 @@ class TowerPlan:
                     self._emit_gemm(self.bwd, tb, width, dy, c, 0, Ref(self.sess.params), cout, 1, self._ref(gst.buf),
                                     gst.ld, None, acc, f"dgrad:{node.branches[0].scope}+", allow_split=False)
             if trains:
-                self._wgrad_blockdense(idx, node, s_st, dy, c, cout)
+                self._wgrad_blockdense(node, s_st, dy, c, cout)
         else:
             b = node.branches[0]
             rowbase = 0
@@ -1502,7 +1477,7 @@ class TowerPlan:
                                     gst.ld, None, acc, f"dgrad:{b.scope}")
                 rowbase += src.npix * src.c
             if trains:
-                self._wgrad_dense(idx, node, aux, dy, c)
+                self._wgrad_dense(node, dy, c)
 
     def _emit_post_bwd(self, node, aux, dz, y_ref, rows, c, dy, want_param):
         has_bn = isinstance(node, G.LinearNode) and node.has_bn
@@ -1609,24 +1584,30 @@ class TowerPlan:
         s_pix = max(1, min(n_pairs, want // s_row))
         return s_pix, s_row
 
-    def _split_ranges(self, s_pix, s_row, n_pairs):
-        """[(pair_lo, pair_hi, r0, r1)] in split order (row range major: the XCD-locality key)."""
-        nb = self.nb
-        rcuts = [min(nb, (nb * s // s_row + 31) // 32 * 32) for s in range(s_row)] + [nb]
-        out = []
-        for sr in range(s_row):
-            for sp in range(s_pix):
-                out.append((n_pairs * sp // s_pix, n_pairs * (sp + 1) // s_pix, rcuts[sr], rcuts[sr + 1]))
-        return out
-
-    def _emit_wgrad(self, tables_by_split_builder, n_groups_blocks, max_segs, slab, w0_offset, n, a_ref, lda, b_ref, ldb,
-                    tag, acc=0, unpack=None):
-        """tables_by_split_builder(S) -> GemmTables whose groups write to c_off = split*slab + local.
+    def _emit_wgrad(self, groups, slab, w0_offset, n, a_ref, lda, b_ref, ldb, tag, acc=0, unpack=None):
+        """Filter-gradient product: groups = [(c_off in the slab, [(a_off, b_off)] pixel pairs, rows, n or 0 = the launch's
+        n)], each the sum over its pixel pairs and the batch rows; split s of the reduction (_wgrad_splits) writes its slab
+        at s * slab.
         unpack (merged levels): dict(buf, entries) -- the product's output is a packed image in buffer `buf`, scattered into
         the gradient slots by block copies after the reduction."""
-        s_pix, s_row = self._wgrad_splits(n_groups_blocks, max_segs)
+        nb = self.nb
+        n_pairs = max(len(prs) for _, prs, _, _ in groups)
+        s_pix, s_row = self._wgrad_splits(sum((rows + GEMM_BM - 1) // GEMM_BM * (((gn or n) + 63) // 64)
+                                              for _, _, rows, gn in groups), n_pairs)
         S = s_pix * s_row
-        tb = tables_by_split_builder((s_pix, s_row))
+        # split = (row range, pixel-pair chunk), row range major (the XCD-locality key); a group with fewer pixel pairs
+        # than the widest one gets proportionally cut chunks
+        rcuts = [min(nb, (nb * s // s_row + 31) // 32 * 32) for s in range(s_row)] + [nb]
+        tb = GemmTables()
+        for sr in range(s_row):
+            r0, r1 = rcuts[sr], rcuts[sr + 1]
+            for sp in range(s_pix):
+                p0, p1 = n_pairs * sp // s_pix, n_pairs * (sp + 1) // s_pix
+                si = sr * s_pix + sp
+                for c_off, prs, rows, gn in groups:
+                    q0, q1 = len(prs) * p0 // n_pairs, len(prs) * p1 // n_pairs
+                    segs = [(a + r0 * lda, b + r0 * ldb, r1 - r0) for a, b in prs[q0:q1]] if r1 > r0 else []
+                    tb.add_group(si * slab + c_off, segs, rows, key=si, n=gn)
         if MERGE_WGRAD:
             if (acc or (unpack and any(e[6] for e in unpack["entries"]))) and self._pending_wgrads:
                 # a second application of shared weights adds to what an earlier pending product writes: keep the order
@@ -1783,156 +1764,75 @@ class TowerPlan:
             self.tables.append(u_t)
             self.bwd.append(Launch("copy_blocks_f32", (base, Ref(u_t), len(unpacks), max(u[2] * u[3] for u in unpacks)),
                                    nbytes=8 * sum(u[2] * u[3] for u in unpacks), tag="level-unpack"))
-    @staticmethod
-    def _split_even(segs, S):
-        """Partition a list into S contiguous chunks (some possibly empty)."""
-        n = len(segs)
-        return [segs[(n * s) // S:(n * (s + 1)) // S] for s in range(S)]
 
-    def _wgrad_level_merged(self, idx, node, lay, s_st, src, dy, c, h, w):
-        """Filter gradient of a merged level: per input offset d ONE product dW_pack[d] = sum_p X[p + d]^T dY[p][:, col0:]
-        with n = C - col0[ring] columns (30 .. 120 for the 30-filter HYPELCNN level instead of 30 per (branch, tap)), written
-        into a dense packed image; hypel_copy_blocks_f32 scatters the [Cin x cout] slices into the HWIO gradient slots."""
+    def _wgrad_conv(self, idx, node, s_st, dy_ref, c):
+        """Filter gradient of a convolution: per tap ONE product dW[tap] = sum_p X[p + (dy, dx)]^T dY[p][:, col:col + n] over
+        the output pixels p whose input pixel is real.  A merged level: per input offset d, n = C - col0[ring] columns (30 ..
+        120 for the 30-filter HYPELCNN level instead of 30 per (branch, tap)) into a dense packed image, whose [Cin x cout]
+        slices hypel_copy_blocks_f32 scatters into the HWIO gradient slots."""
         nb = self.nb
-        C, cin, co = lay["C"], lay["cin"], lay["co"]
-        group_list = []  # (offset of the block in the dense image, [(a_off, b_off)] pixel pairs, columns)
-        for d, (ofy, ofx, r) in enumerate(lay["offs"]):
-            col0 = lay["col0"][r]
-            pairs = [(s_st.pix_off((oy + ofy) * w + ox + ofx), (oy * w + ox) * nb * c + col0)
-                     for oy in range(h) for ox in range(w) if 0 <= oy + ofy < h and 0 <= ox + ofx < w]
-            group_list.append((lay["dense_off"][d], pairs, C - col0))
-        slab = lay["dense_size"]
-        blocks = sum(((cin + GEMM_BM - 1) // GEMM_BM) * ((n_d + 63) // 64) for _, _, n_d in group_list)
-        max_segs = max(len(prs) for _, prs, _ in group_list)
+        src = node.sources[0]
+        h, w = src.hw
 
-        def build(S, group_list=group_list, slab=slab, rows=cin, lda=s_st.ld, ldb=c, npairs=max_segs):
-            tb = GemmTables()
-            for si, (p0, p1, r0, r1) in enumerate(self._split_ranges(S[0], S[1], npairs)):
-                for (loc, pairs, n_d) in group_list:
-                    q0, q1 = len(pairs) * p0 // npairs, len(pairs) * p1 // npairs
-                    segs = [(a + r0 * lda, b_ + r0 * ldb, r1 - r0) for (a, b_) in pairs[q0:q1]] if r1 > r0 else []
-                    tb.add_group(si * slab + loc, segs, rows, key=si, n=n_d)
-            return tb
+        def pairs(dy, dx, col):
+            return [(s_st.pix_off((oy + dy) * w + ox + dx), (oy * w + ox) * nb * c + col)
+                    for oy in range(h) for ox in range(w) if 0 <= oy + dy < h and 0 <= ox + dx < w]
 
-        ents = []
-        for bi, b in enumerate(node.branches):
-            acc = self._param_acc(b.w)
-            pb = (b.k - 1) // 2
-            for i in range(b.k):
-                for j in range(b.k):
-                    d = lay["index"][(i - pb, j - pb)]
-                    r = lay["offs"][d][2]
-                    n_d = C - lay["col0"][r]
-                    dst = b.w.offset + (i * b.k + j) * cin * co
-                    ents.append((lay["dense_off"][d] + (bi - lay["first"][r]) * co, dst, cin, co, n_d, co, acc))
-        self._emit_wgrad(build, blocks, max_segs, slab, 0, C, self._ref(s_st.buf), s_st.ld, dy, c,
-                         f"wgrad:{node.branches[0].scope}/merged", acc=0,
-                         unpack=dict(buf=f"dwpack:{idx}", entries=ents))
-
-    def _wgrad_conv(self, idx, node, aux, s_st, src, dy, c, h, w):
-        nb = self.nb
         lay = self._level_pass(idx, node, "wgrad")
         # (every offset of the largest kernel must meet at least one pixel pair, or its block of the packed image would
         # never be written: (k - 1) / 2 <= min(h, w) - 1)
         if lay is not None and max(b.k for b in node.branches) <= 2 * min(h, w) - 1:
-            self._wgrad_level_merged(idx, node, lay, s_st, src, dy, c, h, w)
+            taps = self._taps(self._columns(node), src.c, lay)
+            ents = []
+            for b, col in self._columns(node):
+                acc = self._param_acc(b.w)
+                for dy, dx, w_, _, _ in self._taps([(b, col)], src.c):
+                    d = lay["index"][(dy, dx)]
+                    _, _, _, col0, n_d = taps[d]
+                    ents.append((lay["dense_off"][d] + col - col0, w_, src.c, b.cout, n_d, b.cout, acc))
+            self._emit_wgrad([(lay["dense_off"][d], pairs(dy, dx, col), src.c, n_d) for d, (dy, dx, _, col, n_d) in enumerate(taps)],
+                             lay["dense_size"], 0, lay["C"], self._ref(s_st.buf), s_st.ld, dy_ref, c,
+                             f"wgrad:{node.branches[0].scope}/merged", unpack=dict(buf=f"dwpack:{idx}", entries=ents))
             return
-        choff = 0
-        w_base = aux["w0"].offset
         by_cout = {}
-        for b in node.branches:
-            by_cout.setdefault(b.cout, []).append((b, choff))
-            choff += b.cout
+        for b, col in self._columns(node):
+            by_cout.setdefault(b.cout, []).append((b, col))
         for cout, items in by_cout.items():
             # the slab of one launch = the contiguous weights of its branches
             lo = min(b.w.offset for b, _ in items)
-            hi = max(b.w.offset + b.w.size for b, _ in items)
-            slab = hi - lo
+            slab = max(b.w.offset + b.w.size for b, _ in items) - lo
             if slab != sum(b.w.size for b, _ in items):
                 # the reduce overwrites the whole slab: sibling branches of another width in between would be clobbered
                 raise RuntimeError(f"filter-gradient slab of {items[0][0].scope}: branches with {cout} filters are not "
                                    f"contiguous in the parameter buffer")
-            group_list = []  # (local c_off, [(a_off, b_off)] pixel pairs)
-            for b, off in items:
-                pb = (b.k - 1) // 2
-                for i in range(b.k):
-                    for j in range(b.k):
-                        pairs = []
-                        for oy in range(h):
-                            iy = oy + i - pb
-                            if iy < 0 or iy >= h:
-                                continue
-                            for ox in range(w):
-                                ix = ox + j - pb
-                                if ix < 0 or ix >= w:
-                                    continue
-                                pairs.append((s_st.pix_off(iy * w + ix), (oy * w + ox) * nb * c + off))
-                        group_list.append((b.w.offset - lo + (i * b.k + j) * src.c * cout, pairs))
-            blocks = len(group_list) * ((src.c + GEMM_BM - 1) // GEMM_BM) * ((cout + 63) // 64)
-            max_segs = max(len(s) for _, s in group_list)
-
-            def build(S, group_list=group_list, slab=slab, rows=src.c, lda=s_st.ld, ldb=c, npairs=max_segs):
-                tb = GemmTables()
-                for si, (p0, p1, r0, r1) in enumerate(self._split_ranges(S[0], S[1], npairs)):
-                    for (loc, pairs) in group_list:
-                        # a tap with fewer valid pixel pairs than the widest one gets proportionally cut chunks
-                        q0, q1 = len(pairs) * p0 // npairs, len(pairs) * p1 // npairs
-                        segs = [(a + r0 * lda, b_ + r0 * ldb, r1 - r0) for (a, b_) in pairs[q0:q1]] if r1 > r0 else []
-                        tb.add_group(si * slab + loc, segs, rows, key=si)
-                return tb
-
             acc = max(self._param_acc(b.w) for b, _ in items)
-            self._emit_wgrad(build, blocks, max_segs, slab, lo, cout, self._ref(s_st.buf), s_st.ld, dy, c,
-                             f"wgrad:{items[0][0].scope}", acc=acc)
+            self._emit_wgrad([(w_ - lo, pairs(dy, dx, col), src.c, 0) for dy, dx, w_, col, _ in self._taps(items, src.c)],
+                             slab, lo, cout, self._ref(s_st.buf), s_st.ld, dy_ref, c, f"wgrad:{items[0][0].scope}", acc=acc)
 
-    def _wgrad_dense(self, idx, node, aux, dy, c):
-        nb = self.nb
+    def _wgrad_dense(self, node, dy, c):
+        """One product per source; a group per source pixel: its block of weight rows, one pixel pair."""
         b = node.branches[0]
         rowbase = 0
         for src in node.sources:
             s_st = self.storage_of(src)
-            slab = src.npix * src.c * c
-            lo = b.w.offset + rowbase * c
-            group_list = [(p * src.c * c, [(s_st.pix_off(p), 0)]) for p in range(src.npix)]
-            blocks = len(group_list) * ((src.c + GEMM_BM - 1) // GEMM_BM) * ((c + 63) // 64)
-            max_segs = 1
-
-            def build(S, group_list=group_list, slab=slab, rows=src.c, lda=s_st.ld, ldb=c):
-                tb = GemmTables()
-                for si, (p0, p1, r0, r1) in enumerate(self._split_ranges(1, S[0] * S[1], 1)):
-                    for (loc, pairs) in group_list:
-                        segs = [(a + r0 * lda, b_ + r0 * ldb, r1 - r0) for (a, b_) in pairs] if r1 > r0 else []
-                        tb.add_group(si * slab + loc, segs, rows, key=si)
-                return tb
-
             acc = self._param_acc(b.w) if rowbase == 0 else (1 if b.w.name + f"#{rowbase}" in self.param_written else 0)
             self.param_written.add(b.w.name + f"#{rowbase}")
-            self._emit_wgrad(build, blocks, max_segs, slab, lo, c, self._ref(s_st.buf), s_st.ld, dy, c,
+            self._emit_wgrad([(p * src.c * c, [(s_st.pix_off(p), 0)], src.c, 0) for p in range(src.npix)],
+                             src.npix * src.c * c, b.w.offset + rowbase * c, c, self._ref(s_st.buf), s_st.ld, dy, c,
                              f"wgrad:{b.scope}", acc=acc)
             rowbase += src.npix * src.c
 
-    def _wgrad_blockdense(self, idx, node, s_st, dy, c, cout):
+    def _wgrad_blockdense(self, node, s_st, dy, c, cout):
         """dW_p = X[:, slice_p]^T dY[:, p*cout:(p+1)*cout] for every slice p in one launch (the weights of a merged
         layer are contiguous: one slab per batch-row split, one reduction)."""
         ws = [b.w for b in node.branches]
         lo = ws[0].offset
-        slab = sum(w.size for w in ws)
-        group_list = [(w.offset - lo, off, pi * cout, width) for pi, (w, (off, width)) in
-                      enumerate(zip(ws, node.in_slices))]
-        blocks = sum((width + GEMM_BM - 1) // GEMM_BM for _, _, _, width in group_list) * ((cout + 63) // 64)
-
-        def build(S, lda=s_st.ld, ldb=c, base=s_st.pix_off(0)):
-            tb = GemmTables()
-            for si, (p0, p1, r0, r1) in enumerate(self._split_ranges(1, S[0] * S[1], 1)):
-                for (loc, a_off, b_off, width) in group_list:
-                    segs = [(base + a_off + r0 * lda, b_off + r0 * ldb, r1 - r0)] if r1 > r0 else []
-                    tb.add_group(si * slab + loc, segs, width, key=si)
-            return tb
-
         acc = self._param_acc(ws[0])
         for w in ws[1:]:
             self.param_written.add(w.name)
-        self._emit_wgrad(build, blocks, 1, slab, lo, cout, self._ref(s_st.buf), s_st.ld, dy, c,
+        self._emit_wgrad([(w.offset - lo, [(s_st.pix_off(0) + off, pi * cout)], width, 0)
+                          for pi, (w, (off, width)) in enumerate(zip(ws, node.in_slices))],
+                         sum(w.size for w in ws), lo, cout, self._ref(s_st.buf), s_st.ld, dy, c,
                          f"wgrad:{node.branches[0].scope}+", acc=acc)
 
     def _bwd_post(self, idx, node):

@@ -287,6 +287,26 @@ def test_merged_levels_match_oracle(monkeypatch, passes, patch, fc):
     U.compare_step(built, ct, params, x, onehot, masks, "HYPELCNNModel", 4, alg, tol_logit=2e-5, tol_grad=2e-4)
 
 
+def test_merged_forward_with_split_forced_off_uses_fp32_chunking(monkeypatch):
+    """A merged level forward is cut for the kernel family that actually runs: with the split-operand kernels forced off by
+    HYPEL_SPLIT_OVERRIDE for a level they would take (24 filters per branch), its tiles hold at most MAX_TAPS_PER_TILE taps
+    and the reduction is cut into channel parts, as on the fp32 kernels; the step still equals the oracle."""
+    from hypelcnn_amd import plan
+    from hypelcnn_amd.backend import GROUP_DTYPE
+    tag = "fwd:connector_0_conv1x1/merged"
+    monkeypatch.setattr(plan, "TAP_SPLIT_MIN_BATCH", 1)
+    monkeypatch.setattr(plan, "MAX_TAPS_PER_TILE", 5)
+    monkeypatch.setattr(plan, "L2_CHUNK_BYTES", 4096)
+    monkeypatch.setattr(plan, "SPLIT_OVERRIDE", {tag: 0})
+    alg = dict(ALG_H, filter_count=192)
+    built, sess, params, x, onehot, masks = _case("HYPELCNNModel", 7, 9, 4, alg, 5, 47)
+    ct = U.run_train_step(built, x, onehot, masks)
+    (l,) = [l for l in ct.plan.fwd if l.tag == tag]
+    groups = l.args[9].t.numpy()[l.args[9].off:].view(GROUP_DTYPE)
+    assert not l.args[14] & 0x8000 and l.kparts > 1 and groups["seg_count"].max() <= 5
+    U.compare_step(built, ct, params, x, onehot, masks, "HYPELCNNModel", 4, alg, tol_logit=2e-5, tol_grad=2e-4)
+
+
 
 
 @pytest.mark.parametrize("frac_min", [0.25, 0.75])
