@@ -41,6 +41,8 @@ TILE_DTYPE = np.dtype([("group", "<i4"), ("m0", "<i4"), ("rows", "<i4"), ("seg_b
                        ("k0", "<i4"), ("c_off", "<i8"), ("a_off0", "<i8"), ("b_off0", "<i8"),
                        ("flags", "<i4"), ("n", "<i4")])
 TILE_PLAIN = 1  # include/hypel.h HYPEL_TILE_PLAIN: K-slice partial (no bias / accumulate / shortcut gather)
+# include/hypel.h HYPEL_DTYPE_*: output dtypes of hypel_denorm_scatter
+OUT_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2, np.dtype(np.uint8): 3}
 COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
                              ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 
@@ -117,6 +119,7 @@ SIGNATURES = {
     "augment_patches_f32": [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "gather_pairs_f32": [_P, _P, _P, _I64, _I32, _P, _P, _P, _F, _P, _P],
     "argmax_scatter": [_P, _I64, _I64, _I32, _P, _P, _I64],
+    "denorm_scatter": [_P, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _I64],
     "lrn_fwd": [_P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64],
     "lrn_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64, _I32],
     "gan_generator_fwd": [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64],

@@ -7,6 +7,8 @@
 //                        output) + left/right and up/down flips + per-channel spectral shift, one pass
 //   * argmax_scatter   : perform_prediction (common_nn_ops.py:313-327): argmax of the logits written straight
 //                        into the uint8 label raster at the target's (x, y)
+//   * denorm_scatter   : the GAN scene conversion's ((g * casi_max) + casi_min).astype(dtype)
+//                        (gan/gan_infer_image_for_shadow.py:84-85), per pixel row, into the output raster
 // All three are pure HBM streaming: one read and one write of every patch element, channel-contiguous so that
 // consecutive lanes touch consecutive addresses (C >= 49 floats per pixel in every configuration).
 #include "common.h"
@@ -144,6 +146,93 @@ __global__ void gather_pairs_kernel(const float* __restrict__ normal, const floa
     }
 }
 
+// NumPy's float32 -> integer cast as compiled for x86-64: cvttss2si to int32 (truncation toward zero; NaN, +-inf and
+// values outside [-2^31, 2^31) give INT_MIN), then the low bits.  The generator ends in tanh, so values below casi_min
+// (negative before the offset) do occur and wrap exactly like this.
+__device__ __forceinline__ int32_t hypel_cvtt_i32(float v) {
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : INT32_MIN;
+}
+
+template <typename T>
+__device__ __forceinline__ T hypel_cast_out(float v) {
+    return (T)hypel_cvtt_i32(v);
+}
+template <>
+__device__ __forceinline__ float hypel_cast_out<float>(float v) {
+    return v;
+}
+
+// float32 multiply, then float32 add, each rounded (NumPy evaluates the two operators separately): no fma
+__device__ __forceinline__ float hypel_denorm(float x, float s, float o) {
+#pragma clang fp contract(off)
+    const float m = x * s;
+    return m + o;
+}
+
+template <typename T>
+struct Vec4Of;
+template <>
+struct Vec4Of<float> { using type = float4; };
+template <>
+struct Vec4Of<uint16_t> { using type = ushort4; };
+template <>
+struct Vec4Of<int16_t> { using type = short4; };
+template <>
+struct Vec4Of<uint8_t> { using type = uchar4; };
+
+// VEC: rows of src and out start 4-element aligned (ld_src, ld_out multiples of 4, aligned bases).  One lane converts
+// four neighbouring bands with one 16-byte load and one 4-element store; the bands % 4 remainder of a row goes through
+// the scalar path of the row's last lane.  Without VEC one lane converts one element.
+template <typename T, bool VEC>
+__global__ void denorm_scatter_kernel(const float* __restrict__ src, int64_t ld_src, const int64_t* __restrict__ rows,
+                                      int64_t n, int bands, const float* __restrict__ scale,
+                                      const float* __restrict__ offset, T* __restrict__ out, int64_t ld_out) {
+    const int per_row = VEC ? (bands + 3) >> 2 : bands;
+    const int64_t total = n * per_row;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; item < total; item += stride) {
+        const int64_t i = item / per_row;
+        const int j = (int)(item - i * per_row);
+        const float* s = src + i * ld_src;
+        T* o = out + (rows ? rows[i] : i) * ld_out;
+        if (VEC) {
+            const int b0 = j << 2;
+            if (b0 + 4 <= bands) {
+                const float4 x = *reinterpret_cast<const float4*>(s + b0);
+                const float4 sc = *reinterpret_cast<const float4*>(scale + b0);
+                const float4 of = *reinterpret_cast<const float4*>(offset + b0);
+                typename Vec4Of<T>::type r;
+                r.x = hypel_cast_out<T>(hypel_denorm(x.x, sc.x, of.x));
+                r.y = hypel_cast_out<T>(hypel_denorm(x.y, sc.y, of.y));
+                r.z = hypel_cast_out<T>(hypel_denorm(x.z, sc.z, of.z));
+                r.w = hypel_cast_out<T>(hypel_denorm(x.w, sc.w, of.w));
+                *reinterpret_cast<typename Vec4Of<T>::type*>(o + b0) = r;
+            } else {
+                for (int b = b0; b < bands; ++b) o[b] = hypel_cast_out<T>(hypel_denorm(s[b], scale[b], offset[b]));
+            }
+        } else {
+            o[j] = hypel_cast_out<T>(hypel_denorm(s[j], scale[j], offset[j]));
+        }
+    }
+}
+
+template <typename T>
+int launch_denorm_scatter(const float* src, int64_t ld_src, const int64_t* rows, int64_t n, int bands,
+                          const float* scale, const float* offset, void* out, int64_t ld_out, hipStream_t st) {
+    T* o = static_cast<T*>(out);
+    const bool vec = ld_src % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)scale & 15) == 0 &&
+                     ((uintptr_t)offset & 15) == 0 && ((uintptr_t)o % (4 * sizeof(T))) == 0;
+    const int64_t work = n * (vec ? (bands + 3) / 4 : bands);
+    const dim3 grid(hypel_grid_1d(work, 256, 256 * 64)), block(256);
+    if (vec)
+        hipLaunchKernelGGL((denorm_scatter_kernel<T, true>), grid, block, 0, st, src, ld_src, rows, n, bands, scale,
+                           offset, o, ld_out);
+    else
+        hipLaunchKernelGGL((denorm_scatter_kernel<T, false>), grid, block, 0, st, src, ld_src, rows, n, bands, scale,
+                           offset, o, ld_out);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int hypel_gather_pairs_f32(const float* normal, const float* shadow, const int64_t* idx, int64_t n, int32_t bands,
@@ -204,5 +293,21 @@ extern "C" int hypel_argmax_scatter(const float* logits, int64_t ld, int64_t n, 
     hipLaunchKernelGGL(argmax_scatter_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, ST, logits, ld, n, c,
                        points, raster, raster_w);
     HYPEL_CHECK_LAUNCH("hypel_argmax_scatter");
+    return 0;
+}
+
+extern "C" int hypel_denorm_scatter(const float* src, int64_t ld_src, const int64_t* rows, int64_t n, int32_t bands,
+                                    const float* scale, const float* offset, int32_t out_dtype, void* out,
+                                    int64_t ld_out, hypel_stream_t stream) {
+    HYPEL_REQUIRE(src && scale && offset && out && n > 0 && bands > 0 && ld_src >= bands && ld_out >= bands,
+                  "hypel_denorm_scatter");
+    switch (out_dtype) {
+        case HYPEL_DTYPE_F32: launch_denorm_scatter<float>(src, ld_src, rows, n, bands, scale, offset, out, ld_out, ST); break;
+        case HYPEL_DTYPE_U16: launch_denorm_scatter<uint16_t>(src, ld_src, rows, n, bands, scale, offset, out, ld_out, ST); break;
+        case HYPEL_DTYPE_I16: launch_denorm_scatter<int16_t>(src, ld_src, rows, n, bands, scale, offset, out, ld_out, ST); break;
+        case HYPEL_DTYPE_U8: launch_denorm_scatter<uint8_t>(src, ld_src, rows, n, bands, scale, offset, out, ld_out, ST); break;
+        default: hypel_set_error("hypel_denorm_scatter: unsupported out_dtype %d", (int)out_dtype); return -1;
+    }
+    HYPEL_CHECK_LAUNCH("hypel_denorm_scatter");
     return 0;
 }

@@ -203,12 +203,16 @@ def run_session(params, base_log_path, backend=None):
     return [div_upper, div_mean]
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     for add in (add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, add_parse_cmds_for_trainers,
                 add_parse_cmds_for_json_loader, add_parse_cmds_for_app, add_parse_cmds_for_opt):
         add(parser)
-    flags, _ = parser.parse_known_args(argv)
+    return parser
+
+
+def main(argv=None):
+    flags, _ = build_parser().parse_known_args(argv)
     params = dict(vars(flags))
     if flags.flag_config_file:
         params.update(json.load(open(flags.flag_config_file, "r")))

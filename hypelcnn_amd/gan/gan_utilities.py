@@ -61,6 +61,16 @@ class GeneratorAugmenter:
         return conv
 
 
+def load_gan_variables(path):
+    """A GAN checkpoint as {TF variable name: array}: a TensorFlow bundle prefix (e.g. the published
+    shadow_gen_model/cycle_gan/model.ckpt-5000) or the .npz save_gan_checkpoint writes (with or without the suffix)."""
+    from hypelcnn_amd.common import tf_checkpoint
+    if not path.endswith(".npz") and tf_checkpoint.is_checkpoint(path):
+        return tf_checkpoint.read_checkpoint(path)
+    with numpy.load(path if path.endswith(".npz") else path + ".npz") as z:
+        return {k.replace("|", "/"): z[k] for k in z.files}
+
+
 def create_gan_struct(gan_inference_wrapper, model_base_dir, ckpt_relative_path, bands=None, backend=None):
     """Lazily built generator augmenters; `shadow_op_initializer` loads an .npz checkpoint keyed by TF names."""
     holders = {}
@@ -74,13 +84,7 @@ def create_gan_struct(gan_inference_wrapper, model_base_dir, ckpt_relative_path,
     def _initializer(restorer, session):
         if state["backend"] is None and session is not None:
             state["backend"] = session.backend  # the augmenter runs on the classifier session's device
-        path = model_base_dir + ckpt_relative_path
-        from hypelcnn_amd.common import tf_checkpoint
-        if not path.endswith(".npz") and tf_checkpoint.is_checkpoint(path):  # a TensorFlow bundle, e.g. the published
-            variables = tf_checkpoint.read_checkpoint(path)                  # shadow_gen_model/cycle_gan/model.ckpt-5000
-        else:
-            with numpy.load(path if path.endswith(".npz") else path + ".npz") as z:
-                variables = {k.replace("|", "/"): z[k] for k in z.files}
+        variables = load_gan_variables(model_base_dir + ckpt_relative_path)
         for flag in (True, False):
             _get(flag).load(variables)
 

@@ -5,11 +5,11 @@ from hypelcnn_amd.gan.gan_sampling_methods import DummySampler, NeighborhoodBase
     TargetBasedSampler
 from hypelcnn_amd.gan.shadow_data_models import shadowdata_discriminator_model, \
     shadowdata_feature_discriminator_model, shadowdata_generator_model
-from hypelcnn_amd.gan.wrappers.cut_wrapper import CUTWrapper
+from hypelcnn_amd.gan.wrappers.cut_wrapper import CUTInferenceWrapper, CUTWrapper
 from hypelcnn_amd.gan.wrappers.cycle_gan_wrapper import CycleGANInferenceWrapper, CycleGANWrapper
-from hypelcnn_amd.gan.wrappers.dcl_cycle_gan_wrapper import DCLCycleGANWrapper
-from hypelcnn_amd.gan.wrappers.dcl_gan_wrapper import DCLGANWrapper
-from hypelcnn_amd.gan.wrappers.gan_wrapper import GANWrapper
+from hypelcnn_amd.gan.wrappers.dcl_cycle_gan_wrapper import DCLCycleGANInferenceWrapper, DCLCycleGANWrapper
+from hypelcnn_amd.gan.wrappers.dcl_gan_wrapper import DCLGANInferenceWrapper, DCLGANWrapper
+from hypelcnn_amd.gan.wrappers.gan_wrapper import GANInferenceWrapper, GANWrapper
 
 
 def get_sampling_map():
@@ -20,8 +20,13 @@ def get_sampling_map():
 
 def get_infer_wrapper_dict():
     generator_fn = partial(shadowdata_generator_model, create_only_encoder=False, is_training=False)
-    cyc = CycleGANInferenceWrapper(shadow_generator_fn=generator_fn)
-    return {"cycle_gan": cyc, "dcl_gan": cyc, "dcl_cycle_gan": cyc}
+    return {"cycle_gan": CycleGANInferenceWrapper(shadow_generator_fn=generator_fn),
+            "gan_x2y": GANInferenceWrapper(fetch_shadows=False, shadow_generator_fn=generator_fn),
+            "gan_y2x": GANInferenceWrapper(fetch_shadows=True, shadow_generator_fn=generator_fn),
+            "cut_x2y": CUTInferenceWrapper(fetch_shadows=False, shadow_generator_fn=generator_fn),
+            "cut_y2x": CUTInferenceWrapper(fetch_shadows=True, shadow_generator_fn=generator_fn),
+            "dcl_gan": DCLGANInferenceWrapper(shadow_generator_fn=generator_fn),
+            "dcl_cycle_gan": DCLCycleGANInferenceWrapper(shadow_generator_fn=generator_fn)}
 
 
 def get_wrapper_dict(flags):

@@ -4,6 +4,7 @@ import collections
 
 from hypelcnn_amd import graph as G
 from hypelcnn_amd.gan.wrappers import gan_common as C
+from hypelcnn_amd.gan.wrappers.gan_wrapper import GANInferenceWrapper
 from hypelcnn_amd.gan.wrappers.wrapper import Wrapper
 
 CUTTrainSteps = collections.namedtuple("CUTTrainSteps", ("generator_train_steps", "discriminator_train_steps",
@@ -98,3 +99,7 @@ class CUTWrapper(Wrapper):
 
     def get_train_hooks_fn(self):
         return lambda train_ops: [train_ops.run_step]
+
+
+class CUTInferenceWrapper(GANInferenceWrapper):
+    """reference :668-670: the CUT generator lives in Model/Generator like the GAN's."""

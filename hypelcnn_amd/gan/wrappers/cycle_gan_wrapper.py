@@ -9,6 +9,19 @@ model_forward_generator_name = "ModelX2Y"
 model_backward_generator_name = "ModelY2X"
 
 
+def create_base_validation_hook(data_set, loader, log_dir, neighborhood, shadow_map, shadow_ratio,
+                                validation_iteration_count, validation_sample_count, model_forward, model_backward,
+                                x_input_tensor, y_input_tensor, ctx):
+    """reference :22-45: X2Y scored on lit samples ("shadowed"), Y2X on shadowed samples with the inverse ratio."""
+    common = dict(iteration_freq=validation_iteration_count, sample_count=validation_sample_count, log_dir=log_dir,
+                  loader=loader, data_set=data_set, neighborhood=neighborhood, shadow_map=shadow_map, ctx=ctx)
+    shadowed = C.ValidationHook(shadow_ratio=shadow_ratio, input_tensor=x_input_tensor, infer_model=model_forward,
+                                fetch_shadows=False, name_suffix="shadowed", **common)
+    de_shadowed = C.ValidationHook(shadow_ratio=1. / shadow_ratio, input_tensor=y_input_tensor,
+                                   infer_model=model_backward, fetch_shadows=True, name_suffix="deshadowed", **common)
+    return C.PeerValidationHook(shadowed, de_shadowed)
+
+
 class CycleGANWrapper(Wrapper):
     def __init__(self, cycle_consistency_loss_weight, identity_loss_weight, use_identity_loss, generator_fn,
                  discriminator_fn):
@@ -91,3 +104,15 @@ class CycleGANInferenceWrapper(InferenceWrapper):
         prefixes = (f"{C.model_base_name}/{model_forward_generator_name}",
                     f"{C.model_base_name}/{model_backward_generator_name}")
         return lambda names: [n for n in names if n.startswith(prefixes)]
+
+    def create_inference_hook(self, data_set, loader, log_dir, neighborhood, shadow_map, shadow_ratio,
+                              validation_iteration_count, validation_sample_count, backend=None):
+        """One tower holding both generators (the reference builds both into one graph); restore into `hook.ctx`."""
+        tower, x, y = C.new_gan_tower(data_set.get_casi_band_count())
+        ctx = C.GanContext(tower, backend)
+        hook = create_base_validation_hook(data_set, loader, log_dir, neighborhood, shadow_map, shadow_ratio,
+                                           validation_iteration_count, validation_sample_count,
+                                           self.construct_inference_graph(x, True, False),
+                                           self.construct_inference_graph(y, False, False), x, y, ctx)
+        hook.ctx = ctx
+        return hook

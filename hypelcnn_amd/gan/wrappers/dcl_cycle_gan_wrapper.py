@@ -5,6 +5,7 @@ import collections
 
 from hypelcnn_amd import graph as G
 from hypelcnn_amd.gan.wrappers import gan_common as C
+from hypelcnn_amd.gan.wrappers.cycle_gan_wrapper import CycleGANInferenceWrapper
 from hypelcnn_amd.gan.wrappers.dcl_gan_wrapper import DCLGANWrapper, dcl_gan_model
 
 DCLCycleGANModel = collections.namedtuple("DCLCycleGANModel", ("model_x2y", "model_y2x", "reconstructed_x",
@@ -27,3 +28,7 @@ class DCLCycleGANWrapper(DCLGANWrapper):
             with G.variable_scope("ModelX2Y"), G.variable_scope("Generator"):
                 rec_y = self._generator_fn(m.model_y2x.generated_data, create_only_encoder=False)
         return DCLCycleGANModel(m.model_x2y, m.model_y2x, rec_x, rec_y)
+
+
+class DCLCycleGANInferenceWrapper(CycleGANInferenceWrapper):
+    """reference :209-211"""

@@ -6,6 +6,7 @@ import collections
 from hypelcnn_amd import graph as G
 from hypelcnn_amd.gan.wrappers import gan_common as C
 from hypelcnn_amd.gan.wrappers.cut_wrapper import cut_model, cut_phases, cut_train_ops
+from hypelcnn_amd.gan.wrappers.cycle_gan_wrapper import CycleGANInferenceWrapper
 from hypelcnn_amd.gan.wrappers.wrapper import Wrapper
 
 DCLGANModel = collections.namedtuple("DCLGANModel", ("model_x2y", "model_y2x"))
@@ -48,3 +49,7 @@ class DCLGANWrapper(Wrapper):
 
     def get_train_hooks_fn(self):
         return lambda train_ops: [train_ops.run_step]
+
+
+class DCLGANInferenceWrapper(CycleGANInferenceWrapper):
+    """reference :322-324: generators in Model/ModelX2Y and Model/ModelY2X, as CycleGAN's."""

@@ -1,6 +1,10 @@
 """Shared GAN machinery (reference gan/wrappers/gan_common.py): scope names, the tfgan-style model records,
-the LR schedule, the tensor pool, and the phase executor that replaces tfgan's RunTrainOpsHook sequence."""
+the LR schedule, the tensor pool, the phase executor that replaces tfgan's RunTrainOpsHook sequence, and the
+band-ratio validation hooks that score a generator (reference :47-219, 315-330, 362-382, 417-429)."""
 import collections
+import json
+import os
+from json import JSONDecodeError
 
 import numpy
 import torch
@@ -200,3 +204,199 @@ def ls_terms_generator(d_gen):
 
 def ls_terms_discriminator(d_real, d_gen):
     return [G.LossTerm("mean_sq", d_real, target=1.0, weight=0.5), G.LossTerm("mean_sq", d_gen, target=0.0, weight=0.5)]
+
+
+# ----------------------------------------------------------------------------- checkpoint scoring (reference :47-219)
+def restore_generators(ctx, restorer, variables):
+    """create_generator_restorer().restore(sess, path): the checkpoint variables the wrapper's restorer selects, into
+    the session of `ctx` (names the inference tower does not hold are skipped, as the reference's Saver only lists
+    the graph's own variables)."""
+    sess = ctx.session()
+    for name in restorer(list(variables)):
+        if name in sess.store.vars:
+            sess.set_variable(name, variables[name])
+    return sess
+
+
+class BestRatioHolder:
+    """The `max_size` best (lowest) divergences with their iterations, ascending; a new point goes in front of equal
+    ones."""
+
+    def __init__(self, max_size):
+        self.data_holder = []
+        self.max_size = max_size
+
+    def add_point(self, iteration, diver_val):
+        iteration = int(iteration)
+        diver_val = float(diver_val)
+        insert_idx = sum(1 for _, curr_diver in self.data_holder if diver_val > curr_diver)
+        self.data_holder.insert(insert_idx, (iteration, diver_val))
+        if len(self.data_holder) > self.max_size:
+            self.data_holder.pop()
+
+    def get_best_diver(self):
+        return self.data_holder[0][1] if self.data_holder else None
+
+    def get_point_with_itr(self, iteration):
+        for curr_iter, curr_diver in self.data_holder:
+            if curr_iter == iteration:
+                return curr_iter, curr_diver
+        return None, None
+
+    def load(self, file_address):
+        try:
+            with open(file_address, "rb") as read_file:
+                self.data_holder = json.load(read_file)
+            print(f"Best ratio file {file_address} is loaded.", self.data_holder)
+        except IOError:
+            print(f"File {file_address} file not found. No best ratio is loaded.")
+        except JSONDecodeError:
+            print(f"File {file_address} file can not be decoded. No best ratio is loaded.")
+
+    def save(self, file_address):
+        with open(file_address, "w") as write_file:
+            write_file.write(json.dumps(self.data_holder))
+
+    @staticmethod
+    def create_common_iterations(ratio_holder_1, ratio_holder_2):
+        result = BestRatioHolder(ratio_holder_1.max_size)
+        for curr_iter, _ in ratio_holder_1.data_holder:
+            found_itr, found_kl = ratio_holder_2.get_point_with_itr(curr_iter)
+            if found_itr is not None:
+                result.add_point(found_itr, found_kl)
+        return result
+
+    def __str__(self):
+        return str(self.data_holder)
+
+
+class BaseValidationHook:
+    def __init__(self, iteration_freq, log_dir, shadow_ratio):
+        self._iteration_frequency = iteration_freq
+        self._shadow_ratio = shadow_ratio
+        self._log_dir = log_dir
+        self.best_mean_div_holder = BestRatioHolder(10)
+        self.best_upper_div_holder = BestRatioHolder(10)
+        self.validation_itr_mark = False
+
+    def after_create_session(self, session=None, coord=None):
+        pass
+
+    def _is_validation_itr(self, current_iteration):
+        if self._iteration_frequency != 0:
+            return current_iteration % self._iteration_frequency == 1 and current_iteration != 1
+        return True
+
+    def get_best_mean_div(self):
+        return self.best_mean_div_holder.get_best_diver()
+
+    def get_best_upper_div(self):
+        return self.best_upper_div_holder.get_best_diver()
+
+
+class PeerValidationHook:
+    """The shadowed and de-shadowed hooks of a two-generator GAN, run together; prints the iterations both rank."""
+
+    def __init__(self, *validation_base_hooks):
+        self._validation_base_hooks = validation_base_hooks
+
+    def after_create_session(self, session=None, coord=None):
+        for hook in self._validation_base_hooks:
+            hook.after_create_session(session, coord)
+
+    def after_run(self, current_iteration=0):
+        ratio_holder_list = []
+        for hook in self._validation_base_hooks:
+            hook.after_run(current_iteration)
+            ratio_holder_list.append(hook.best_mean_div_holder)
+        if self._validation_base_hooks[0].validation_itr_mark:
+            print("Best common options:",
+                  BestRatioHolder.create_common_iterations(ratio_holder_list[0], ratio_holder_list[1]))
+
+    def get_best_mean_div(self):
+        return [h.get_best_mean_div() for h in self._validation_base_hooks if h.get_best_mean_div() is not None]
+
+    def get_best_upper_div(self):
+        return [h.get_best_upper_div() for h in self._validation_base_hooks if h.get_best_upper_div() is not None]
+
+    def last_divergences(self):
+        return [d for h in self._validation_base_hooks for d in h.last_divergences()]
+
+
+class ValidationHook(BaseValidationHook):
+    """Runs the generator `infer_model` (a symbol of the tower of `ctx`, fed through the placeholder `input_tensor`) on
+    `sample_count` fixed pixels of one side of the shadow map and tracks create_stats' divergences.  The band-ratio
+    plot of the reference is not drawn; best_ratio_<suffix>.json and a line of log_dir/summaries.jsonl record the
+    result."""
+
+    def __init__(self, iteration_freq, sample_count, log_dir, loader, data_set, neighborhood, shadow_map, shadow_ratio,
+                 input_tensor, infer_model, name_suffix, fetch_shadows, ctx, seed=1234):
+        super().__init__(iteration_freq, log_dir, shadow_ratio)
+        self._ctx = ctx
+        self._infer_model = infer_model
+        self._input_tensor = input_tensor
+        self._name_suffix = name_suffix
+        self._best_mean_div_addr = os.path.join(self._log_dir, f"best_ratio_{name_suffix}.json")
+        self.best_mean_div_holder.load(self._best_mean_div_addr)
+        self._bands = loader.get_band_measurements()
+        self.sample_indices = sample_indices_for_testing(sample_count, neighborhood, shadow_map, fetch_shadows,
+                                                         numpy.random.default_rng(seed))
+        self._data_sample_list = load_samples_for_testing(data_set, self.sample_indices)
+        self.last_stats = None
+
+    def last_divergences(self):
+        """[mean divergence] of the last validation run ([] before one)"""
+        return [] if self.last_stats is None else [self.last_stats[0]]
+
+    def after_run(self, current_iteration=0):
+        self.validation_itr_mark = self._is_validation_itr(current_iteration)
+        if not self.validation_itr_mark:
+            return
+        from hypelcnn_amd.gan.gan_train_for_shadow import create_stats
+        sess = self._ctx.session()
+        n = self._data_sample_list.shape[0]
+        ct = sess.compile_phase(self._ctx.tower, n, outputs=[self._infer_model], key="validate_" + self._name_suffix)
+        x = torch.as_tensor(self._data_sample_list).to(sess.backend.device)
+        ct.set_input(self._input_tensor.name, x)
+        ct.forward()
+        generated = ct.value(self._infer_model, copy=False)
+        ratio = torch.as_tensor(numpy.asarray(self._shadow_ratio, numpy.float32)).to(x.device)
+        div_mean, div_upper, mean, std = create_stats(generated, x, ratio)
+        self.last_stats = (div_mean, div_upper, mean.cpu().numpy(), std.cpu().numpy())
+        self.best_mean_div_holder.add_point(current_iteration, div_mean)
+        self.best_mean_div_holder.save(self._best_mean_div_addr)
+        self.best_upper_div_holder.add_point(current_iteration, div_upper)
+        with open(os.path.join(self._log_dir, "summaries.jsonl"), "a") as f:
+            f.write(json.dumps({"step": int(current_iteration), f"divergence_{self._name_suffix}": div_mean}) + "\n")
+        print(f"Validation metrics for {self._name_suffix} #{current_iteration}")
+        print_overall_info(self.last_stats[2], self.last_stats[3])
+        print(f"Divergence for {self._name_suffix}; mean:{div_mean}, upper:{div_upper}")
+        print(f"Best {self._name_suffix} options:{self.best_mean_div_holder}")
+
+
+def sample_indices_for_testing(sample_count, neighborhood, shadow_map, fetch_shadows, rng):
+    """The (x, y) scene coordinates load_samples_for_testing (reference :362-382) draws, with replacement, from the
+    shadowed (> 0) or lit (== 0) pixels of the unpadded map.  Drawn with a seeded NumPy generator instead of Python's
+    `random`, so the sample is reproducible; the distribution is the same."""
+    if neighborhood > 0:
+        shadow_map = shadow_map[neighborhood:-neighborhood, neighborhood:-neighborhood]
+    indices = numpy.where(shadow_map > 0) if fetch_shadows else numpy.where(shadow_map == 0)
+    picks = rng.integers(0, indices[0].size, size=sample_count)
+    return numpy.stack([indices[1][picks], indices[0][picks]], axis=1)
+
+
+def load_samples_for_testing(data_set, sample_indices):
+    """[n, bands] float32: the spectrum of each (x, y) (neighbourhood 0: the reference's squeeze(axis=[1, 2]))."""
+    band_size = data_set.get_casi_band_count()
+    samples = [data_set.get_data_point(int(x), int(y))[:, :, 0:band_size] for x, y in sample_indices]
+    return numpy.ascontiguousarray(numpy.asarray(samples, numpy.float32).reshape(len(samples), band_size))
+
+
+def print_overall_info(mean, std):
+    print("Mean&std Generated vs Original Ratio: ")
+    band_size = mean.shape[0]
+    for band_index in range(0, band_size):
+        prefix = "[ " if band_index == 0 else ""
+        postfix = " ]" if band_index == band_size - 1 and band_index != 0 else ""
+        print(f"{prefix}{mean[band_index]:2.4f}\u00B1{std[band_index]:2.2f}{postfix}",
+              end="\n" if band_index % 5 == 1 else " ")

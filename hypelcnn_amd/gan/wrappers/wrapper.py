@@ -35,3 +35,8 @@ class InferenceWrapper(ABC):
     @abstractmethod
     def create_generator_restorer(self):
         pass
+
+    @abstractmethod
+    def create_inference_hook(self, data_set, loader, log_dir, neighborhood, shadow_map, shadow_ratio,
+                              validation_iteration_count, validation_sample_count, backend=None):
+        """(backend: this package's addition -- the device the hook's generator tower runs on; None = the HIP device)"""

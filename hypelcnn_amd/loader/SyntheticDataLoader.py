@@ -5,7 +5,8 @@ which exists in the build or test environment, so every benchmark and end-to-end
 `path` selects the geometry, e.g. "grss2013" (144 HSI bands + LiDAR, 15 classes), "grss2018" (48 + LiDAR, 20),
 "avon" (360 bands, no LiDAR, 2 classes), optionally followed by ":key=value" overrides
 (h, w, bands, classes, lidar, seed, samples, gan_ckpt=<npz checkpoint of a shadow GAN for the generator-based
-shadow augmenters>, base_dir=<directory that get_model_base_dir reports, e.g. where TFRecord exports live>).  Each class has its own smooth spectrum and height, pixels are
+shadow augmenters>, base_dir=<directory that get_model_base_dir reports, e.g. where TFRecord exports live>,
+dtype=uint16|int16|uint8 to quantise the scene to that integer dtype, as the contest rasters are stored; default float32).  Each class has its own smooth spectrum and height, pixels are
 class spectrum + noise laid out in blobs, so that a classifier can actually learn the scene."""
 import numpy
 
@@ -22,6 +23,16 @@ PRESETS = {
 }
 
 
+def quantise(casi, dtype):
+    """Rounds the float32 scene (values about 700..4700) into the integer dtype: uint16 / int16 keep it as is,
+    uint8 scales it by 1/20 first."""
+    if dtype not in ("uint16", "int16", "uint8"):
+        raise ValueError(f"SyntheticDataLoader: dtype={dtype} is not one of float32, uint16, int16, uint8")
+    info = numpy.iinfo(dtype)
+    v = casi / 20.0 if dtype == "uint8" else casi
+    return numpy.clip(numpy.rint(v), info.min, info.max).astype(dtype)
+
+
 class SyntheticDataLoader(DataLoader):
 
     def __init__(self, path):
@@ -30,7 +41,7 @@ class SyntheticDataLoader(DataLoader):
         cfg.update(seed=1234, samples=0.5)
         for kv in parts[1:]:
             k, v = kv.split("=", 1)
-            cfg[k] = v if k in ("gan_ckpt", "base_dir") else (float(v) if k == "samples" else int(v))
+            cfg[k] = v if k in ("gan_ckpt", "base_dir", "dtype") else (float(v) if k == "samples" else int(v))
         self.cfg = cfg
         self._targets = None
 
@@ -53,6 +64,8 @@ class SyntheticDataLoader(DataLoader):
         self._shadow_map = (sd < (min(h, w) / 4.5) ** 2).astype(numpy.uint8)
         atten = 0.35 + 0.3 * numpy.linspace(0, 1, b)
         casi = numpy.where(self._shadow_map[..., None] == 1, casi * atten, casi).astype(numpy.float32)
+        if c.get("dtype", "float32") != "float32":
+            casi = quantise(casi, c["dtype"])
         lidar = None
         if c["lidar"]:
             heights = rng.rand(k) * 30

@@ -414,6 +414,15 @@ int hypel_argmax_scatter(const float* logits, int64_t ld, int64_t n, int32_t c, 
 int hypel_gather_pairs_f32(const float* normal, const float* shadow, const int64_t* idx, int64_t n, int32_t bands,
                            const float* ratio, const float* u1, const float* u2, float rate, float* out_x, float* out_y,
                            hypel_stream_t stream);
+/* The GAN scene conversion's write-back (gan/gan_infer_image_for_shadow.py:84-85, ((g * casi_max) + casi_min)
+ * .astype(dtype) per pixel): out[rows[i] * ld_out + b] = cast(src[i * ld_src + b] * scale[b] + offset[b]) for i < n,
+ * b < bands; rows NULL = identity.  Multiply and add are rounded separately (no fma), as NumPy's float32 operators.
+ * cast: float32 as is; the integer dtypes as NumPy on x86-64 -- truncation to int32 (NaN, +-inf and out-of-range
+ * values give INT_MIN), then the low bits.  out_dtype: HYPEL_DTYPE_*. */
+enum { HYPEL_DTYPE_F32 = 0, HYPEL_DTYPE_U16 = 1, HYPEL_DTYPE_I16 = 2, HYPEL_DTYPE_U8 = 3 };
+int hypel_denorm_scatter(const float* src, int64_t ld_src, const int64_t* rows, int64_t n, int32_t bands,
+                         const float* scale, const float* offset, int32_t out_dtype, void* out, int64_t ld_out,
+                         hypel_stream_t stream);
 
 /* ---- LRN (tf.nn.local_response_normalization, CONCNNModel.py:37,41) -------------------------------------- */
 int hypel_lrn_fwd(const float* x, int64_t ldx, int64_t rows, int32_t c, int32_t radius, float bias, float alpha,
