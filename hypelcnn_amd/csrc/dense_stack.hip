@@ -29,12 +29,6 @@ typedef float ds_f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-#ifndef DS_DIAG
-#define DS_DIAG 0  // timing diagnostics (results wrong): 1 = no weight staging, 2 = no layer products, 3 = no zero fill
-#endif
-#ifndef DS_REGW
-#define DS_REGW 1  // forward of stacks with every width <= 64: weights in registers (0: the LDS-staged kernel for every shape)
-#endif
 constexpr int DS_ROWS = 16;
 constexpr int DS_THREADS = 256;
 constexpr int DS_WAVES = 4;
@@ -61,7 +55,6 @@ __device__ __forceinline__ float ds_act(float v, int act, float alpha) {
 }
 
 __device__ __forceinline__ void ds_zero(float* p, int n, int tid) {
-    if (DS_DIAG == 3) return;
     for (int i = tid; i < n; i += DS_THREADS) p[i] = 0.0f;
 }
 
@@ -100,7 +93,6 @@ __device__ __forceinline__ void ds_zero_w_margins(float* wl, int cin, int cout, 
 // W_l [cin][cout] -> LDS [cin][cp] (margins: ds_zero_w_margins)
 __device__ __forceinline__ void ds_stage_w(float* wl, const float* __restrict__ w, int cin, int cout, int cp, int lane,
                                            int wave) {
-    if (DS_DIAG == 1) return;
     for (int r = wave; r < cin; r += DS_WAVES) ds_dma_row(w + r * cout, wl + r * cp, cout, lane);
 }
 
@@ -132,7 +124,7 @@ __device__ __forceinline__ void ds_layer_fwd(const float* src, float* dst, const
         ds_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
         const float* ap = src + r * pa + kq;
         const float* bp = wl + kq * cp + 16 * jt + r;
-        if (DS_DIAG != 2) acc = ds_dot(ap, 4, bp, 4 * cp, ksteps, acc);
+        acc = ds_dot(ap, 4, bp, 4 * cp, ksteps, acc);
         const int c = 16 * jt + r;
         if (c < cout) {
             const float bv = bias[c];
@@ -209,8 +201,8 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stack_fwd_kernel(const float
 // tiles -- one per wave -- and at most 16 k-steps, so a lane's share of ALL layers' weights is <= 4 x 16 fragments.  They are
 // requested straight from global memory (L2: every block reads the same 40 KB) into registers at kernel entry, all layers at once,
 // under the input tile's DMA; no weight image in LDS, no margin zeroing, none of the 160 dword LDS-DMA instructions and their drain in
-// front of the first barrier (round-4 diagnostic DS_DIAG=1: 4.3 us of the forward launch's 11.2).  Same k-step order as
-// ds_layer_fwd, i.e. the same fmaf chain.
+// front of the first barrier (round-4 timing with the weight staging skipped: 4.3 us of the forward launch's 11.2).  Same k-step
+// order as ds_layer_fwd, i.e. the same fmaf chain.
 constexpr int DS_RW = 64;             // widest layer of the register-weight path
 constexpr int DS_RK = DS_RW / 4;      // k-steps of its widest layer
 __global__ __launch_bounds__(DS_THREADS) void dense_stack_fwd_regw_kernel(const float* __restrict__ x, int64_t ldx, int64_t n,
@@ -457,8 +449,8 @@ bool ds_shape(int n_layers, const int32_t* widths, int32_t act_mask, float alpha
 }
 
 // The register-weight forward pays a fixed price (4 x 16 predicated fragment loads, a 16-step predicated product loop) and saves the
-// weight image's staging, so it is chosen by the size of that image -- same-box A/B, round 5 (tools/exp/dense_regw_ab.sh):
-// 64-64-64-32 (10 240 floats) 11.3 -> 8.8 us, 64-64 (4 096) 5.9 -> 6.5, 16-16-16-8 (640) 6.2 -> 8.1.
+// weight image's staging, so it is chosen by the size of that image -- same-box A/B, round 5 (tools/exp/dense_regw_ab.sh, kept at
+// 112c2f2): 64-64-64-32 (10 240 floats) 11.3 -> 8.8 us, 64-64 (4 096) 5.9 -> 6.5, 16-16-16-8 (640) 6.2 -> 8.1.
 constexpr int DS_REGW_MIN_WEIGHTS = 8192;
 bool ds_regw(const DsShape& sh) {
     for (int l = 0; l <= sh.n_layers; ++l)
@@ -505,7 +497,7 @@ extern "C" int hypel_dense_stack_fwd(const float* x, int64_t ldx, int64_t n, int
     const int32_t widths[DS_MAXL + 1] = {w0, w1, w2, w3, w4};
     DsShape sh;
     HYPEL_REQUIRE(x && w && b && out && n > 0 && ds_shape(n_layers, widths, act_mask, alpha, sh), "hypel_dense_stack_fwd");
-    if (DS_REGW && ds_regw(sh)) {
+    if (ds_regw(sh)) {
         hipLaunchKernelGGL(dense_stack_fwd_regw_kernel, dim3(hypel_dense_stack_blocks(n)), dim3(DS_THREADS), ds_fwd_regw_lds(sh), ST,
                            x, ldx, n, sh, w, b, out, ldo, DsApps{1, 0, 0, 0, 0});
         HYPEL_CHECK_LAUNCH("hypel_dense_stack_fwd");
@@ -528,7 +520,7 @@ extern "C" int hypel_dense_stack_fwd_apps(const float* x, int64_t ldx, int64_t n
     DsShape sh;
     HYPEL_REQUIRE(x && w && b && out && n > 0 && n_apps >= 1 && n_apps <= 16 && ds_shape(n_layers, widths, act_mask, alpha, sh),
                   "hypel_dense_stack_fwd_apps");
-    if (DS_REGW && ds_regw(sh)) {
+    if (ds_regw(sh)) {
         hipLaunchKernelGGL(dense_stack_fwd_regw_kernel, dim3(hypel_dense_stack_blocks_apps(n, n_apps)), dim3(DS_THREADS),
                            ds_fwd_regw_lds(sh), ST, x, ldx, n, sh, w, b, out, ldo, DsApps{n_apps, w_stride, b_stride, 0, 0});
         HYPEL_CHECK_LAUNCH("hypel_dense_stack_fwd_apps");

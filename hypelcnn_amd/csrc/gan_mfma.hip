@@ -17,8 +17,6 @@
 //    small diagonal reduction per block, in a fixed order (no float atomics).
 // fp32 MFMA is a k-ordered fmaf chain: same arithmetic class as the VALU kernels in gan.hip, which stay in charge
 // of bands < 16 and bands > 384 (and of everything under HYPEL_GAN_MFMA=0).
-#include <stdlib.h>
-
 #include "common.h"
 
 // No fused multiply-adds outside the MFMAs: whether hipcc contracts `gd * f` into a neighbouring sum depends on the code
@@ -35,37 +33,10 @@ struct GmApps {
 namespace {
 
 constexpr int GM_ROWS = 16;     // samples per row tile
-#ifndef GM_WAVES_N
-#define GM_WAVES_N 8
-#endif
-#ifndef GM_MAXT_N
-#define GM_MAXT_N 3
-#endif
-constexpr int GM_WAVES = GM_WAVES_N;  // wavefronts per block (two per SIMD)
+constexpr int GM_WAVES = 8;     // wavefronts per block (two per SIMD)
 constexpr int GM_THREADS = 64 * GM_WAVES;
-constexpr int GM_MAXT = GM_MAXT_N;    // column tiles per wave: bands <= 16 * GM_WAVES * GM_MAXT
+constexpr int GM_MAXT = 3;      // column tiles per wave: bands <= 16 * GM_WAVES * GM_MAXT
 constexpr int GM_MAX_BANDS = 16 * GM_WAVES * GM_MAXT;
-#ifndef GM_PIPE
-#define GM_PIPE 0  // 1: fragments of the next 16-column chunk requested by hand ahead of the current chunk's MFMAs
-                   // (measured slower than hipcc's own schedule: forward 62 vs 51 us, backward 177 vs 167 us at N = 4096)
-#endif
-#ifndef GM_TWO_CHAINS
-#define GM_TWO_CHAINS 1
-#endif
-#ifndef GM_DIAG
-#define GM_DIAG 0
-#endif
-#ifndef GM_FWD_ROLLED
-#define GM_FWD_ROLLED 0  // forward kernel: 1 = rolled layer loop (54 vs 51 us); the backward kernel's recompute is always
-                         // rolled (unrolled it spills > 200 registers)
-#endif
-#if GM_DIAG == 7  // forward phase stamps: cycles of thread 0 of block 0 per phase, reported through out[0..7]
-__device__ long long gm_fdbg[8];
-__device__ long long gm_fmark;
-#define GM_FMARK(i) { if (threadIdx.x == 0 && blockIdx.x == 0) { const long long now_ = clock64(); gm_fdbg[i] += now_ - gm_fmark; gm_fmark = now_; } }
-#else
-#define GM_FMARK(i)
-#endif
 constexpr int GM_GP = 17;       // pitch of a 16 x 16 filter-gradient tile in LDS (diagonal reads hit distinct banks)
 
 struct GmGeo {
@@ -93,13 +64,11 @@ __host__ __device__ inline int gm_woff(int bands, int l) {
 __host__ __device__ inline int gm_raw(int bands) {  // floats of the block's LDS copy of every layer's taps + 8 biases
     return (gm_woff(bands, 7) + 8 + 3) / 4 * 4;
 }
-#ifndef GM_FWD_ONE_TABLE
-#define GM_FWD_ONE_TABLE 1  // forward kernel: ONE tap table (a second barrier per layer instead of a second table): 80.7 instead
-                            // of 85.1 KB at 360 bands, i.e. TWO resident blocks per CU (2 x 85.1 KB > 160 KB by 5 KB)
-#endif
+// forward kernel: ONE tap table (a second barrier per layer instead of a second table): 80.7 instead of 85.1 KB at 360
+// bands, i.e. TWO resident blocks per CU (2 x 85.1 KB > 160 KB by 5 KB)
 __host__ __device__ inline size_t gm_fwd_lds(int bands) {
     const GmGeo g = gm_geo(bands);
-    return sizeof(float) * (3 * (size_t)GM_ROWS * g.pitch + (GM_FWD_ONE_TABLE ? 1 : 2) * 3 * (size_t)g.bp + gm_raw(bands));
+    return sizeof(float) * (3 * (size_t)GM_ROWS * g.pitch + 3 * (size_t)g.bp + gm_raw(bands));
 }
 __host__ __device__ inline int gm_atiles(int bands) { return (bands + 30) / 16 + 2; }  // upper bound of the tile offsets a
 __host__ __device__ inline size_t gm_bwd_lds(int bands) {
@@ -113,14 +82,6 @@ __host__ __device__ inline size_t gm_bwd_lds(int bands) {
 // pitch = 18 mod 32 the 32 lanes of a ds_read_b32 group (16 rows x 2 k-slots) hit 32 banks.  B fragment: lane
 // (c = lane & 15, kq) supplies T[k][j0 + c] = w[k - (j0 + c) + pad] (mirrored: w[(j0 + c) - k + pad]) from the
 // zero-margined tap table wz (taps at [bp, bp + ksz)).
-#ifndef GM_CONV_SCHED
-#define GM_CONV_SCHED 0  // 1: the fetch / mac / fetch / mac order of the loop below pinned with sched_barrier
-#endif
-#if GM_CONV_SCHED
-#define GM_CONV_PIN __builtin_amdgcn_sched_barrier(0);
-#else
-#define GM_CONV_PIN
-#endif
 template <bool MIRROR>
 __device__ __forceinline__ gm_f32x4 gm_conv_tile(const float* __restrict__ src, const float* __restrict__ wz, const GmGeo g,
                                                  int j0, int ksz, int pad, int lane) {
@@ -135,22 +96,11 @@ __device__ __forceinline__ gm_f32x4 gm_conv_tile(const float* __restrict__ src, 
     // j0 / ksz / pad are wave-uniform (the callers take the wave index through readfirstlane), so this is a scalar
     // loop.  Two chunks per trip, the fragments of one requested while the other's four MFMAs run: left to itself
     // hipcc loaded two fragments, waited, issued two MFMAs, and again -- the LDS round trip exposed twice per chunk
-    // (61 cycles per MFMA and SIMD instead of 32).
+    // (61 cycles per MFMA and SIMD instead of 32).  The first hand prefetch, before this loop was scalar, measured slower
+    // than hipcc's own schedule (forward 62 vs 51 us, backward 177 vs 167 us at N = 4096); pinning the fetch / mac order
+    // with sched_barrier, as gm_wgrad_tiles does, measured slower here.
     const int k0 = lo & ~15;
     const int nch = hi >= k0 ? ((hi - k0) >> 4) + 1 : 0;
-#if GM_DIAG == 4  // timing diagnostics: everything but the products
-    acc[0] = (float)nch;
-    return acc;
-#elif GM_DIAG
-    for (int c = 0; c < nch; ++c)
-        for (int s = 0; s < 4; ++s) {
-            const int k = k0 + 16 * c + 4 * s;
-            const float av = GM_DIAG == 1 ? ap[k] : 1.0f + (float)s;
-            const float bv = GM_DIAG == 2 ? (MIRROR ? tp[-k] : tp[k]) : 2.0f + (float)s;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        }
-    return acc;
-#else
     if (nch == 0) return acc;
     float a0[4], b0[4], a1[4], b1[4];
     auto fetch = [&](int c, float (&a)[4], float (&b)[4]) {
@@ -165,27 +115,18 @@ __device__ __forceinline__ gm_f32x4 gm_conv_tile(const float* __restrict__ src, 
     // cycles but its result is ready after 40, and a wave has one partner on its SIMD
     gm_f32x4 acc2 = {0.0f, 0.0f, 0.0f, 0.0f};
     auto mac = [&](const float (&a)[4], const float (&b)[4]) {
-#if GM_TWO_CHAINS
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], acc, 0, 0, 0);
         acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], acc2, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], acc, 0, 0, 0);
         acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], acc2, 0, 0, 0);
-#else
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
-#endif
     };
     fetch(0, a0, b0);
     int c = 0;
     for (; c + 2 < nch; c += 2) {
         fetch(c + 1, a1, b1);
-        GM_CONV_PIN
         mac(a0, b0);
-        GM_CONV_PIN
         fetch(c + 2, a0, b0);
-        GM_CONV_PIN
         mac(a1, b1);
-        GM_CONV_PIN
     }
     if (c + 1 < nch) {  // two chunks left
         fetch(c + 1, a1, b1);
@@ -194,12 +135,9 @@ __device__ __forceinline__ gm_f32x4 gm_conv_tile(const float* __restrict__ src, 
     } else {
         mac(a0, b0);
     }
-#if GM_TWO_CHAINS
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] += acc2[e];
-#endif
     return acc;
-#endif
 }
 
 // Every layer's taps and the 8 biases are copied into LDS ONCE per block (gm_stage_raw); a layer's zero-margined table
@@ -226,8 +164,6 @@ struct GmKeep {
     static constexpr int V4 = SLOTS * GM_MAXT + 2;  // float4 per thread and row tile
 };
 
-typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
-
 // STASH: every layer's outputs / branch bits go straight from the epilogue to this thread's place in the kept-activation
 // buffer (`stash` = the row tile's base + tid, in float4): nothing stays in registers, the unrolled forward stays cheap.
 template <bool ENC, bool KEEP, bool ROLLED = true, bool STASH = false, bool ONE_TABLE = false, bool TAP = false>
@@ -238,10 +174,7 @@ __device__ __forceinline__ int gm_forward(float* lds0, float* wz0, float* wz1, c
                                           gm_f32x4* __restrict__ stash = nullptr, float* __restrict__ enc_out = nullptr,
                                           int64_t ld_enc = 0) {
     constexpr int L = ENC ? 4 : 7;
-#ifndef GM_FWD_REGSKIP
-#define GM_FWD_REGSKIP 1
-#endif
-    constexpr bool REGSKIP = GM_FWD_REGSKIP && !KEEP;
+    constexpr bool REGSKIP = !KEEP;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: tile loops are wave-uniform
     const int col = lane & 15, rg = lane >> 4;
     const int img = GM_ROWS * g.pitch;
@@ -264,11 +197,9 @@ __device__ __forceinline__ int gm_forward(float* lds0, float* wz0, float* wz1, c
         if constexpr (ONE_TABLE) {  // wz0 == wz1: every wave must have left layer l - 1's products before its taps go
             if (l > 0) __syncthreads();
         }
-        GM_FMARK(4)  // end of the previous layer's epilogue .. (ONE_TABLE barrier)
         gm_fill_taps(wz, g, w + woff, ksz, tid);
         woff += ksz;
         __syncthreads();  // taps of layer l and the outputs of layer l - 1 are in LDS
-        GM_FMARK(1)  // tap table + barrier
         const float* src = lds0 + (l % 3) * img;          // n_l (x for l = 0)
         const float* skip2 = lds0 + ((l + 2) % 3) * img;  // n_{l-1}
         float* dst = lds0 + ((l + 1) % 3) * img;
@@ -296,7 +227,6 @@ __device__ __forceinline__ int gm_forward(float* lds0, float* wz0, float* wz1, c
             if (jt >= g.nt) break;
             const int j0 = 16 * jt;
             const gm_f32x4 acc = gm_conv_tile<false>(src, wz, g, j0, ksz, pad, lane);
-            GM_FMARK(2)  // products
             const int c = j0 + col;
             [[maybe_unused]] gm_f32x4 kept = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -349,7 +279,6 @@ __device__ __forceinline__ int gm_forward(float* lds0, float* wz0, float* wz1, c
             if constexpr (STASH) {  // slots n_1..n_3 (encoder) / n_1..n_6 + the tanh output
                 if (ENC ? l < 3 : true) stash[(l * GM_MAXT + m) * GM_THREADS] = kept;
             }
-            GM_FMARK(3)  // epilogue
         }
         if constexpr (KEEP) {
 #pragma unroll
@@ -425,12 +354,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     extern __shared__ __attribute__((aligned(16))) float gm_lds[];
     const GmGeo g = gm_geo(bands);
     const int tid = threadIdx.x;
-#if GM_DIAG == 7
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        for (int i = 0; i < 8; ++i) gm_fdbg[i] = 0;
-        gm_fmark = clock64();
-    }
-#endif
     const int bpa = gridDim.x / apps.n_apps, app = blockIdx.x / bpa, blk = blockIdx.x - app * bpa;
     w += app * apps.w_stride;
     bias += app * apps.b_stride;
@@ -438,10 +361,8 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     out += (int64_t)app * n * ldo;
     if constexpr (TAP) enc_out += (int64_t)app * n * ld_enc;
     float* const bufs[3] = {gm_lds, gm_lds + GM_ROWS * g.pitch, gm_lds + 2 * GM_ROWS * g.pitch};
-    constexpr bool ONE = GM_FWD_ONE_TABLE != 0;
-    float* wz0 = gm_lds + 3 * GM_ROWS * g.pitch;
-    float* wz1 = ONE ? wz0 : wz0 + 3 * g.bp;
-    float* raw = wz1 + 3 * g.bp;
+    float* wz = gm_lds + 3 * GM_ROWS * g.pitch;  // the one tap table (see gm_fwd_lds)
+    float* raw = wz + 3 * g.bp;
     static_assert(GM_WAVES == 8 && GM_ROWS == 16, "gm_rows_issue: two rows per wave");
     const int64_t tiles = (n + GM_ROWS - 1) / GM_ROWS;
     // Block set-up.  Wide spectra: the taps, the biases and the first row tile are REQUESTED first, the zero fill of the
@@ -460,7 +381,7 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         }
         if (blk < tiles)
             gm_rows_issue(xr, g, x + (int64_t)blk * GM_ROWS * ldx, ldx, (int)min((int64_t)GM_ROWS, n - (int64_t)blk * GM_ROWS), tid);
-        gm_zero(gm_lds, 3 * GM_ROWS * g.pitch + (ONE ? 3 : 6) * g.bp, tid);  // image padding and tap margins stay zero
+        gm_zero(gm_lds, 3 * GM_ROWS * g.pitch + 3 * g.bp, tid);  // image padding and tap margins stay zero
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < GM_WCH; ++k) {
@@ -470,12 +391,11 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         if (blk < tiles) gm_rows_store(bufs[0], g, xr, tid);
         __syncthreads();  // the LDS copy of the taps is complete before the first layer builds its table
     } else {
-        gm_zero(gm_lds, 3 * GM_ROWS * g.pitch + (ONE ? 3 : 6) * g.bp, tid);
+        gm_zero(gm_lds, 3 * GM_ROWS * g.pitch + 3 * g.bp, tid);
         gm_stage_raw(raw, bands, w, bias, tid);
         __syncthreads();
         if (blk < tiles) gm_load_rows(bufs[0], g, x + (int64_t)blk * GM_ROWS * ldx, ldx, (int)min((int64_t)GM_ROWS, n - (int64_t)blk * GM_ROWS), tid);
     }
-    GM_FMARK(0)  // block set-up
     float keep[6][GM_MAXT][4];
     unsigned mask[7];
     for (int64_t t = blk; t < tiles; t += bpa) {
@@ -485,16 +405,12 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         gm_f32x4* sp = nullptr;
         if constexpr (STASH)
             sp = reinterpret_cast<gm_f32x4*>(stash) + (size_t)(app * tiles + t) * GmKeep<ENC>::V4 * GM_THREADS + tid;
-        gm_forward<ENC, false, GM_FWD_ROLLED != 0, STASH, ONE, TAP>(gm_lds, wz0, wz1, g, raw, raw + gm_woff(bands, 7),
-                                                                    out + r0 * ldo, ldo, rows_valid, tid, keep, mask, sp,
-                                                                    TAP ? enc_out + r0 * ld_enc : nullptr, ld_enc);
+        // unrolled layer loop: the rolled one measured 54 vs 51 us
+        gm_forward<ENC, false, false, STASH, true, TAP>(gm_lds, wz, wz, g, raw, raw + gm_woff(bands, 7), out + r0 * ldo, ldo,
+                                                        rows_valid, tid, keep, mask, sp, TAP ? enc_out + r0 * ld_enc : nullptr,
+                                                        ld_enc);
         __syncthreads();  // the next row tile overwrites bufs[0]
-        GM_FMARK(5)  // last epilogue .. tile end
     }
-#if GM_DIAG == 7
-    if (threadIdx.x == 0 && blockIdx.x == 0)
-        for (int i = 0; i < 8; ++i) out[i] = (float)gm_fdbg[i];
-#endif
 }
 
 // Sum over the 64 lanes of a wave in registers (row_shr 1 / 2 / 4 / 8 inside the rows of 16, row_bcast15 / 31 across them:
@@ -516,270 +432,17 @@ __device__ __forceinline__ float gm_wave_sum(float v) {
 // two k-slots a ds_read_b32 lane group serves (kq = 0, 1 / 2, 3) are 8 rows apart: with the images' pitch of 18 mod 32
 // (chosen for the convolution tiles' fragments) that is a bank distance of 16, so the 2 x 16 consecutive columns of a
 // group hit 32 banks (rows 4 s + kq collided in two banks per group: every fragment read took two LDS cycles more).
-#ifndef GM_BROW
-#define GM_BROW 1
-#endif
-__device__ __forceinline__ int gm_brow(int kq) { return GM_BROW ? 4 * (kq >> 1) + 8 * (kq & 1) : 4 * kq; }
+__device__ __forceinline__ int gm_brow(int kq) { return 4 * (kq >> 1) + 8 * (kq & 1); }
 
 // ---- filter gradient of one layer (step B of the backward kernels) ---------------------------------------------------
 // G_a = sum_j X_{j+a}^T . Z_j for every tile offset a in [a_lo, a_hi] (X_t, Z_t: the 16-column tiles of the [16 x B] LDS
-// images; tap t = d + pad is the sum of diagonal d of the G_a that contain it).  Work items are (offset, half of the
-// column tiles) -- layers with fewer offsets than waves (k <= B / 4 at 360 bands: 5 - 7 offsets) cut the j axis at nt / 2,
-// so that they still feed 8 waves -- in half-major, offset-minor order; the list is cut into GM_WAVES contiguous runs of
-// nearly equal work (gm_wgrad_schedule, once per block) and a wave sweeps its run in sub-runs of <= GM_RUN CONSECUTIVE
-// offsets: at column tile j the offsets a0 .. a0 + C - 1 multiply X tiles j + a0 .. j + a0 + C - 1 by the SAME Z tile, and
-// the next j needs one new X tile and one new Z tile -- 8 fragment words for 4 C MFMAs where one (offset, j) pair at a
-// time took 8 for 4 (round-4 phase stamps: this step 112 k cycles per row tile against 64 k of MFMA issue on its busiest
-// SIMD).  An X tile outside [0, nt) enters as zeros (the ragged ends of a sub-run: C (C - 1) / 2 idle tile pairs).  Fixed
-// order of the sums: j ascending inside an item, k-steps 0..3 (two chains 0,2 / 1,3 when C <= 2), halves added in order
-// by gm_diag_sum.
-#ifndef GM_RUN
-#define GM_RUN 4
-#endif
-#ifndef GM_BSTEP
-#define GM_BSTEP 2  // 2: pair at a time with gm_conv_tile's loop shape (gm_wgrad_tiles_v2, adopted: 186 -> 180 us at 8192 x 360);
-                    // 0: the round-3 loop (gm_wgrad_tiles_v0, same sums bit for bit); 1: balanced runs of consecutive offsets (slower)
-#endif
-#ifndef GM_BSCHED
-#define GM_BSCHED 1
-#endif
-#ifndef GM_BDIAG
-#define GM_BDIAG 0  // timing diagnostics of the filter-gradient step (results garbage): 1 = no fragment reads in the j loop,
-                    // 2 = no MFMAs
-#endif
-struct GmItems {
-    int a_lo, n_off, halves, n_items, jmid;  // half 0: column tiles [0, jmid], half 1: (jmid, nt)
-};
-__device__ __forceinline__ GmItems gm_items(const GmGeo g, int ksz, int pad) {
-    GmItems it;
-    it.a_lo = -((pad + 15) / 16);
-    const int a_hi = (ksz - 1 - pad + 15) / 16;
-    it.n_off = a_hi - it.a_lo + 1;
-    it.halves = (GM_BSTEP == 1 && it.n_off < GM_WAVES && 2 * it.n_off <= gm_atiles(g.bands) && g.nt >= 2) ? 2 : 1;
-    it.n_items = it.n_off * it.halves;
-    it.jmid = it.halves == 2 ? (g.nt - 1) / 2 : g.nt - 1;
-    return it;
-}
-// column tiles [lo, hi] of item i (empty: lo > hi)
-__device__ __forceinline__ void gm_item_range(const GmItems& it, int nt, int i, int& a, int& lo, int& hi) {
-    const int h = i >= it.n_off ? 1 : 0;
-    a = it.a_lo + (i - h * it.n_off);
-    lo = max(h ? it.jmid + 1 : 0, -a);
-    hi = min(h || it.halves == 1 ? nt - 1 : it.jmid, nt - 1 - a);
-}
-// sched[l * GM_WAVES + w] = first | last << 8: the items [first, last) of layer l that wave w sweeps.  Item i goes to wave
-// floor((work before i + work_i / 2) * GM_WAVES / total) -- a running comparison, no division.
-__device__ __forceinline__ void gm_wgrad_schedule(int* sched, const GmGeo g, int L, int tid) {
-    if (tid >= L * GM_WAVES) return;
-    const int l = tid / GM_WAVES, w = tid % GM_WAVES;
-    const int ksz = gm_ksz(g.bands, l), pad = (ksz - 1) / 2;
-    const GmItems it = gm_items(g, ksz, pad);
-    int total = 0;
-    for (int i = 0; i < it.n_items; ++i) {
-        int a, lo, hi;
-        gm_item_range(it, g.nt, i, a, lo, hi);
-        total += max(0, hi - lo + 1);
-    }
-    int first = it.n_items, last = 0, cum = 0, owner = 0;
-    for (int i = 0; i < it.n_items; ++i) {
-        int a, lo, hi;
-        gm_item_range(it, g.nt, i, a, lo, hi);
-        const int wk = max(0, hi - lo + 1);
-        if (total > 0) {
-            while (owner < GM_WAVES - 1 && (owner + 1) * 2 * total <= (2 * cum + wk) * GM_WAVES) ++owner;
-        } else {
-            owner = i % GM_WAVES;
-        }
-        if (owner == w) {
-            first = min(first, i);
-            last = max(last, i + 1);
-        }
-        cum += wk;
-    }
-    if (first > last) first = last = 0;
-    sched[tid] = first | (last << 8);
-}
-
-template <int C>
-__device__ __forceinline__ void gm_wgrad_run(const float* __restrict__ X, const float* __restrict__ Z, float* __restrict__ G,
-                                             const GmGeo g, const GmItems& it, int i0, int lane) {
-    constexpr int NCH = C <= 2 ? 2 : 1;
-    const int col = lane & 15, rg = lane >> 4;
-    int a0, jA, jB;
-    gm_item_range(it, g.nt, i0, a0, jA, jB);
-    {
-        int a, lo, hi;
-        gm_item_range(it, g.nt, i0 + C - 1, a, lo, hi);
-        jA = min(jA, lo);  // the union of the items' ranges: they differ only by the clipping of j + a to [0, nt)
-        jB = max(jB, hi);
-    }
-    gm_f32x4 acc[C][NCH];
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) acc[i][c] = gm_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (jA <= jB) {
-        const float* xp = X + gm_brow(rg) * g.pitch + col;
-        const float* zp = Z + gm_brow(rg) * g.pitch + col;
-        // raw fragment of X tile t (address clamped); the caller replaces it by zeros where `ok` is false (wave-uniform)
-        auto xtile = [&](int t, float (&f)[4]) -> bool {
-            const bool ok = t >= 0 && t < g.nt;
-            const int tc = ok ? t : 0;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) f[s] = xp[16 * tc + s * g.pitch];
-            return ok;
-        };
-        float xf[C][4], zf[4], xn[4], zn[4];
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            const bool ok = xtile(jA + a0 + i, xf[i]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) xf[i][s] = ok ? xf[i][s] : 0.0f;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) zf[s] = zp[16 * jA + s * g.pitch];
-        for (int j = jA; j <= jB; ++j) {
-            // the next column tile's two new fragments, requested ahead of this tile's products (the last trip
-            // re-reads tile jB: no branch in the loop body)
-            const int jn = min(j + 1, jB);
-#if GM_BDIAG == 1
-            const bool okn = true;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { xn[s] = xf[0][s] + 1.0f; zn[s] = zf[s] + 1.0f; }
-#else
-            const bool okn = xtile(jn + a0 + C - 1, xn);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) zn[s] = zp[16 * jn + s * g.pitch];
-#endif
-#if GM_BSCHED
-            __builtin_amdgcn_sched_barrier(0);  // hipcc otherwise sinks the eight reads below the MFMAs, right in front of their wait
-#endif
-#if GM_BDIAG == 2
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int i = 0; i < C; ++i) acc[i][s % NCH][0] += xf[i][s] * zf[s];
-#else
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int i = 0; i < C; ++i)
-                    acc[i][s % NCH] = __builtin_amdgcn_mfma_f32_16x16x4f32(xf[i][s], zf[s], acc[i][s % NCH], 0, 0, 0);
-#endif
-#if GM_BSCHED
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int i = 0; i + 1 < C; ++i) xf[i][s] = xf[i + 1][s];
-                xf[C - 1][s] = okn ? xn[s] : 0.0f;
-                zf[s] = zn[s];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        if constexpr (NCH == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][0][e] += acc[i][1][e];
-        }
-        float* gt = G + (i0 + i) * 16 * GM_GP;  // [i_local = 4 rg + e][j_local = col]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gt[(4 * rg + e) * GM_GP + col] = acc[i][0][e];
-    }
-}
-
+// images; tap t = d + pad is the sum of diagonal d of the G_a that contain it), offsets dealt to the waves round robin.
+// A wave sweeps the column tiles of its offset with the loop shape of gm_conv_tile: two fragment sets used alternately (no
+// register copies), the next pair's eight reads requested ahead of this pair's MFMAs by a scalar two-pair software
+// pipeline, one LDS base per sample-row step (adopted: 186 -> 180 us at 8192 x 360).  Fixed order of the sums: j
+// ascending, k-steps in two chains 0, 2 / 1, 3 added at the end.
 __device__ __forceinline__ void gm_wgrad_tiles(const float* __restrict__ X, const float* __restrict__ Z, float* __restrict__ G,
-                                               const GmGeo g, int ksz, int pad, int run, int lane) {
-    const GmItems it = gm_items(g, ksz, pad);
-    int i0 = __builtin_amdgcn_readfirstlane(run & 0xff);
-    const int last = __builtin_amdgcn_readfirstlane(run >> 8);
-    while (i0 < last) {
-        // a sub-run: <= GM_RUN consecutive offsets of ONE half
-        const int h_end = i0 >= it.n_off ? it.n_items : it.n_off;
-        const int c = min(GM_RUN, min(last, h_end) - i0);
-        if (GM_RUN >= 4 && c >= 4) gm_wgrad_run<4>(X, Z, G, g, it, i0, lane);
-        else if (GM_RUN >= 3 && c == 3) gm_wgrad_run<3>(X, Z, G, g, it, i0, lane);
-        else if (c == 2) gm_wgrad_run<2>(X, Z, G, g, it, i0, lane);
-        else gm_wgrad_run<1>(X, Z, G, g, it, i0, lane);
-        i0 += c;
-    }
-}
-
-// GM_BSTEP=0: the round-3 form of the step (one (offset, column tile) pair at a time, offsets dealt to the waves round
-// robin), kept for A/B runs
-__device__ __forceinline__ void gm_wgrad_tiles_v0(const float* __restrict__ X, const float* __restrict__ Z,
-                                                  float* __restrict__ G, const GmGeo g, int ksz, int pad, int wave, int lane) {
-    const int col = lane & 15, rg = lane >> 4;
-    const int a_lo = -((pad + 15) / 16), a_hi = (ksz - 1 - pad + 15) / 16;
-    for (int a = a_lo + wave; a <= a_hi; a += GM_WAVES) {
-        gm_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f}, accb = {0.0f, 0.0f, 0.0f, 0.0f};  // two chains (see gm_conv_tile)
-        const int j_lo = max(0, -a), j_hi = min(g.nt - 1, g.nt - 1 - a);
-        // A[i_local][n] = X[n][16 (jt + a) + i_local], B[n][j_local] = Z[n][16 jt + j_local]; sample row n of k-step s,
-        // k-slot kq: gm_brow(kq) + s
-        const float* ap = X + gm_brow(rg) * g.pitch + 16 * a + col;
-        const float* bp = Z + gm_brow(rg) * g.pitch + col;
-        float fa[4], fb[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            fa[s] = ap[16 * j_lo + s * g.pitch];
-            fb[s] = bp[16 * j_lo + s * g.pitch];
-        }
-        for (int jt = j_lo; jt < j_hi; ++jt) {
-            float na[4], nb[4];
-#if GM_BDIAG == 1
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { na[s] = fa[s] + 1.0f; nb[s] = fb[s] + 1.0f; }
-#else
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                na[s] = ap[16 * (jt + 1) + s * g.pitch];
-                nb[s] = bp[16 * (jt + 1) + s * g.pitch];
-            }
-#endif
-#if GM_BDIAG == 2
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc[s] += fa[s] * fb[s];
-#else
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-            accb = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], accb, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-            accb = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], accb, 0, 0, 0);
-#endif
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                fa[s] = na[s];
-                fb[s] = nb[s];
-            }
-        }
-        if (j_lo <= j_hi) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-            accb = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], accb, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-            accb = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], accb, 0, 0, 0);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += accb[e];
-        float* gt = G + (a - a_lo) * 16 * GM_GP;  // [i_local = 4 rg + e][j_local = col]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gt[(4 * rg + e) * GM_GP + col] = acc[e];
-    }
-}
-
-#ifndef GM_V2_SCHED
-#define GM_V2_SCHED 1  // the order fetch / mac / fetch / mac pinned (hipcc otherwise merges both fetches behind the first MFMAs
-#endif                 // and waits for the second right in front of its use)
-#if GM_V2_SCHED
-#define GM_V2_PIN __builtin_amdgcn_sched_barrier(0);
-#else
-#define GM_V2_PIN
-#endif
-// GM_BSTEP=2: the same products in the same order as gm_wgrad_tiles_v0 (bit-identical), with the loop shape of gm_conv_tile:
-// two fragment sets used alternately (no register copies), the next pair's eight reads requested ahead of this pair's MFMAs
-// by a scalar two-pair software pipeline, one LDS base per sample-row step
-__device__ __forceinline__ void gm_wgrad_tiles_v2(const float* __restrict__ X, const float* __restrict__ Z,
-                                                  float* __restrict__ G, const GmGeo g, int ksz, int pad, int wave, int lane) {
+                                               const GmGeo g, int ksz, int pad, int wave, int lane) {
     const int col = lane & 15, rg = lane >> 4;
     const int a_lo = -((pad + 15) / 16), a_hi = (ksz - 1 - pad + 15) / 16;
     const float* xb = X + gm_brow(rg) * g.pitch + col;
@@ -789,6 +452,7 @@ __device__ __forceinline__ void gm_wgrad_tiles_v2(const float* __restrict__ X, c
         const int j_lo = max(0, -a), j_hi = min(g.nt - 1, g.nt - 1 - a);
         const int nch = j_hi - j_lo + 1;
         if (nch > 0) {
+            // A[i_local][n] = X[n][16 (jt + a) + i_local], B[n][j_local] = Z[n][16 jt + j_local]
             const float* ap = xb + 16 * (a + j_lo);
             const float* bp = zb + 16 * j_lo;
             float a0[4], b0[4], a1[4], b1[4];
@@ -805,17 +469,19 @@ __device__ __forceinline__ void gm_wgrad_tiles_v2(const float* __restrict__ X, c
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
                 accb = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], accb, 0, 0, 0);
             };
+            // the order fetch / mac / fetch / mac pinned: hipcc otherwise merges both fetches behind the first MFMAs and
+            // waits for the second right in front of its use
             fetch(0, a0, b0);
             int c = 0;
             for (; c + 2 < nch; c += 2) {
                 fetch(c + 1, a1, b1);
-                GM_V2_PIN
+                __builtin_amdgcn_sched_barrier(0);
                 mac(a0, b0);
-                GM_V2_PIN
+                __builtin_amdgcn_sched_barrier(0);
                 fetch(c + 2, a0, b0);
-                GM_V2_PIN
+                __builtin_amdgcn_sched_barrier(0);
                 mac(a1, b1);
-                GM_V2_PIN
+                __builtin_amdgcn_sched_barrier(0);
             }
             if (c + 1 < nch) {  // two pairs left
                 fetch(c + 1, a1, b1);
@@ -833,47 +499,42 @@ __device__ __forceinline__ void gm_wgrad_tiles_v2(const float* __restrict__ X, c
     }
 }
 
-// tap `tap` of the layer: the sum of diagonal d = tap - pad of G, halves ascending, tiles ascending, rows ascending
-__device__ __forceinline__ float gm_diag_sum(const float* __restrict__ G, const GmGeo g, int ksz, int pad, int tap) {
-    const GmItems it = gm_items(g, ksz, pad);
-    const int a_hi = it.a_lo + it.n_off - 1;
+// tap `tap` of the layer: the sum of diagonal d = tap - pad of G, tiles ascending, rows ascending
+__device__ __forceinline__ float gm_diag_sum(const float* __restrict__ G, int ksz, int pad, int tap) {
+    const int a_lo = -((pad + 15) / 16), a_hi = (ksz - 1 - pad + 15) / 16;
     const int d = tap - pad;
     const int a0 = (d + 15 >= 0 ? (d + 15) / 16 : -((-(d + 15) + 15) / 16));  // floor((d + 15) / 16)
-    float total = 0.0f;
-#pragma unroll 1
-    for (int h = 0; h < it.halves; ++h) {
-        // Diagonal d crosses the tiles a0 - 1 (rows dl0 .. 15, dl0 = d - 16 (a0 - 1) in [1, 16]) and a0 (rows 0 .. dl0 - 1):
-        // 16 elements, row il from tile a0 when il < dl0.  All 16 are fetched before the first add (as nested loops with
-        // data-dependent bounds this was <= 32 dependent LDS round trips per thread and layer); an element of an absent
-        // tile is read from G's first tile and replaced by 0 (volatile: hipcc otherwise sinks every load under its
-        // predicate -- a branch and an LDS round trip each).
-        const int dl0 = d - 16 * (a0 - 1);
-        const bool ok0 = a0 - 1 >= it.a_lo && a0 - 1 <= a_hi, ok1 = a0 >= it.a_lo && a0 <= a_hi;
-        // element il of tile t sits at gt_t[il * (GM_GP + 1) - dl_t]
-        const float* b0 = G + (ok0 ? h * it.n_off + a0 - 1 - it.a_lo : 0) * 16 * GM_GP - (ok0 ? dl0 : 0);
-        const float* b1 = G + (ok1 ? h * it.n_off + a0 - it.a_lo : 0) * 16 * GM_GP - (ok1 ? dl0 - 16 : 0);
-        typedef const volatile __attribute__((address_space(3))) float* gm_lds_vptr;
-        // (two loops: with the select next to its load hipcc waited for every load before it issued the next one -- 16
-        // serial LDS round trips, 1.8 k cycles per layer whatever the band count)
-        float v[16];
+    // Diagonal d crosses the tiles a0 - 1 (rows dl0 .. 15, dl0 = d - 16 (a0 - 1) in [1, 16]) and a0 (rows 0 .. dl0 - 1):
+    // 16 elements, row il from tile a0 when il < dl0.  All 16 are fetched before the first add (as nested loops with
+    // data-dependent bounds this was <= 32 dependent LDS round trips per thread and layer); an element of an absent
+    // tile is read from G's first tile and replaced by 0 (volatile: hipcc otherwise sinks every load under its
+    // predicate -- a branch and an LDS round trip each).
+    const int dl0 = d - 16 * (a0 - 1);
+    const bool ok0 = a0 - 1 >= a_lo && a0 - 1 <= a_hi, ok1 = a0 >= a_lo && a0 <= a_hi;
+    // element il of tile t sits at gt_t[il * (GM_GP + 1) - dl_t]
+    const float* b0 = G + (ok0 ? a0 - 1 - a_lo : 0) * 16 * GM_GP - (ok0 ? dl0 : 0);
+    const float* b1 = G + (ok1 ? a0 - a_lo : 0) * 16 * GM_GP - (ok1 ? dl0 - 16 : 0);
+    typedef const volatile __attribute__((address_space(3))) float* gm_lds_vptr;
+    // (two loops: with the select next to its load hipcc waited for every load before it issued the next one -- 16
+    // serial LDS round trips, 1.8 k cycles per layer whatever the band count)
+    float v[16];
 #pragma unroll
-        for (int il = 0; il < 16; ++il) v[il] = ((gm_lds_vptr)(il < dl0 ? b1 : b0))[il * (GM_GP + 1)];
-        float s = 0.0f;
+    for (int il = 0; il < 16; ++il) v[il] = ((gm_lds_vptr)(il < dl0 ? b1 : b0))[il * (GM_GP + 1)];
+    float s = 0.0f;
 #pragma unroll
-        for (int il = 0; il < 16; ++il) s += ((il < dl0 ? ok1 : ok0) ? v[il] : 0.0f);  // rows ascending
-        total = h == 0 ? s : total + s;
-    }
-    return total;
+    for (int il = 0; il < 16; ++il) s += ((il < dl0 ? ok1 : ok0) ? v[il] : 0.0f);  // rows ascending
+    return s;
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
-// pw[blocks][sum k], pb[blocks][8]: this block's partial filter / bias gradients (summed over its row tiles).
-template <bool ENC, bool STASH, bool TAP = false>
+// pw[blocks][sum k], pb[blocks][8]: this block's partial filter / bias gradients (summed over its row tiles).  Without kept
+// activations: the forward pass is recomputed per row tile (from kept ones, gan_generator_bwd2_mfma_kernel below runs).
+template <bool ENC, bool TAP = false>
 __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
     const float* __restrict__ x, int64_t ldx, const float* __restrict__ dout, int64_t lddo, int64_t n, int bands,
     const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ dx, int64_t lddx, int accumulate_dx,
-    float* __restrict__ pw, float* __restrict__ pb, int wtotal, int slabs, const float* __restrict__ stash,
-    const float* __restrict__ d_enc, int64_t ld_denc, GmApps apps) {
+    float* __restrict__ pw, float* __restrict__ pb, int wtotal, int slabs, const float* __restrict__ d_enc, int64_t ld_denc,
+    GmApps apps) {
     constexpr int L = ENC ? 4 : 7;
     extern __shared__ __attribute__((aligned(16))) float gm_lds[];
     const GmGeo g = gm_geo(bands);
@@ -894,11 +555,9 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
     float* wz2 = wz + 3 * g.bp;    // second tap table of the forward recompute
     float* G = wz2 + 3 * g.bp;     // [a][16][GM_GP]
     float* red = G + gm_atiles(bands) * 16 * GM_GP;  // [GM_WAVES] bias-gradient partials, [GM_WAVES + l] their sums
-    int* sched = reinterpret_cast<int*>(red + 64);    // [L][GM_WAVES] filter-gradient runs (gm_wgrad_schedule)
-    float* raw = red + 128;                           // LDS copy of every layer's taps + biases
+    float* raw = red + 128;                           // LDS copy of every layer's taps + biases (red + 64 ..: unused)
     gm_zero(gm_lds, 5 * img + 6 * g.bp, tid);
     gm_stage_raw(raw, bands, w, bias, tid);
-    if (GM_BSTEP == 1) gm_wgrad_schedule(sched, g, L, tid);
     __syncthreads();
 
     float dwacc[7];  // thread t owns tap t of every layer; red[GM_WAVES + l] collects the bias gradients
@@ -906,67 +565,23 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
     for (int l = 0; l < 7; ++l) dwacc[l] = 0.0f;
     if (tid < 7) red[GM_WAVES + tid] = 0.0f;
 
-#if GM_DIAG == 5
-    long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tmark = clock64();
-#define GM_MARK(i) { const long long now_ = clock64(); dbg[i] += now_ - tmark; tmark = now_; }
-#else
-#define GM_MARK(i)
-#endif
     const int64_t tiles = (n + GM_ROWS - 1) / GM_ROWS;
     for (int64_t t = blk; t < tiles; t += bpa) {
         const int64_t r0 = t * GM_ROWS;
         const int rows_valid = (int)min((int64_t)GM_ROWS, n - r0);
-        GM_MARK(0)
         float keep[6][GM_MAXT][4];
         unsigned mask[7];
-        [[maybe_unused]] float ylast[GM_MAXT][4];  // STASH: the tanh output of this lane's elements
-        int res = 0;
-        if constexpr (STASH) {  // the forward pass left its activations behind (see GmKeep)
-            const gm_f32x4* sp =
-                reinterpret_cast<const gm_f32x4*>(stash) + (size_t)(app * tiles + t) * GmKeep<ENC>::V4 * GM_THREADS + tid;
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int m = 0; m < GM_MAXT; ++m) {
-                    gm_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (q < (ENC ? 3 : 6) && wave + GM_WAVES * m < g.nt) v = sp[(q * GM_MAXT + m) * GM_THREADS];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) keep[q][m][e] = v[e];
-                }
-            if constexpr (!ENC) {
-#pragma unroll
-                for (int m = 0; m < GM_MAXT; ++m) {
-                    gm_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (wave + GM_WAVES * m < g.nt) v = sp[(6 * GM_MAXT + m) * GM_THREADS];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ylast[m][e] = v[e];
-                }
-            }
-            typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
-            const gm_u32x4* mp = reinterpret_cast<const gm_u32x4*>(sp + GmKeep<ENC>::SLOTS * GM_MAXT * GM_THREADS);
-            const gm_u32x4 m0 = mp[0];
-            mask[0] = m0[0]; mask[1] = m0[1]; mask[2] = m0[2]; mask[3] = m0[3];
-            mask[4] = mask[5] = mask[6] = 0u;
-            if constexpr (!ENC) {
-                const gm_u32x4 m1 = mp[GM_THREADS];
-                mask[4] = m1[0]; mask[5] = m1[1];
-            }
-        } else {
-            gm_load_rows(bufs[0], g, x + r0 * ldx, ldx, rows_valid, tid);
-            res = gm_forward<ENC, true>(gm_lds, wz, wz2, g, raw, raw + gm_woff(bands, 7), nullptr, 0, rows_valid, tid, keep,
-                                        mask);
-        }
+        gm_load_rows(bufs[0], g, x + r0 * ldx, ldx, rows_valid, tid);
+        const int res = gm_forward<ENC, true>(gm_lds, wz, wz2, g, raw, raw + gm_woff(bands, 7), nullptr, 0, rows_valid, tid,
+                                              keep, mask);
         __syncthreads();
         // gradient ring: Da = dn_l (complete), Db = partial dn_{l-1}, Dc = dn_{l-2} being initialised
         float* Da = bufs[(res + 1) % 3];
         float* Db = bufs[(res + 2) % 3];
         float* Dc = bufs[res];  // still holds the forward result until the top layer has read it
         const float* fwd_out = bufs[res];
-        GM_MARK(1)  // forward recompute
         gm_load_rows(Da, g, dout + r0 * lddo, lddo, rows_valid, tid);
         __syncthreads();
-        GM_MARK(2)  // dout load
         int woff = gm_woff(bands, L);
         // One rolled loop over the layers (the kept activations / branch bits of layer l are picked by wave-uniform
         // selects): unrolled, the seven bodies needed > 200 scalar and > 200 vector spill slots.
@@ -1008,9 +623,7 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
                         const float gd = Da[o];
                         float f;
                         if (top_tanh) {
-                            float y;
-                            if constexpr (STASH) y = ylast[m][e];
-                            else y = fwd_out[o];
+                            const float y = fwd_out[o];
                             f = 1.0f - y * y;
                         } else {
                             f = ((mk >> (4 * m + e)) & 1u) ? 1.0f : 0.1f;
@@ -1040,27 +653,15 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
                 for (int wv = 0; wv < GM_WAVES; ++wv) s += red[wv];
                 red[GM_WAVES + l] += s;
             }
-            GM_MARK(3)  // step A
-            // ---- step B: filter gradient (gm_wgrad_tiles: balanced runs of consecutive tile offsets) ----
-#if GM_BSTEP == 1
-            gm_wgrad_tiles(X, Z, G, g, ksz, pad, sched[l * GM_WAVES + wave], lane);
-#elif GM_BSTEP == 2
-            gm_wgrad_tiles_v2(X, Z, G, g, ksz, pad, wave, lane);
-#else
-            gm_wgrad_tiles_v0(X, Z, G, g, ksz, pad, wave, lane);
-#endif
+            // ---- step B: filter gradient ----
+            gm_wgrad_tiles(X, Z, G, g, ksz, pad, wave, lane);
             __syncthreads();
-            GM_MARK(4)  // step B products
-#ifndef GM_NO_DIAGSUM
-#define GM_NO_DIAGSUM 0
-#endif
-            if (!GM_NO_DIAGSUM && tid < ksz) {  // thread t owns tap t
-                const float s = gm_diag_sum(G, g, ksz, pad, tid);
+            if (tid < ksz) {  // thread t owns tap t
+                const float s = gm_diag_sum(G, ksz, pad, tid);
 #pragma unroll
                 for (int q = 0; q < 7; ++q)
                     if (q == l) dwacc[q] += s;
             }
-            GM_MARK(5)  // diagonal sums
             // ---- step C: data gradient dn_{l-1} += dz_l . T^T ----
             if (l > 0 || dx != nullptr) {
 #pragma unroll
@@ -1076,7 +677,6 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
                 }
             }
             __syncthreads();
-            GM_MARK(6)  // step C
             float* old = Da;
             Da = Db;
             Db = Dc;
@@ -1111,35 +711,18 @@ __global__ __launch_bounds__(GM_THREADS) void gan_generator_bwd_mfma_kernel(
         woff += ksz;
     }
     if (tid < 8) pb[(size_t)slab * 8 + tid] = tid < L ? red[GM_WAVES + tid] : 0.0f;
-#if GM_DIAG == 5
-    GM_MARK(7)
-    if (tid == 0 && blockIdx.x == 0)
-        for (int i = 0; i < 8; ++i) pb[i] = (float)dbg[i];
-#endif
 }
 
 // Block barrier of the register-ring backward kernel's layer loop: every wave's LDS accesses are complete, its global
 // loads (the next layer's kept activations, taps and branch bits, requested a layer ahead) stay in flight --
 // __syncthreads() waits for vmcnt(0) too, which put one exposed HBM round trip into every layer.
-#ifndef GM_LDS_BARRIER
-#define GM_LDS_BARRIER 1
-#endif
-#ifndef GM_KEEP_B128
-#define GM_KEEP_B128 1  // 16-byte loads of the kept activations (0: four dword buffer loads; 3 % slower)
-#endif
-__device__ __forceinline__ void gm_lds_barrier() {
-#if GM_LDS_BARRIER
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-    __syncthreads();
-#endif
-}
+__device__ __forceinline__ void gm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- backward from kept activations, two resident blocks per CU (round 4) -----------------------------------------------
-// The round-3 kernel above keeps five [16 x B] images (three of them the gradient ring dn_l / dn_{l-1} / dn_{l-2}), two tap
-// tables and every layer's taps in LDS: 161 KB at 360 bands, ONE block per CU, and its per-layer bookkeeping (step A: 12
-// elements per lane, each an LDS read-modify-write chain inside a divergent branch; the sub-run set-up of step B; the
-// diagonal sums) is ~60 % of its cycles with the matrix pipe idle (phase stamps, NOTES 4.J).  This kernel serves the form
+// The LDS-ring kernel above keeps five [16 x B] images (three of them the gradient ring dn_l / dn_{l-1} / dn_{l-2}), two
+// tap tables and every layer's taps in LDS: 161 KB at 360 bands, ONE block per CU, and its per-layer bookkeeping (step A:
+// 12 elements per lane, each an LDS read-modify-write chain inside a divergent branch; the diagonal sums) is ~60 % of its
+// cycles with the matrix pipe idle (phase stamps, NOTES 4.J).  This kernel serves the form
 // the train ops run (activations kept by the forward pass) with the ring in REGISTERS: a lane owns the same 12 elements
 // (MFMA C layout) in every layer -- step A reads dn_l from registers, step C adds the data-gradient tile to registers --
 // and of the kept activations only the layer at hand is resident (12 floats, requested one layer ahead, like the taps and
@@ -1174,9 +757,7 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     float* wz = gm_lds + 2 * img;
     float* G = wz + 3 * g.bp;  // [item][16][GM_GP]
     float* red = G + gm_atiles(bands) * 16 * GM_GP;  // [GM_WAVES] bias-gradient partials, [GM_WAVES + l] their sums
-    int* sched = reinterpret_cast<int*>(red + 64);   // [L][GM_WAVES] filter-gradient runs
     gm_zero(gm_lds, 2 * img + 3 * g.bp, tid);  // image padding and tap margins stay zero
-    if (GM_BSTEP == 1) gm_wgrad_schedule(sched, g, L, tid);
     if (tid < 7) red[GM_WAVES + tid] = 0.0f;
     __syncthreads();
 
@@ -1185,16 +766,8 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     for (int l = 0; l < 7; ++l) dwacc[l] = 0.0f;
     const int64_t tiles = (n + GM_ROWS - 1) / GM_ROWS;
     constexpr int kOOB = 0x7fffffff;
-#if GM_DIAG == 5
-    long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tmark = clock64();
-#endif
-#if GM_DIAG == 6  // occupancy timeline: every block reports its start / end (100 MHz wall clock) and where it ran
-    const long long wall0 = wall_clock64();
-#endif
     for (int64_t t = blk; t < tiles; t += bpa) {
         const int64_t r0 = t * GM_ROWS;
-        GM_MARK(0)
         const int rows_valid = (int)min((int64_t)GM_ROWS, n - r0);
         // (opaque copies: hipcc otherwise hoists the ~50 element addresses of the tile and layer loops out of them and
         // spills them)
@@ -1217,9 +790,8 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             (void*)(stash + (size_t)(app * tiles + t) * GmKeep<ENC>::V4 * GM_THREADS * 4), 0,
             GmKeep<ENC>::V4 * GM_THREADS * 16, 0x00020000);
         auto load_slot = [&](int q, float (&v)[GM_MAXT][4]) {  // tiles beyond nt hold nothing
-#if GM_KEEP_B128
-            // one 16-byte load per column tile: scalar base + a 32-bit lane offset (a dwordx4 RAW BUFFER load under the
-            // dword descriptor returned only its first component)
+            // one 16-byte load per column tile: scalar base + a 32-bit lane offset (four dword buffer loads measured 3 %
+            // slower; a dwordx4 RAW BUFFER load under the dword descriptor returned only its first component)
             const char* kb = reinterpret_cast<const char*>(stash) +
                              ((size_t)(app * tiles + t) * GmKeep<ENC>::V4 + (size_t)q * GM_MAXT) * GM_THREADS * 16;
 #pragma unroll
@@ -1230,17 +802,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[m][e] = f[e];
             }
-#else
-            // (dword loads: a dwordx4 raw buffer load under this dword descriptor returned only its first component)
-            const int so = __builtin_amdgcn_readfirstlane(q * GM_MAXT * GM_THREADS * 16);
-#pragma unroll
-            for (int m = 0; m < GM_MAXT; ++m) {
-                const int vo = wave + GM_WAVES * m < g.nt ? tidt * 16 + m * GM_THREADS * 16 : kOOB;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    v[m][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(keep_rsrc, vo + 4 * e, so, 0));
-            }
-#endif
         };
         auto load_mask = [&](int l) {  // branch bits of layer l: word l of the two uint4 behind the slots
             return (unsigned)__builtin_amdgcn_raw_buffer_load_b32(
@@ -1266,7 +827,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             if (tid < k0) wreg = w[woff - k0 + tid];
         }
         unsigned mk = ENC ? load_mask(3) : 0u;  // branch bits of the layer at hand (the tanh layer has none)
-        GM_MARK(2)  // tile set-up: dout and the top layer's operands requested
 #pragma unroll 1
         for (int l = L - 1; l >= 0; --l) {
             const int ksz = gm_ksz(bands, l), pad = (ksz - 1) / 2;
@@ -1323,14 +883,10 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
                     for (int e = 0; e < 4; ++e) X[lbase + e * g.pitch + 16 * GM_WAVES * m] = xin[m][e];
                 }
             }
-            GM_MARK(1)  // (diagnostics) step A up to the element loop's end
             if (l == 0) gm_load_rows(X, g, x + r0 * ldx, ldx, rows_valid, tid);
             // next layer's operands: its input n_{l-2}, its taps, its branch bits
-#ifndef GM_ADIAG
-#define GM_ADIAG 0  // timing diagnostics (results garbage): 1 = no requests for the next layer's operands
-#endif
-            if (!GM_ADIAG && l >= 2) load_slot(l - 2, xin);
-            if (!GM_ADIAG && l >= 1) {
+            if (l >= 2) load_slot(l - 2, xin);
+            if (l >= 1) {
                 const int k1 = gm_ksz(bands, l - 1);
                 wreg = tid < k1 ? w[woff - k1 + tid] : 0.0f;
                 mk = load_mask(l - 1);
@@ -1345,7 +901,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
                 for (int wv = 0; wv < GM_WAVES; ++wv) s += red[wv];
                 red[GM_WAVES + l] += s;
             }
-            GM_MARK(3)  // step A
             // ---- step C: data gradient dn_{l-1} += dz_l . T^T (this wave's column tiles, into its registers) ----
             // Steps C and B only READ dz_l / n_{l-1} / the tap table and are independent of each other: no barrier between
             // them (a wave's MFMA-dense data-gradient tiles run beside other waves' latency-bound filter-gradient items);
@@ -1363,25 +918,15 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
                     }
                 }
             }
-            GM_MARK(6)  // step C
             // ---- step B: filter gradient ----
-#if GM_BSTEP == 1
-            gm_wgrad_tiles(X, Z, G, g, ksz, pad, sched[l * GM_WAVES + wave], lane_l);
-#elif GM_BSTEP == 2
-            gm_wgrad_tiles_v2(X, Z, G, g, ksz, pad, wave, lane_l);
-#else
-            gm_wgrad_tiles_v0(X, Z, G, g, ksz, pad, wave, lane_l);
-#endif
-            GM_MARK(7)  // (diagnostics) step B: wave 0's own products
+            gm_wgrad_tiles(X, Z, G, g, ksz, pad, wave, lane_l);
             gm_lds_barrier();  // every wave has left Z / X / wz; G is complete
-            GM_MARK(4)  // step B products
             if (tid_l < ksz) {
-                const float s = gm_diag_sum(G, g, ksz, pad, tid_l);
+                const float s = gm_diag_sum(G, ksz, pad, tid_l);
 #pragma unroll
                 for (int q = 0; q < 7; ++q)
                     if (q == l) dwacc[q] += s;
             }
-            GM_MARK(5)  // diagonal sums
         }
         if (dx != nullptr) {
             const __amdgpu_buffer_rsrc_t rs = tile_rsrc(dx, lddx);
@@ -1413,21 +958,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
         woff += ksz;
     }
     if (tid < 8) pb[(size_t)slab * 8 + tid] = tid < L ? red[GM_WAVES + tid] : 0.0f;
-#if GM_DIAG == 5
-    GM_MARK(7)
-    if (tid == 0 && blockIdx.x == 0)
-        for (int i = 0; i < 8; ++i) pb[i] = (float)dbg[i];
-#endif
-#if GM_DIAG == 6
-    __syncthreads();
-    if (tid == 0) {
-        int* o = reinterpret_cast<int*>(pb + (size_t)slab * 8);
-        o[0] = (int)(unsigned)wall0;
-        o[1] = (int)(unsigned)wall_clock64();
-        o[2] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-        o[3] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    }
-#endif
 }
 
 }  // namespace
@@ -1485,9 +1015,7 @@ int hypel_gm_bwd(const float* x, int64_t ldx, const float* dout, int64_t lddo, i
     // every one of the `blocks` partial slabs is written (the planner's reduce sums all of them)
     const int64_t tiles = (n + GM_ROWS - 1) / GM_ROWS;
     const int grid = n_apps > 1 ? blocks : (int)(tiles < blocks ? tiles : blocks);
-    // from kept activations: the register-ring kernel (two resident blocks per CU); HYPEL_GAN_BWD2=0 = the round-3 kernel
-    static const int use_bwd2 = getenv("HYPEL_GAN_BWD2") ? atoi(getenv("HYPEL_GAN_BWD2")) : 1;
-    if (keep && use_bwd2) {
+    if (keep) {  // from kept activations: the register-ring kernel (two resident blocks per CU)
         const size_t lds2 = gm_bwd2_lds(bands);
 #define GM_BWD2(K)                                                                                                     \
     do {                                                                                                               \
@@ -1501,17 +1029,10 @@ int hypel_gm_bwd(const float* x, int64_t ldx, const float* dout, int64_t lddo, i
 #undef GM_BWD2
         return 0;
     }
-#define GM_BWD_ARGS x, ldx, dout, lddo, n, bands, w, b, dx, lddx, accumulate_dx, pw, pb, wtotal, blocks, keep, d_enc, ld_denc, apps
-    if (only_encoder) {
-        if (keep) GM_LAUNCH((gan_generator_bwd_mfma_kernel<true, true>), GM_BWD_ARGS);
-        else GM_LAUNCH((gan_generator_bwd_mfma_kernel<true, false>), GM_BWD_ARGS);
-    } else if (d_enc) {
-        if (keep) GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, true, true>), GM_BWD_ARGS);
-        else GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, false, true>), GM_BWD_ARGS);
-    } else {
-        if (keep) GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, true>), GM_BWD_ARGS);
-        else GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, false>), GM_BWD_ARGS);
-    }
+#define GM_BWD_ARGS x, ldx, dout, lddo, n, bands, w, b, dx, lddx, accumulate_dx, pw, pb, wtotal, blocks, d_enc, ld_denc, apps
+    if (only_encoder) GM_LAUNCH((gan_generator_bwd_mfma_kernel<true, false>), GM_BWD_ARGS);
+    else if (d_enc) GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, true>), GM_BWD_ARGS);
+    else GM_LAUNCH((gan_generator_bwd_mfma_kernel<false, false>), GM_BWD_ARGS);
 #undef GM_BWD_ARGS
     return 0;
 }

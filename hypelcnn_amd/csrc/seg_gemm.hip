@@ -68,50 +68,18 @@ __device__ __forceinline__ void hypel_for_range(F&& f, std::integer_sequence<int
     (f(std::integral_constant<int, LO + Is>{}), ...);
 }
 
-#ifndef HYPEL_GEMM_BK
-#define HYPEL_GEMM_BK 32  // reduction columns per LDS tile (a multiple of 16)
-#endif
-constexpr int BK_WIDE = HYPEL_GEMM_BK;
-#ifndef HYPEL_GEMM_BK_NARROW
-#define HYPEL_GEMM_BK_NARROW 32  // reduction columns per LDS tile of the 128x16 variant (experiments: 64)
-#endif
-constexpr int BK_NARROW = HYPEL_GEMM_BK_NARROW;
+constexpr int BK = 32;  // reduction columns per LDS tile, every variant (BK = 64 for the 128x16 one measured neutral)
 #ifndef HYPEL_GEMM_CLK
 #define HYPEL_GEMM_CLK 0  // tools/gemm_quantisation.py: 1 = --clk (shader clock the kernel ran at), 2 = --timeline
 #endif
-#ifndef HYPEL_GEMM_CHUNK
-#define HYPEL_GEMM_CHUNK 8  // granularity (reduction columns) at which a short k-tile stops issuing MFMAs
-#endif
-#ifndef HYPEL_GEMM_RD64
-#define HYPEL_GEMM_RD64 51  // operand fragments of two consecutive MFMA k-steps from ONE ds_read_b64 (see RD64 below); bits:
-                           // 1 = A B products, 2 = A B^T, 4 = A^T B, 8 = A^T B^T; 16 = also the 128x32 variants;
-                           // 32 = k-contiguous operands are transposed into the pair-interleaved image as well
-#endif
-#ifndef HYPEL_GEMM_BATCHED_EPILOGUE
-#define HYPEL_GEMM_BATCHED_EPILOGUE 2  // 1: read-modify-write epilogues of full tiles issue all loads before the stores;
-                                       // 2: every full tile's epilogue on raw buffer accesses (one offset + scalar row step)
-#endif
-#ifndef HYPEL_GEMM_HOIST_EPI
-#define HYPEL_GEMM_HOIST_EPI 1  // bias / shortcut column ranges requested before the k loop
-#endif
-constexpr int CHUNK = HYPEL_GEMM_CHUNK;
-static_assert(CHUNK % 4 == 0 && BK_WIDE % CHUNK == 0 && BK_NARROW % CHUNK == 0, "chunk of k2 / k4 steps");
-#ifndef HYPEL_SPLIT_WAVE_ROWS_FIRST
-#define HYPEL_SPLIT_WAVE_ROWS_FIRST 1  // split variants: wave -> (wave % WM, wave / WM) instead of (wave / WN, wave % WN)
-#endif
-#ifndef HYPEL_OCC_BN32
-#define HYPEL_OCC_BN32 3  // waves per SIMD the 128x32 variant is compiled for
-#endif
-#ifndef HYPEL_OCC_BN64_TA
-#define HYPEL_OCC_BN64_TA 3  // waves per SIMD the 128x64 filter-gradient (A transposed) variants are compiled for
-#endif
-#ifndef HYPEL_OCC_BN32_TA
-#define HYPEL_OCC_BN32_TA 3  // ... the 128x32 filter-gradient variants
-#endif
-#ifndef HYPEL_OCC_BN96
-#define HYPEL_OCC_BN96 5  // ... and the 128x96 data-gradient variant (5 blocks per CU = 1280 resident: 392 x 3 row x column
-                          // tiles fit); the forward variant needs ~104 registers: 4 waves per SIMD, 1024 resident
-#endif
+constexpr int CHUNK = 8;  // granularity (reduction columns) at which a short k-tile stops issuing MFMAs
+static_assert(CHUNK % 4 == 0 && BK % CHUNK == 0, "chunk of k2 / k4 steps");
+// waves per SIMD the variants are compiled for (HYPEL_GEMM_BOUNDS)
+constexpr int OCC_BN32 = 3;     // 128x32
+constexpr int OCC_BN64_TA = 3;  // 128x64 filter-gradient (A transposed) variants
+constexpr int OCC_BN32_TA = 3;  // 128x32 filter-gradient variants
+constexpr int OCC_BN96 = 5;     // 128x96 data-gradient variant (5 blocks per CU = 1280 resident: 392 x 3 row x column tiles
+                                // fit); the forward variant needs ~104 registers: 4 waves per SIMD, 1024 resident
 
 // NARROW: 128x16 blocks on v_mfma_f32_16x16x4_f32 for n <= 16 (the Cout = 15 level of HYPELCNN, fc_final): each wave
 // owns 32 rows x 16 columns as two 16x16 accumulators, so a 15-column output wastes 1/16 of the MFMA work instead of
@@ -166,7 +134,6 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
     static_assert(!NARROW || (WM == 4 && TM == 1 && (TN == 1 || (TN == 4 && !TA && !TB && !MULTI))),
                   "narrow variant: 4 x 1 waves of 32 x 16 (forward: 32 x 64)");
     // LDS images (rows x pitch), global row order preserved
-    constexpr int BK = NARROW ? BK_NARROW : BK_WIDE;
     constexpr int A_ROWS = TA ? BK : BM;
     constexpr int A_COLS = TA ? BM : BK;
     // pitches: a fragment read must hit 32 distinct banks per half-wave.  32x32x2 fragments read 32 rows at one k
@@ -179,13 +146,13 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
     // [n][k]) keep their natural order with an even pitch of BK + 2 = 34 floats (32 rows x 8 bytes then cover the 64
     // banks exactly once; the 2-way conflict of the staging stores is hidden under their register transfer); the
     // k-strided images ([k][m], [k][n]) interleave the rows of a column pair: (k, x) -> ((k >> 1) * W + x) * 2 + (k & 1).
-    // The order of the products inside a k-tile changes (0,2,1,3,4,6,...), the result stays one fixed fmaf chain.
-    constexpr bool RD64 = !NARROW && ((HYPEL_GEMM_RD64 >> ((TA ? 2 : 0) + (TB ? 1 : 0))) & 1) &&
-                          (TM * TN > 1 || (HYPEL_GEMM_RD64 & 16));
+    // The order of the products inside a k-tile changes (0,2,1,3,4,6,...), the result stays one fixed fmaf chain.  On for
+    // every product with A untransposed (A B, A B^T) outside the 128x16 variant.
+    constexpr bool RD64 = !NARROW && !TA;
     // LIN: a k-contiguous operand is transposed on its way into LDS, into the same pair-interleaved image the
     // k-strided operands use -- (x, k) -> (k >> 1) * PP + 2 x + (k & 1), pair pitch PP = 2 W + 2 (the 32 lanes that
     // store one row's 32 columns then hit 32 banks) -- so that its fragment reads are 32 consecutive 8-byte words too
-    constexpr bool LIN = RD64 && (HYPEL_GEMM_RD64 & 32);
+    constexpr bool LIN = RD64;
     constexpr int PPA = 2 * BM + 2, PPB = 2 * BN + 2;
     constexpr int A_PITCH = TA ? (NARROW ? BM + 16 : BM) : (NARROW || RD64 ? BK + 2 : BK + 1);
     constexpr int B_ROWS = TB ? BN : BK;
@@ -265,8 +232,8 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
     // SPLIT: consecutive waves (= the four SIMDs of a CU) take different ROW slabs of the same column tiles first, so that a
     // group that fills only the first column tile(s) of the block (the outer rings of a merged multi-kernel level:
     // hypel_tile_t.n = 30 of 120 columns) still has MFMA work on every SIMD; the fp32 kernels keep the column-major deal
-    const int wm = SPLIT && HYPEL_SPLIT_WAVE_ROWS_FIRST ? wave % WM : wave / WN;
-    const int wn = SPLIT && HYPEL_SPLIT_WAVE_ROWS_FIRST ? wave / WM : wave % WN;
+    const int wm = SPLIT ? wave % WM : wave / WN;
+    const int wn = SPLIT ? wave / WM : wave % WN;
     const int l31 = lane & 31, lhi = lane >> 5;
 
     // per-thread staging coordinates
@@ -511,10 +478,10 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
 
     // Epilogue operands that only depend on the block's position -- the shortcut gradient's column ranges and the bias --
     // are requested BEFORE the k loop: at the end of the block they would be one more dependent round trip in front of
-    // the gather passes (HYPEL_GEMM_HOIST_EPI=0: load them in the epilogue).
+    // the gather passes.
     [[maybe_unused]] int h_o0[TN], h_o1[TN];
     [[maybe_unused]] float h_bv[TN];
-    constexpr bool HOIST = HYPEL_GEMM_HOIST_EPI && !NARROW && !TA && TM * TN == 1;  // wider tiles: 6 more live
+    constexpr bool HOIST = !NARROW && !TA && TM * TN == 1;  // wider tiles: 6 more live
     if constexpr (HOIST) {                                                                 // registers cost a wave per SIMD
         const int bias_c0 = bias ? (int)(grp.c_off % ldc) + n0 : 0;
 #pragma unroll
@@ -1064,7 +1031,7 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
                 o0 = res_start[n0 + col];
                 o1 = res_start[n0 + col + 1];
             }
-            if (HYPEL_GEMM_BATCHED_EPILOGUE > 1 && !res && rows_left >= wm * 32 + 32) {
+            if (!res && rows_left >= wm * 32 + 32) {
                 // full 32-row slab: raw buffer accesses, one per-lane offset, rows stepped by a scalar (see below)
                 const int ldc4 = __builtin_amdgcn_readfirstlane((int)ldc * 4);
                 const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc((void*)cbase, 0, 0x7ffffff0, 0x00020000);
@@ -1124,7 +1091,7 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
                     }
                 }
                 const bool full_tile = rows_left >= (wm * TM + i) * 32 + 32;
-                if (HYPEL_GEMM_BATCHED_EPILOGUE && (HYPEL_GEMM_BATCHED_EPILOGUE > 1 || accumulate || res) && full_tile) {
+                if (full_tile) {
                     // Read-modify-write epilogue of a FULL 32-row accumulator tile with every addend IN FLIGHT before the
                     // first store.  As `put` writes it, hipcc must keep each load behind the previous element's store
                     // (they may alias): 16 x (1 + gathered addends) dependent round trips per lane, 15-40 us of a
@@ -1193,8 +1160,8 @@ __device__ __forceinline__ void seg_gemm_body(const float* __restrict__ A, int64
 #define HYPEL_GEMM_ARGS \
     A, lda, B, ldb, C, ldc, n, groups, segs, tiles_v, n_tiles, n_ntiles, bias, accumulate, res, ldr, res_start, stats
 #define HYPEL_GEMM_BOUNDS \
-    __launch_bounds__(256, (TM * TN == 1 ? (TA ? HYPEL_OCC_BN32_TA : HYPEL_OCC_BN32)       \
-                                         : (TM * TN == 3 ? (TB ? HYPEL_OCC_BN96 : 4) : (TA && TM * TN == 2 ? HYPEL_OCC_BN64_TA : 3))))
+    __launch_bounds__(256, (TM * TN == 1 ? (TA ? OCC_BN32_TA : OCC_BN32)                   \
+                                         : (TM * TN == 3 ? (TB ? OCC_BN96 : 4) : (TA && TM * TN == 2 ? OCC_BN64_TA : 3))))
 
 template <int WM, int WN, int TM, int TN, bool TA, bool TB, bool NARROW = false, bool MULTI = false, bool PAIR = false,
           bool VARN = false, bool ACT = false>

@@ -161,8 +161,8 @@ MERGE_WGRAD_MAX_COUT = 64
 # Round 6, same box (profiles/r6_exp_merged_levels_split.txt; one staged + split A tile serves up to four branches):
 # the 30-filter level of H13 -- fp32 kernel, unmerged: 411 us + 55 us of partial-copy reduces; merged on the 128x128 split
 # blocks with the round-5 chunking (9 taps, two channel parts): 329 + 65; 16 taps per tile and NO channel parts: 328 + 38
-# (= -100 us).  It needs the rows-first wave deal of the split kernels (seg_gemm.hip HYPEL_SPLIT_WAVE_ROWS_FIRST: 357 -> 329 us;
-# a ring-3 group fills one column tile of four).  The 60-filter level loses merged (371 + 49 vs 362 + 39), the 15-filter level
+# (= -100 us).  It needs the rows-first wave deal of the split kernels (seg_gemm.hip, wave -> (wave % WM, wave / WM): 357 ->
+# 329 us; a ring-3 group fills one column tile of four).  The 60-filter level loses merged (371 + 49 vs 362 + 39), the 15-filter level
 # loses on the split kernels (128x64 blocks: 145 us vs 135 on the 16x16x4 MFMA): both keep their round-5 forms.
 MERGE_FWD_MAX_COUT_SPLIT = 32
 MERGE_MAX_TAPS = 0  # 0 = MAX_TAPS_PER_TILE

@@ -2,7 +2,7 @@
 # Builds a second copy of the library with extra compiler flags for a same-box A/B (HYPEL_LIB_PATH selects it):
 #   tools/exp/build_variant.sh NAME "-DSOME_MACRO=0"   ->  hypelcnn_amd/csrc/variants/NAME/libhypel_hip.so
 #   REV=<commit> tools/exp/build_variant.sh NAME          ->  seg_gemm.hip as of that commit (the other objects from the tree)
-#   FILE=dense_stack.hip tools/exp/build_variant.sh NAME -DDS_REGW=0   ->  the flags (or REV) apply to that source instead
+#   FILE=gan_mfma.hip REV=112c2f2 tools/exp/build_variant.sh NAME -DGM_DIAG=5   ->  the flags (or REV) apply to that source instead
 set -e
 cd "$(dirname "$0")/../../hypelcnn_amd/csrc"
 name=$1; shift
