@@ -149,6 +149,15 @@ SIGNATURES = {
     "l2norm_segs_fwd": [_P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P],
     "l2norm_segs_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _I64, _I32],
     "l2norm_bwd": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I64, _I32],
+    "caps_uhat_fwd": [_P, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _I32, _P],
+    "caps_route_fwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "caps_agree_fwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "caps_head_bwd": [_P, _P, _P, _I64, _I32, _I32, _P],
+    "caps_agree_bwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "caps_route_bwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
+    "caps_uhat_bwd": [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _I64, _I32],
+    "caps_mask_fwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _I64],
+    "caps_mask_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

@@ -272,6 +272,8 @@ class LinearNode:
         self.dropout_keep = None
         self.residuals = []
         self.out = None
+        self.valid = False  # kind "conv": VALID padding (output pixels = those whose whole window is inside the input)
+        self.bn_update = True  # batch statistics also move the moving averages
         self.in_slices = None  # kind "blockdense": (channel offset, width) of the source slice each branch reads
 
     @property
@@ -341,6 +343,36 @@ class DenseStackNode:
     @property
     def widths(self):
         return [self.layers[0][0].shape[0]] + [w.shape[1] for w, _, _ in self.layers]
+
+
+class CapsuleNode:
+    """Digit capsules with dynamic routing as ONE op (nnmodel/CAPModel.py:72-129 of the reference): per primary capsule i
+    its own [D, J*D] map to the prediction vectors u_hat[n, i, j, :], `iterations` rounds of routing whose logits are
+    summed over the batch, and the length of the last round's output vectors.  `src` is the primary-capsule tensor
+    [N, H, W, M*D]: capsule i = p*M + g is channels [g*D, (g+1)*D) of pixel p -- a view of the pixel-major buffer.
+    Two outputs: `out` = y_conv [N, J], `out_v` = the output vectors [N, J*D] (the decoder's input)."""
+
+    def __init__(self, src, weights, biases, classes, width, iterations):
+        self.src = src
+        self.weights = weights  # I Variables [1, 1, D, J*D], contiguous in the parameter buffer (one [I, D, J*D] slab)
+        self.biases = biases  # I Variables [J*D], contiguous
+        self.classes, self.width, self.iterations = int(classes), int(width), int(iterations)
+        self.out = None
+        self.out_v = None
+
+    @property
+    def capsules(self):
+        return len(self.weights)
+
+
+class LabelMaskNode:
+    """masked_v[n, :] = sum_j labels[n, j] * v[n, j, :] (CAPModel.py:136-140): [N, J*D] x [N, J] -> [N, D]."""
+
+    def __init__(self, src, labels, classes, width):
+        self.src = src
+        self.labels = labels
+        self.classes, self.width = int(classes), int(width)
+        self.out = None
 
 
 class FeatStackNode:
@@ -428,20 +460,35 @@ def _bn_opts(opts, tower):
 
 def conv2d(inputs, num_outputs, kernel_size, scope, activation_fn=_UNSET, normalizer_fn=_UNSET,
            normalizer_params=_UNSET, weights_initializer=_UNSET, biases_initializer=_UNSET, weights_regularizer=_UNSET,
-           data_format=None):
-    """tf_slim.conv2d: NHWC, stride 1, SAME, square kernel (HYPELCNNModel.py:136,157,177)."""
+           data_format=None, padding="SAME"):
+    """tf_slim.conv2d: NHWC, stride 1, square kernel (HYPELCNNModel.py:136,157,177).  padding="VALID" (odd kernels): only
+    the output pixels whose whole window lies inside the input exist -- the same tap list over fewer output pixels, so
+    a batch norm behind it sees exactly those pixels; a 1x1 kernel is the same under either padding."""
     opts = _defaults(dict(activation_fn=activation_fn, normalizer_fn=normalizer_fn, normalizer_params=normalizer_params,
                           weights_initializer=weights_initializer, biases_initializer=biases_initializer,
                           weights_regularizer=weights_regularizer))
     k = kernel_size[0] if isinstance(kernel_size, (list, tuple)) else int(kernel_size)
     if isinstance(kernel_size, (list, tuple)) and kernel_size[0] != kernel_size[1]:
         raise NotImplementedError("only square kernels are on the hot path (HYPELCNNModel.py:174)")
+    if padding not in ("SAME", "VALID"):
+        raise ValueError(f"conv2d padding {padding!r}")
+    valid = padding == "VALID" and k != 1
+    if valid and k % 2 == 0:
+        raise NotImplementedError(f"conv2d padding='VALID' with an even kernel ({k}x{k}): only odd kernels have the "
+                                  "centred tap list the planner builds every pass from")
+    if valid and (inputs.hw is None or min(inputs.hw) < k):
+        raise ValueError(f"conv2d padding='VALID': a {k}x{k} kernel does not fit the {inputs.hw} input")
     tower = inputs.tower
     act = opts.get("activation_fn", relu)
     br = _make_branch(tower, scope, k, inputs.c, int(num_outputs), True, opts)
     decay, eps, training = _bn_opts(opts, tower)
     node = LinearNode("conv", [inputs.use()], [br], act, decay, eps, training)
-    node.out = SymTensor(tower, inputs.hw, br.cout, node=node)
+    node.valid = valid
+    # batch statistics without the moving-average update (an evaluation tower of a model that always normalises with
+    # the batch in hand): normalizer_params["update_moving"] = False
+    node.bn_update = bool((opts.get("normalizer_params") or {}).get("update_moving", True))
+    out_hw = (inputs.hw[0] - k + 1, inputs.hw[1] - k + 1) if valid else inputs.hw
+    node.out = SymTensor(tower, out_hw, br.cout, node=node)
     tower.nodes.append(node)
     return node.out
 
@@ -494,7 +541,7 @@ def concat(values, axis):
     ok = ok and all(n.sources[0] is first.sources[0] for n in nodes)
     ok = ok and all(n.act == first.act and n.has_bn == first.has_bn and n.bn_decay == first.bn_decay
                     and n.dropout_keep is None and not n.residuals for n in nodes)
-    ok = ok and all(v.consumers == 0 for v in values)
+    ok = ok and all(v.consumers == 0 for v in values) and not any(n.valid for n in nodes)
     if not ok:
         raise NotImplementedError("concat(axis=3) is supported for sibling convolutions over one input")
     tower = first.out.tower
@@ -568,6 +615,46 @@ def local_response_normalization(inputs, depth_radius=5, bias=1.0, alpha=1.0, be
     node = LRNNode(inputs.use(), depth_radius, bias, alpha, beta)
     node.out = SymTensor(inputs.tower, inputs.hw, inputs.c, node=node)
     inputs.tower.nodes.append(node)
+    return node.out
+
+
+CAPSULE_MAX_WIDTH = 32  # hypel.h HYPEL_CAPS_MAX_D: capsule width the routing kernels keep in registers
+CAPSULE_MAX_COLS = 512  # ... HYPEL_CAPS_MAX_JD: classes x width
+
+
+def capsule_routing(primary, capsule_count, classes, width, iterations, scope_prefix="DigitCaps_layer_w_"):
+    """Digit capsules + dynamic routing over the primary-capsule tensor [N, H, W, capsule_count * width].  Creates, in the
+    reference's order and under its names, `<scope_prefix><i>/weights` [1, 1, width, classes*width] (Xavier) and
+    `/biases` [classes*width] (zeros) for every capsule i; returns (y_conv [N, classes], v [N, classes*width])."""
+    if primary.hw is None or primary.c != capsule_count * width:
+        raise ValueError("capsule_routing expects [N, H, W, capsule_count * width]")
+    if iterations < 1:
+        raise ValueError("capsule_routing needs at least one routing iteration")
+    if width > CAPSULE_MAX_WIDTH or classes * width > CAPSULE_MAX_COLS:
+        raise NotImplementedError(f"capsule_routing: width {width} / {classes * width} prediction columns exceed what the "
+                                  f"routing kernels hold per thread ({CAPSULE_MAX_WIDTH} / {CAPSULE_MAX_COLS})")
+    tower = primary.tower
+    st = tower.store
+    n_caps = primary.npix * capsule_count
+    jd = classes * width
+    ws, bs = [], []
+    for i in range(n_caps):
+        ws.append(st.get(f"{scope_prefix}{i}/weights", (1, 1, width, jd), xavier_init(), True))
+        bs.append(st.get(f"{scope_prefix}{i}/biases", (jd,), zeros_init(), True))
+    node = CapsuleNode(primary.use(), ws, bs, classes, width, iterations)
+    node.out = SymTensor(tower, None, classes, node=node)
+    node.out_v = SymTensor(tower, None, jd, node=node)
+    tower.nodes.append(node)
+    return node.out, node.out_v
+
+
+def label_mask(v, labels, classes, width):
+    """sum_j labels[n, j] * v[n, j, :] -> [N, width]; the gradient flows into `v` only."""
+    if v.c != classes * width or labels.c != classes:
+        raise ValueError("label_mask: v is [N, classes*width], labels [N, classes]")
+    node = LabelMaskNode(v.use(), labels, classes, width)
+    node.out = SymTensor(v.tower, None, width, node=node)
+    v.tower.nodes.append(node)
     return node.out
 
 

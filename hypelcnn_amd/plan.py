@@ -750,6 +750,10 @@ class TowerPlan:
                 self._fwd_post(idx, node)
             elif isinstance(node, G.LRNNode):
                 self._fwd_lrn(idx, node)
+            elif isinstance(node, G.CapsuleNode):
+                self._fwd_capsule(idx, node)
+            elif isinstance(node, G.LabelMaskNode):
+                self._fwd_label_mask(idx, node)
             else:
                 raise TypeError(node)
         self._emit_level_packs(pack_pos)
@@ -766,6 +770,10 @@ class TowerPlan:
                     self._bwd_post(idx, node)
                 elif isinstance(node, G.LRNNode):
                     self._bwd_lrn(idx, node)
+                elif isinstance(node, G.CapsuleNode):
+                    self._bwd_capsule(idx, node)
+                elif isinstance(node, G.LabelMaskNode):
+                    self._bwd_label_mask(idx, node)
                 if idx in sync_map:
                     # every weight gradient at flat offsets >= lo is final once the side stream is joined: the session
                     # starts the all-reduce of what no earlier point covered here, under the rest of the backward pass
@@ -910,11 +918,21 @@ class TowerPlan:
                 for b, col in branches for i in range(b.k) for j in range(b.k)]
 
     @staticmethod
-    def _fwd_segs(taps, s_st, h, w, p):
-        """Forward segments of output pixel p: one per tap that reads a real input pixel, over all Cin reduction columns."""
-        py, px = divmod(p, w)
+    def _fwd_segs(taps, s_st, h, w, p, wo=None, r=0):
+        """Forward segments of output pixel p: one per tap that reads a real input pixel, over all Cin reduction columns.
+        VALID padding: the output is (h - 2r) x wo pixels and output pixel (y, x) is centred on input pixel (y + r, x + r)."""
+        py, px = divmod(p, w if wo is None else wo)
+        py, px = py + r, px + r
         return [(s_st.pix_off((py + dy) * w + px + dx), w_, s_st.c) for dy, dx, w_, _, _ in taps
                 if 0 <= py + dy < h and 0 <= px + dx < w]
+
+    @staticmethod
+    def _valid_geometry(node):
+        """(output width, ring) of a convolution: (None, 0) with SAME padding; VALID: output pixel (y, x) of the
+        (h - 2r) x (w - 2r) map reads the window centred on input pixel (y + r, x + r)."""
+        if not node.valid:
+            return None, 0
+        return node.out.hw[1], (node.branches[0].k - 1) // 2
 
     @staticmethod
     def _partial_copies(segs, S, kp_n=1, ldb=0):
@@ -1026,8 +1044,10 @@ class TowerPlan:
                 kp_used = max(kp_used, kp_n)
                 S_tap = S // kp_n
                 taps = self._taps([(b, col)], cin)
-                for p in range(h * w):
-                    for kp, si, chunk in self._partial_copies(self._fwd_segs(taps, s_st, h, w, p), S_tap, kp_n, cout):
+                wo, vr = self._valid_geometry(node)
+                for p in range(node.out.npix):
+                    for kp, si, chunk in self._partial_copies(self._fwd_segs(taps, s_st, h, w, p, wo, vr), S_tap, kp_n,
+                                                              cout):
                         tb.add_group((kp * S_tap + si) * rows_all * c + p * nb * c + col, chunk, nb, subkey=kp)
             # the kernel indexes bias by (c_off % ldc) + column, so merged branches share one launch
             pos = len(self.fwd)
@@ -1154,7 +1174,7 @@ class TowerPlan:
         partials are merged into one (mean, M2, rows) record, the records of all ranks are all-gathered (a host-side
         collective between two graph segments) and merged in rank order."""
         mean_ref, rstd_ref = self._ref(f"mean:{idx}"), self._ref(f"rstd:{idx}")
-        tail = (float(node.bn_eps), mean_ref, rstd_ref, self._s(aux["mm"]), self._s(aux["mv"]), float(node.bn_decay))
+        tail = (float(node.bn_eps), mean_ref, rstd_ref, self._s(aux["mm"]), self._s(aux["mv"]), self._bn_decay(node))
         if not self.sync_bn:
             l2 = Launch("bn_finalize", (None, n_chunks, chunk, rows, c) + tail, tag="bn-finalize")
             self._scratch(l2, 0, "scratch_partial", n_chunks * 2 * c)
@@ -1170,6 +1190,12 @@ class TowerPlan:
         l4 = Launch("bn_finalize_ranks", (None, self.world, c) + tail, tag="bn-finalize")
         self._scratch(l4, 0, "sbn_all", self.world * rec)
         self.fwd += [l2, l3, l4]
+
+    @staticmethod
+    def _bn_decay(node):
+        """Decay of the moving averages; a node that normalises with batch statistics but must leave the moving averages
+        alone (graph.conv2d, normalizer_params["update_moving"] = False) passes 1: m * 1 + batch * 0 = m, bit for bit."""
+        return float(node.bn_decay) if node.bn_update else 1.0
 
     def _mask_ref(self, idx, node, rows, c):
         if node.dropout_keep is None:
@@ -1216,7 +1242,7 @@ class TowerPlan:
             self.fwd.append(Launch("bn_act_small_fwd", (
                 y_ref, ldy, rows, c, float(node.bn_eps), aux["beta_ref"], act.code if act else 0,
                 act.alpha if act else 0.0, mask, c, aux["mean"], aux["rstd"], self._s(aux["mm"]), self._s(aux["mv"]),
-                float(node.bn_decay), z_ref, c), nbytes=12 * rows * c, tag="post-fwd-small"))
+                self._bn_decay(node), z_ref, c), nbytes=12 * rows * c, tag="post-fwd-small"))
             return
         self.fwd.append(Launch("bn_act_fwd", (
             y_ref, ldy, rows, c, aux.get("mean") if has_bn else None, aux.get("rstd") if has_bn else None,
@@ -1407,8 +1433,12 @@ class TowerPlan:
                         # input pixel (iy, ix) sums one segment per tap: the tap's columns of dY at output pixel
                         # (iy - dy, ix - dx) -- merged level: 49 instead of 84 segments of 15 .. 60 columns at the centre
                         # of a 7x7 patch
-                        per_pixel = [[(((iy - dy) * w + ix - dx) * nb * c + col, w_, n) for dy, dx, w_, col, n in taps
-                                      if 0 <= iy - dy < h and 0 <= ix - dx < w] for iy in range(h) for ix in range(w)]
+                        wo, vr = self._valid_geometry(node)
+                        ho, wo = (h, w) if wo is None else node.out.hw
+                        per_pixel = [[(((iy - dy - vr) * wo + ix - dx - vr) * nb * c + col, w_, n)
+                                      for dy, dx, w_, col, n in taps
+                                      if 0 <= iy - dy - vr < ho and 0 <= ix - dx - vr < wo]
+                                     for iy in range(h) for ix in range(w)]
                     # Segment splitting, the data-gradient twin of the forward tap splitting: an input pixel of a
                     # multi-kernel level sums up to sum(k^2) segments (165 for the five kernels of DUALCNN) and its
                     # block runs that much longer than a corner pixel's.  The segment list is cut into S chunks
@@ -1774,9 +1804,12 @@ class TowerPlan:
         src = node.sources[0]
         h, w = src.hw
 
+        wo, vr = self._valid_geometry(node)
+        ho, wo = (h, w) if wo is None else node.out.hw
+
         def pairs(dy, dx, col):
-            return [(s_st.pix_off((oy + dy) * w + ox + dx), (oy * w + ox) * nb * c + col)
-                    for oy in range(h) for ox in range(w) if 0 <= oy + dy < h and 0 <= ox + dx < w]
+            return [(s_st.pix_off((oy + vr + dy) * w + ox + vr + dx), (oy * wo + ox) * nb * c + col)
+                    for oy in range(ho) for ox in range(wo) if 0 <= oy + vr + dy < h and 0 <= ox + vr + dx < w]
 
         lay = self._level_pass(idx, node, "wgrad")
         # (every offset of the largest kernel must meet at least one pixel pair, or its block of the packed image would
@@ -1872,6 +1905,120 @@ class TowerPlan:
                                            rows, c, node.radius, float(node.bias), float(node.alpha), float(node.beta),
                                            self._ref(gst.buf, gst.ch_off), gst.ld, acc), nbytes=16 * rows * c,
                                tag="lrn-bwd"))
+
+    # ------------------------------------------------------------------ capsules (csrc/capsule.hip)
+    def _fwd_capsule(self, idx, node):
+        """Prediction vectors u_hat [N, I, J*D] (one pass that reads every W_i once), then per routing iteration one
+        launch that sums over the capsules (s_r, squash -> v_r) and one that sums the agreement over the batch
+        (b_{r+1}, softmax -> c_{r+1}); the last iteration writes y_conv instead.  Kept for the backward pass: u_hat,
+        every c_r, s_r and v_r.  Coefficients live in ONE buffer [2R-1][I][J] (c_0 .. c_{R-1}, then the backward pass's
+        db_1 .. db_{R-1}) and the batch vectors in ONE buffer [2R-1][N][J*D] (the backward pass's ds_0 .. ds_{R-1}, then
+        v_0 .. v_{R-2}): the gradient of u_hat is the sum of their 2R-1 outer products and is never written to memory."""
+        if getattr(self.sess, "dist", None) is not None:
+            raise NotImplementedError("capsule routing is single-device only: its agreement is summed over the batch, so "
+                                      "data parallel (WORLD_SIZE > 1) would need an all-reduce inside every routing iteration")
+        nb, src = self.nb, node.src
+        J, D, R, I = node.classes, node.width, node.iterations, node.capsules
+        M = src.c // D
+        jd = J * D
+        s_st = self.storage_of(src)
+        self._assert_contiguous(node.weights)
+        self._assert_contiguous(node.biases)
+        t = self.be.upload(np.asarray([s_st.pix_off(p) for p in range(src.npix)], np.int64))
+        self.tables.append(t)
+        aux = {"pix": Ref(t), "x": s_st}
+        self.node_aux[idx] = aux
+        self._alloc(f"uhat:{idx}", nb * I * jd)
+        self._alloc(f"capc:{idx}", (2 * R - 1) * I * J)
+        import torch
+        self._alloc(f"capb:{idx}", max(R - 1, 1) * I * J, torch.float64)  # routing logits: fp64 (they grow with the batch)
+        self._alloc(f"capvec:{idx}", (2 * R - 1) * nb * jd)
+        self._alloc(f"caps:{idx}", R * nb * jd)
+        y_st = self._new_value(node.out, f"capy:{idx}")
+        v_st = self._new_value(node.out_v, f"capv:{idx}")
+        uhat, cc, vec = self._ref(f"uhat:{idx}"), self._ref(f"capc:{idx}"), self._ref(f"capvec:{idx}")
+        ubytes = 4 * nb * I * jd
+        self.fwd.append(Launch("caps_uhat_fwd", (self._ref(s_st.buf), aux["pix"], s_st.ld, M, self._p(node.weights[0]),
+                                                 self._p(node.biases[0]), nb, I, D, jd, uhat),
+                               nbytes=ubytes + 4 * I * (D + 1) * jd, tag="caps-uhat"))
+        self.fwd.append(Launch("fill_f32", (cc, I * J, 1.0 / J), tag="caps-c0"))
+        for r in range(R):
+            last = r == R - 1
+            v_ref = self._ref(v_st.buf) if last else vec + (R + r) * nb * jd
+            self.fwd.append(Launch("caps_route_fwd", (uhat, cc + r * I * J, nb, I, J, D,
+                                                      self._ref(f"caps:{idx}", r * nb * jd), v_ref,
+                                                      self._ref(y_st.buf) if last else None), nbytes=ubytes,
+                                   tag="caps-route"))
+            if not last:
+                self.fwd.append(Launch("caps_agree_fwd", (uhat, v_ref, nb, I, J, D,
+                                                          self._ref(f"capb:{idx}", (r - 1) * I * J) if r > 0 else None,
+                                                          self._ref(f"capb:{idx}", r * I * J), cc + (r + 1) * I * J),
+                                       nbytes=ubytes, tag="caps-agree"))
+
+    def _bwd_capsule(self, idx, node):
+        """Reverse sweep over the routing iterations: ds_{R-1} from the gradients of y_conv and v; then for r = R-1 .. 1
+        one pass over u_hat for dc_r (-> db_r through the softmax) and one for dv_{r-1} (-> ds_{r-1} through the squash);
+        c_0 is a constant, so iteration 0 reads nothing.  One last launch builds du_hat on the fly from the 2R-1
+        (coefficient, batch vector) pairs and reduces it into dW_i, dbias_i and dx."""
+        nb, src = self.nb, node.src
+        J, D, R, I = node.classes, node.width, node.iterations, node.capsules
+        M = src.c // D
+        jd = J * D
+        aux = self.node_aux[idx]
+        s_st = aux["x"]
+        y_st, v_st = self.storage[id(node.out)], self.storage[id(node.out_v)]
+        gy = self._ref("g:" + y_st.buf) if self.grad_written.get(id(node.out), False) else None
+        gv = self._ref("g:" + v_st.buf) if self.grad_written.get(id(node.out_v), False) else None
+        if gy is None and gv is None:
+            raise RuntimeError(f"capsule node {idx} receives no gradient")
+        uhat, cc, vec = self._ref(f"uhat:{idx}"), self._ref(f"capc:{idx}"), self._ref(f"capvec:{idx}")
+        ss = self._ref(f"caps:{idx}")
+        ubytes = 4 * nb * I * jd
+        self.bwd.append(Launch("caps_head_bwd", (gy, gv, ss + (R - 1) * nb * jd, nb, J, D, vec + (R - 1) * nb * jd),
+                               tag="caps-head-bwd"))
+        for r in range(R - 1, 0, -1):
+            db = cc + (R + r - 1) * I * J
+            self.bwd.append(Launch("caps_agree_bwd", (uhat, vec + r * nb * jd, nb, I, J, D, cc + r * I * J,
+                                                      cc + (R + r) * I * J if r < R - 1 else None, db),
+                                   nbytes=ubytes, tag="caps-agree-bwd"))
+            self.bwd.append(Launch("caps_route_bwd", (uhat, db, nb, I, J, D, ss + (r - 1) * nb * jd,
+                                                      vec + (r - 1) * nb * jd), nbytes=ubytes, tag="caps-route-bwd"))
+        trains = self._trains(node.weights)
+        dw = db_ = None
+        acc_w = 0
+        if trains:
+            dw, db_ = self._g(node.weights[0]), self._g(node.biases[0])
+            acc_w = max([self._param_acc(v) for v in node.weights + node.biases])
+        dx, lddx, acc_x, dpix = None, 0, 0, aux["pix"]
+        if self._needs_grad(src):
+            gst, acc_x = self._grad_target(src)
+            dx, lddx = self._ref(gst.buf), gst.ld
+            if [gst.pix_off(p) for p in range(src.npix)] != [s_st.pix_off(p) for p in range(src.npix)]:
+                t = self.be.upload(np.asarray([gst.pix_off(p) for p in range(src.npix)], np.int64))
+                self.tables.append(t)
+                dpix = Ref(t)
+        self.bwd.append(Launch("caps_uhat_bwd", (self._ref(s_st.buf), aux["pix"], s_st.ld, M, self._p(node.weights[0]), nb,
+                                                 I, J, D, 2 * R - 1, cc, vec, dw, db_, acc_w, dx, dpix, lddx, acc_x),
+                               nbytes=4 * I * (D + 1) * jd * (2 if trains else 1), tag="caps-uhat-bwd"))
+
+    def _fwd_label_mask(self, idx, node):
+        v_st, l_st = self.storage_of(node.src), self.storage_of(node.labels)
+        st = self._new_value(node.out, f"z:{idx}")
+        self.fwd.append(Launch("caps_mask_fwd", (self._ref(v_st.buf, v_st.ch_off), v_st.ld, self._ref(l_st.buf, l_st.ch_off),
+                                                 l_st.ld, self.nb, node.classes, node.width, self._ref(st.buf), st.ld),
+                               tag="caps-mask"))
+
+    def _bwd_label_mask(self, idx, node):
+        z_st = self.storage[id(node.out)]
+        if not self.grad_written.get(id(node.out.owner), False):
+            raise RuntimeError(f"label mask node {idx} receives no gradient")
+        if not self._needs_grad(node.src):
+            return
+        l_st = self.storage_of(node.labels)
+        gst, acc = self._grad_target(node.src)
+        self.bwd.append(Launch("caps_mask_bwd", (self._ref("g:" + z_st.buf), z_st.ld, self._ref(l_st.buf, l_st.ch_off),
+                                                 l_st.ld, self.nb, node.classes, node.width, self._ref(gst.buf, gst.ch_off),
+                                                 gst.ld, acc), tag="caps-mask-bwd"))
 
 
 # =========================================================================================== GAN phases

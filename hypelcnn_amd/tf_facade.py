@@ -613,6 +613,10 @@ class ReferenceModel:
     def __init__(self, model_name, reference_root):
         import importlib
         from .common import common_nn_ops as P
+        if model_name == "CAPModel":
+            raise NotImplementedError(
+                "the reference's CAPModel.py is not served through the facade: its per-capsule Python loop of split / tile / "
+                "depthwise_conv2d is not a pattern worth recognising -- use hypelcnn_amd.nnmodel.CAPModel (--model_name CAPModel)")
         self._ctx = installed(reference_root)
         with self._ctx:
             mod = importlib.import_module("nnmodel." + model_name)

@@ -584,6 +584,46 @@ int hypel_nce_loss(const float* g, int64_t ldg, const float* r, int64_t ldr, int
                    float tau, float weight, float* loss, int32_t accumulate_loss, float* dg, int64_t lddg,
                    int32_t acc_dg, float* dr, int64_t lddr, int32_t acc_dr, float* ws, hypel_stream_t stream);
 
+/* ---- capsule classifier (reference nnmodel/CAPModel.py; csrc/capsule.hip) -------------------------------------
+ * Batch n, primary capsules i, classes j, capsule width d (<= HYPEL_CAPS_MAX_D), jd = j * d prediction columns
+ * (<= HYPEL_CAPS_MAX_JD).  x[n][i][:] is a view of a pixel-major buffer: element pix[i / m] + n * ldx + (i % m) * d.
+ * w is the [i][d][jd] slab of the per-capsule maps, bias [i][jd], uhat [n][i][jd].  All sums run in a fixed order inside
+ * one block (no atomics): two runs give identical bits.
+ *   uhat_fwd   uhat[n][i][:] = bias_i + x[n][i][:] . W_i                                     (reads W once)
+ *   route_fwd  s[n][col] = sum_i coef[i][col / d] * uhat[n][i][col];  v = squash(s), q = mean(s^2) per capsule,
+ *              v = q s / ((1 + q) sqrt(q + 1e-9));  y[n][j] = |v[n][j][:]| when y is not null
+ *   agree_fwd  b_out[i][j] = b_in[i][j] (null = 0) + sum_n <uhat[n][i][j][:], v[n][j][:]>;  c_out = softmax_j(b_out);
+ *              the routing logits b are fp64 buffers and both agree kernels sum in fp64 (b grows with the batch)
+ *   head_bwd   dv = gy * v / |v| + gv (either may be null), ds = squash'(s) dv
+ *   agree_bwd  dc[i][j] = sum_n <uhat[n][i][j][:], ds[n][j][:]>;  db = c * (dc - <c, dc>) + db_next (null = 0)
+ *   route_bwd  dv[n][col] = sum_i coef[i][col / d] * uhat[n][i][col];  ds_out = squash'(s_in) dv
+ *   uhat_bwd   duhat[n][i][col] = sum_t coefs[t][i][col / d] * vecs[t][n][col] (n_terms pairs, never stored);
+ *              dw_i = x_i^T duhat_i, dbias_i = sum_n duhat_i (both or neither), dx[n][i][:] = duhat[n][i][:] . W_i^T
+ *              at dpix[i / m] + n * lddx + (i % m) * d (null dx = skipped); acc_w / acc_x: add to what is there
+ *   mask_fwd   out[n][e] = sum_j labels[n][j] * v[n][j * d + e];  mask_bwd: gv[n][j * d + e] (+)= labels[n][j] * gout[n][e] */
+#define HYPEL_CAPS_MAX_D 32
+#define HYPEL_CAPS_MAX_JD 512
+int hypel_caps_uhat_fwd(const float* x, const int64_t* pix, int64_t ldx, int32_t m, const float* w, const float* bias,
+                        int64_t n, int32_t i, int32_t d, int32_t jd, float* uhat, hypel_stream_t stream);
+int hypel_caps_route_fwd(const float* uhat, const float* coef, int64_t n, int32_t i, int32_t j, int32_t d, float* s,
+                         float* v, float* y, hypel_stream_t stream);
+int hypel_caps_agree_fwd(const float* uhat, const float* v, int64_t n, int32_t i, int32_t j, int32_t d,
+                         const double* b_in, double* b_out, float* c_out, hypel_stream_t stream);
+int hypel_caps_head_bwd(const float* gy, const float* gv, const float* s, int64_t n, int32_t j, int32_t d, float* ds,
+                        hypel_stream_t stream);
+int hypel_caps_agree_bwd(const float* uhat, const float* ds, int64_t n, int32_t i, int32_t j, int32_t d, const float* c,
+                         const float* db_next, float* db, hypel_stream_t stream);
+int hypel_caps_route_bwd(const float* uhat, const float* coef, int64_t n, int32_t i, int32_t j, int32_t d,
+                         const float* s_in, float* ds_out, hypel_stream_t stream);
+int hypel_caps_uhat_bwd(const float* x, const int64_t* pix, int64_t ldx, int32_t m, const float* w, int64_t n, int32_t i,
+                        int32_t j, int32_t d, int32_t n_terms, const float* coefs, const float* vecs, float* dw,
+                        float* dbias, int32_t acc_w, float* dx, const int64_t* dpix, int64_t lddx, int32_t acc_x,
+                        hypel_stream_t stream);
+int hypel_caps_mask_fwd(const float* v, int64_t ldv, const float* labels, int64_t ldl, int64_t n, int32_t j, int32_t d,
+                        float* out, int64_t ldo, hypel_stream_t stream);
+int hypel_caps_mask_bwd(const float* gout, int64_t ldg, const float* labels, int64_t ldl, int64_t n, int32_t j, int32_t d,
+                        float* gv, int64_t ldgv, int32_t accumulate, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
