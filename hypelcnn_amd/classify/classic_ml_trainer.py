@@ -1,0 +1,167 @@
+"""Classic-ML baseline (reference classify/classic_ml_trainer.py:20-157): a kernel SVC on flattened patches, trained and
+served on the device by hypelcnn_amd.classic.svc.SVC, with the reference's flow, flag names and output files --
+`confusion_matrix_<loader>_run<i>.csv`, `metrics_<loader>_run<i>.txt` (OA,AA,KAPPA) and `params_<loader>_run<i>.json`
+under --base_log_path, next to which utilities/latex_table_from_conf_set*.py expects the CNN's.
+
+Differences from the reference, all on purpose:
+ - the estimator, which the reference picks by editing comments (:46-50), is a flag: --estimator svc_rbf (its GRSS2013
+   line :49, gamma 1e-09, C 10000; --svc_gamma / --svc_c / --svc_tol) or svc_poly (its :48, degree 1, gamma "scale");
+ - RandomForestClassifier (:46) and --hyperparamopt (:126-136) are refused by name: a forest's result depends on
+   scikit-learn's random stream and cannot be held to a fixture, and the grid search needs scikit-learn's
+   StratifiedShuffleSplit index stream on the machine that runs it;
+ - --fullscene writes result_raw.tif / result_colorized.tif under --output_path, not the reference's hard-wired ".."
+   (:111); patches are cut on the device (hypel_gather_patches_f32) and predicted in chunks sized from free memory,
+   independent of --batch_size;
+ - OA / AA / kappa come from the confusion matrix on the host (sklearn.metrics' definitions, :56-59)."""
+import argparse
+import json
+import os
+import time
+
+import numpy
+
+from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, \
+    add_parse_cmds_for_trainers, type_ensure_strtobool
+from hypelcnn_amd.common.common_nn_ops import SceneArrays, create_colored_image, get_loader_from_name
+from hypelcnn_amd.common.tiff_io import imwrite
+from hypelcnn_amd.importer.InMemoryImporter import InMemoryImporter
+
+ESTIMATORS = ("svc_rbf", "svc_poly")
+
+
+def add_parse_cmds_for_app(parser):
+    parser.add_argument("--hyperparamopt", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, performs hyper parameter optimization.")
+    parser.add_argument("--fullscene", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, performs full scene classification.")
+    parser.add_argument("--split_count", nargs="?", type=int, default=1, help="Split count")
+    parser.add_argument("--estimator", nargs="?", type=str, default="svc_rbf",
+                        help="svc_rbf (reference :49) or svc_poly (reference :48)")
+    parser.add_argument("--svc_gamma", nargs="?", type=float, default=1e-09, help="RBF gamma (svc_rbf)")
+    parser.add_argument("--svc_c", nargs="?", type=float, default=None, help="C (default: 10000 svc_rbf, 1 svc_poly)")
+    parser.add_argument("--svc_tol", nargs="?", type=float, default=1e-3, help="Stopping tolerance of the solver")
+
+
+def create_estimator(flags, backend=None):
+    from hypelcnn_amd.classic.svc import SVC
+    name = flags.estimator
+    if name in ("random_forest", "rf", "RandomForestClassifier", "ExtraTreesClassifier"):
+        raise NotImplementedError(
+            f"--estimator {name}: RandomForestClassifier (reference classic_ml_trainer.py:46) is not built: its result "
+            f"depends on scikit-learn's random stream, so it cannot be held to a fixture, and tree building is a different "
+            f"kind of kernel; use one of {ESTIMATORS}")
+    if name == "svc_rbf":
+        return SVC(kernel="rbf", gamma=flags.svc_gamma, C=10000.0 if flags.svc_c is None else flags.svc_c,
+                   tol=flags.svc_tol, backend=backend)
+    if name == "svc_poly":
+        return SVC(kernel="poly", degree=1, gamma="scale", C=1.0 if flags.svc_c is None else flags.svc_c,
+                   tol=flags.svc_tol, backend=backend)
+    raise ValueError(f"--estimator {name}: one of {ESTIMATORS}")
+
+
+def flatten_data(data):
+    return numpy.reshape(data, [data.shape[0], data.shape[1] * data.shape[2] * data.shape[3]])
+
+
+def confusion_matrix(labels, predicted):
+    """sklearn.metrics.confusion_matrix: rows = truth, columns = prediction, over the sorted labels seen in either."""
+    labels, predicted = numpy.asarray(labels).astype(numpy.int64), numpy.asarray(predicted).astype(numpy.int64)
+    seen = numpy.unique(numpy.concatenate([labels, predicted]))
+    index = numpy.searchsorted(seen, numpy.arange(seen.max() + 1))
+    cm = numpy.zeros((len(seen), len(seen)), numpy.int64)
+    numpy.add.at(cm, (index[labels], index[predicted]), 1)
+    return cm
+
+
+def scores(cm):
+    """accuracy_score, balanced_accuracy_score (mean recall over the classes that occur), cohen_kappa_score."""
+    cm = cm.astype(numpy.float64)
+    total = cm.sum()
+    oa = numpy.trace(cm) / total
+    support = cm.sum(1)
+    aa = float(numpy.mean(numpy.diag(cm)[support > 0] / support[support > 0]))
+    expected = numpy.outer(cm.sum(1), cm.sum(0)) / total
+    off = 1.0 - numpy.eye(len(cm))
+    kappa = 1.0 - (off * cm).sum() / (off * expected).sum()
+    return float(oa), aa, float(kappa)
+
+
+def print_output(algorithm_params, average_accuracy, conf_matrix, kappa, overall_accuracy, index, name, base_log_path):
+    """reference :139-157"""
+    print("OA:%5.5f" % overall_accuracy)
+    print("AA:%5.5f" % average_accuracy)
+    print("KAPPA:%5.5f" % kappa)
+    print("Confusion Matrix:")
+    print(conf_matrix)
+    file_id = f"{name}_run{index}"
+    os.makedirs(base_log_path, exist_ok=True)
+    numpy.savetxt(os.path.join(base_log_path, f"confusion_matrix_{file_id}.csv"), conf_matrix, fmt="%d", delimiter=",")
+    with open(os.path.join(base_log_path, f"metrics_{file_id}.txt"), "w") as metrics_file:
+        print("OA,AA,KAPPA", file=metrics_file)
+        print("%.6f,%.6f,%.6f" % (overall_accuracy, average_accuracy, kappa), file=metrics_file)
+    with open(os.path.join(base_log_path, f"params_{file_id}.json"), "w") as params_file:
+        json.dump(algorithm_params, params_file)
+
+
+def perform_full_scene_classification(data_path, loader_name, neighborhood, estimator, output_path):
+    """reference :83-115: every pixel of the scene, row-major, one (x, y) target each."""
+    import torch
+    backend = estimator._backend()
+    loader = get_loader_from_name(loader_name, data_path)
+    data_set = loader.load_data(neighborhood, False)
+    scene_shape = data_set.get_scene_shape()
+    ys, xs = numpy.meshgrid(numpy.arange(scene_shape[0]), numpy.arange(scene_shape[1]), indexing="ij")
+    targets = numpy.stack([xs.reshape(-1), ys.reshape(-1), numpy.zeros(xs.size, dtype=int)], axis=1)
+    arrays = SceneArrays()
+    arrays.feed(data_set, targets, backend)
+    raster = torch.zeros(scene_shape[0] * scene_shape[1], dtype=torch.uint8, device=backend.device)
+    estimator.predict_scene(arrays, raster, scene_shape[1])
+    scene_as_image = raster.cpu().numpy().reshape(scene_shape[0], scene_shape[1])
+    os.makedirs(output_path, exist_ok=True)
+    imwrite(os.path.join(output_path, "result_raw.tif"), scene_as_image)
+    imwrite(os.path.join(output_path, "result_colorized.tif"),
+            create_colored_image(scene_as_image, loader.get_samples_color_list()))
+    return scene_as_image
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    add_parse_cmds_for_loaders(parser)
+    add_parse_cmds_for_loggers(parser)
+    add_parse_cmds_for_app(parser)
+    add_parse_cmds_for_trainers(parser)
+    return parser
+
+
+def main(argv=None, backend=None):
+    flags, _ = build_parser().parse_known_args(argv)
+    if flags.hyperparamopt:
+        raise NotImplementedError(
+            "--hyperparamopt (reference classic_ml_trainer.py:126-136, GridSearchCV over StratifiedShuffleSplit) is not "
+            "built: it needs scikit-learn's split index stream on the machine that runs it; search on the host and pass "
+            "the result as --svc_gamma / --svc_c")
+    results = []
+    for run_index in range(flags.split_count):
+        print("Starting episode#%d" % run_index)
+        training, _, validation, _, _, _, _ = InMemoryImporter().read_data_set(
+            loader_name=flags.loader_name, path=flags.path, test_data_ratio=0, train_data_ratio=0.1,
+            neighborhood=flags.neighborhood, normalize=False)
+        start_time = time.time()
+        estimator = create_estimator(flags, backend)
+        estimator.fit(flatten_data(training.data), training.labels)
+        print("Completed training(%.3f sec)" % (time.time() - start_time))
+        predicted = estimator.predict(flatten_data(validation.data))
+        conf_matrix = confusion_matrix(validation.labels, predicted)
+        overall_accuracy, average_accuracy, kappa = scores(conf_matrix)
+        print_output(estimator.get_params(), average_accuracy, conf_matrix, kappa, overall_accuracy, run_index,
+                     flags.loader_name, flags.base_log_path)
+        scene = None
+        if flags.fullscene:
+            scene = perform_full_scene_classification(flags.path, flags.loader_name, flags.neighborhood, estimator,
+                                                      flags.output_path)
+        results.append((estimator, predicted, conf_matrix, (overall_accuracy, average_accuracy, kappa), scene))
+    return results
+
+
+if __name__ == "__main__":
+    main()

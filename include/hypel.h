@@ -30,7 +30,7 @@ extern "C" {
 
 typedef void* hypel_stream_t; /* hipStream_t */
 
-#define HYPEL_ABI_VERSION 6  /* bump whenever a prototype, a struct layout or the meaning of a flag changes */
+#define HYPEL_ABI_VERSION 7  /* bump whenever a prototype, a struct layout or the meaning of a flag changes */
 
 /* activation codes (leaky_relu: HYPELCNNModel.py:39, DUALCNNModel.py:18, shadow_data_models.py:53;
  * relu: tf_slim default, CONCNNModel.py; sigmoid: HYPELCNNModel.py:93; tanh: shadow_data_models.py:86) */
@@ -623,6 +623,45 @@ int hypel_caps_mask_fwd(const float* v, int64_t ldv, const float* labels, int64_
                         float* out, int64_t ldo, hypel_stream_t stream);
 int hypel_caps_mask_bwd(const float* gout, int64_t ldg, const float* labels, int64_t ldl, int64_t n, int32_t j, int32_t d,
                         float* gv, int64_t ldgv, int32_t accumulate, hypel_stream_t stream);
+
+/* ---- kernel support-vector classifier (classify/classic_ml_trainer.py:46-54,105: sklearn.svm.SVC.fit / .predict, i.e.
+ * libsvm's C-SVC with one-vs-one voting) ---------------------------------------------------------------------------
+ * The two big products -- rows x vectors over the features, rows x pairs over the vectors -- are hypel_seg_gemm_f32
+ * launches (HYPEL_GEMM_SPLIT6); these entry points are what sits between them.
+ *
+ * hypel_svm_center_norms_f32: x[r][0..cols) -= mean (mean NULL: left as it is), norms[r] = sum of squares of the row as
+ *   stored afterwards, summed in fp64 (norms NULL: not written).  RBF only subtracts the training mean: distances do not
+ *   change while |x|^2 falls by orders of magnitude, and one fp32 rounding of |x|^2 times gamma is the error of the
+ *   exponent.  The polynomial kernel is not translation invariant and is never centred.
+ * hypel_svm_kernel_apply_f32: inner products g[r][c] = x_r . z_c -> kernel values in place, one streaming pass.
+ *   HYPEL_SVM_RBF: exp(-gamma max(0, row_norms[r] + col_norms[c] - 2 g)); HYPEL_SVM_POLY: (gamma g + coef0)^degree,
+ *   degree 1..3.  Evaluated in fp64, stored fp32 (libsvm's Qfloat).
+ * hypel_svm_smo_ovo: libsvm's Solver::Solve for C-SVC on every class pair at once, one workgroup per pair.  k is the
+ *   whole training kernel matrix [l][ldk] with the rows sorted by class; pair p works on rows [a0, a0 + na) (y = +1,
+ *   the lower class) and [b0, b0 + nb) (y = -1).  Second-order working-set selection (Fan, Chen, Lin 2005), clipped
+ *   two-variable update, gradient update from two rows of k, stop when m(alpha) - M(alpha) < tol; no shrinking.
+ *   alpha and the gradient are fp64 as in libsvm: in LDS while 3 * l_max doubles fit 48 KB, else in ws (3 doubles per
+ *   element, pair p at ws + 3 * out_off; may be NULL when every pair fits).  Per pair: alpha_y[out_off + t] = alpha_t
+ *   y_t, rho[p], obj[p] = the dual objective 1/2 a'Qa - sum a as the solver sees it, n_iter[p], status[p].  The loop is
+ *   bounded: after max_iter (<= HYPEL_SVM_MAX_ITER_LIMIT) iterations a pair ends with HYPEL_SVM_NOT_CONVERGED and the
+ *   caller raises.
+ * hypel_svm_vote: dec[r][p] (pair order (0,1), (0,2) ... as svm_predict_values) -> label: dec > 0 votes for the lower
+ *   class of the pair, anything else for the higher; the FIRST class with the maximal count wins.  The label is
+ *   class_labels[winner] (NULL: the winner's index), written to out[y * raster_w + x] for points[r] = (x, y) -- the
+ *   whole-scene path, like hypel_argmax_scatter -- or to out[r] when points is NULL. */
+enum { HYPEL_SVM_RBF = 0, HYPEL_SVM_POLY = 1 };
+enum { HYPEL_SVM_CONVERGED = 0, HYPEL_SVM_NOT_CONVERGED = 1 };
+#define HYPEL_SVM_MAX_ITER_LIMIT 1000000
+typedef struct { int32_t a0; int32_t na; int32_t b0; int32_t nb; int64_t out_off; } hypel_svm_pair_t;
+int hypel_svm_center_norms_f32(float* x, int64_t ld, int64_t rows, int32_t cols, const float* mean, double* norms,
+                               hypel_stream_t stream);
+int hypel_svm_kernel_apply_f32(float* g, int64_t ld, int64_t rows, int32_t cols, int32_t kind, double gamma, double coef0,
+                               int32_t degree, const double* row_norms, const double* col_norms, hypel_stream_t stream);
+int hypel_svm_smo_ovo(const float* k, int64_t ldk, const hypel_svm_pair_t* pairs, int32_t n_pairs, int32_t l_max,
+                      double c, double tol, int32_t max_iter, double* alpha_y, double* rho, double* obj, int32_t* n_iter,
+                      int32_t* status, double* ws, hypel_stream_t stream);
+int hypel_svm_vote(const float* dec, int64_t ld, int64_t rows, int32_t n_classes, const uint8_t* class_labels,
+                   const int32_t* points, uint8_t* out, int64_t raster_w, hypel_stream_t stream);
 
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);

@@ -1,0 +1,170 @@
+"""TEST INFRASTRUCTURE: numpy twin of the support-vector entry points (include/hypel.h, hypel_svm_*), attached to
+tests/emu_backend.EmuBackend on import.  An executable specification of each kernel's contract, written from the
+header and from libsvm's published algorithm (Fan, Chen, Lin 2005; Chang and Lin, "LIBSVM", section 4) -- buffers have
+the device's dtypes, the arithmetic inside a kernel runs in float64."""
+import numpy as np
+
+from hypelcnn_amd.backend import SVM_MAX_ITER_LIMIT, SVM_PAIR_DTYPE
+from tests.emu_backend import EmuBackend, _arr, _mat
+
+TAU = 1e-12
+RBF, POLY = 0, 1
+CONVERGED, NOT_CONVERGED = 0, 1
+
+
+def kernel_values(g, kind, gamma, coef0, degree, rn=None, cn=None):
+    g = np.asarray(g, np.float64)
+    if kind == RBF:
+        return np.exp(-gamma * np.maximum(rn[:, None] + cn[None, :] - 2.0 * g, 0.0))
+    assert kind == POLY and 1 <= degree <= 3
+    return (gamma * g + coef0) ** degree
+
+
+def _last_argmax(v):
+    """index of the maximum; among equal values the largest index (libsvm scans upwards with >=)"""
+    return len(v) - 1 - int(np.argmax(v[::-1]))
+
+
+def smo_pair(K, na, C, tol, max_iter):
+    """libsvm's Solver::Solve for C-SVC on one pair: K [l, l] (fp32 values), the first na elements have y = +1.
+    Returns alpha * y, rho, objective, iterations, status."""
+    l = K.shape[0]
+    K = K.astype(np.float64)
+    y = np.where(np.arange(l) < na, 1.0, -1.0)
+    alpha = np.zeros(l)
+    G = -np.ones(l)
+    QD = np.diag(K).copy()
+    status, it = NOT_CONVERGED, 0
+    while it < max_iter:
+        up = np.where(y > 0, alpha < C, alpha > 0)
+        low = np.where(y > 0, alpha > 0, alpha < C)
+        yg = y * G
+        if not up.any():
+            status = CONVERGED
+            break
+        i = _last_argmax(np.where(up, -yg, -np.inf))
+        gmax = -yg[i]
+        if not low.any():
+            status = CONVERGED
+            break
+        g2 = np.max(np.where(low, yg, -np.inf))
+        gd = gmax + yg
+        cand = low & (gd > 0)
+        if gmax + g2 < tol or not cand.any():
+            status = CONVERGED
+            break
+        quad = QD[i] + QD - 2.0 * K[i]
+        quad = np.where(quad > 0, quad, TAU)
+        j = _last_argmax(np.where(cand, gd * gd / quad, -np.inf))
+        q = quad[j]
+        ai0, aj0 = alpha[i], alpha[j]
+        ai, aj = ai0, aj0
+        if y[i] != y[j]:
+            delta = (-G[i] - G[j]) / q
+            diff = ai - aj
+            ai += delta
+            aj += delta
+            if diff > 0:
+                if aj < 0:
+                    aj, ai = 0.0, diff
+            elif ai < 0:
+                ai, aj = 0.0, -diff
+            if diff > 0:
+                if ai > C:
+                    ai, aj = C, C - diff
+            elif aj > C:
+                aj, ai = C, C + diff
+        else:
+            delta = (G[i] - G[j]) / q
+            s = ai + aj
+            ai -= delta
+            aj += delta
+            if s > C:
+                if ai > C:
+                    ai, aj = C, s - C
+            elif aj < 0:
+                aj, ai = 0.0, s
+            if s > C:
+                if aj > C:
+                    aj, ai = C, s - C
+            elif ai < 0:
+                ai, aj = 0.0, s
+        alpha[i], alpha[j] = ai, aj
+        G += y * (K[i] * ((ai - ai0) * y[i]) + K[j] * ((aj - aj0) * y[j]))
+        it += 1
+    yg = y * G
+    free = (alpha > 0) & (alpha < C)
+    if free.any():
+        rho = yg[free].sum() / free.sum()
+    else:
+        at_c, at_0 = alpha >= C, alpha <= 0
+        ub_set = (at_c & (y < 0)) | (at_0 & (y > 0))
+        lb_set = (at_c & (y > 0)) | (at_0 & (y < 0))
+        ub = yg[ub_set].min() if ub_set.any() else np.inf
+        lb = yg[lb_set].max() if lb_set.any() else -np.inf
+        rho = (ub + lb) / 2.0
+    return alpha * y, rho, float((alpha * (G - 1.0)).sum() / 2.0), it, status
+
+
+def vote(dec, n_classes):
+    """libsvm svm_predict_values + svm_predict: dec [rows, >= n_pairs] -> winner index per row."""
+    rows = dec.shape[0]
+    votes = np.zeros((rows, n_classes), np.int32)
+    p = 0
+    for a in range(n_classes):
+        for b in range(a + 1, n_classes):
+            lower = dec[:, p] > 0
+            votes[:, a] += lower
+            votes[:, b] += ~lower
+            p += 1
+    return np.argmax(votes, axis=1)  # numpy's argmax is the FIRST maximum
+
+
+def _k_svm_center_norms_f32(self, x, ld, rows, cols, mean, norms):
+    m = _mat(x, ld, rows, cols)
+    if mean is not None:
+        m[...] = m - _arr(mean)[:cols]  # fp32 subtraction, stored
+    if norms is not None:
+        _arr(norms, np.float64)[:rows] = (m.astype(np.float64) ** 2).sum(1)
+
+
+def _k_svm_kernel_apply_f32(self, g, ld, rows, cols, kind, gamma, coef0, degree, row_norms, col_norms):
+    m = _mat(g, ld, rows, cols)
+    rn = None if row_norms is None else _arr(row_norms, np.float64)[:rows]
+    cn = None if col_norms is None else _arr(col_norms, np.float64)[:cols]
+    assert kind != RBF or (rn is not None and cn is not None)
+    m[...] = kernel_values(m, kind, gamma, coef0, degree, rn, cn).astype(np.float32)
+
+
+def _k_svm_smo_ovo(self, k, ldk, pairs, n_pairs, l_max, c, tol, max_iter, alpha_y, rho, obj, n_iter, status, ws):
+    assert 0 < max_iter <= SVM_MAX_ITER_LIMIT, "the iteration cap is bounded"
+    tab = pairs.t.numpy()[pairs.off:].view(SVM_PAIR_DTYPE)[:n_pairs]
+    kf = _arr(k)
+    for p, rec in enumerate(tab):
+        a0, na, b0, nb, off = (int(rec[f]) for f in ("a0", "na", "b0", "nb", "out_off"))
+        assert na + nb <= l_max and (3 * l_max * 8 <= 48 * 1024 or ws is not None)
+        rows = np.concatenate([np.arange(a0, a0 + na), np.arange(b0, b0 + nb)])
+        sub = kf[(rows[:, None] * ldk + rows[None, :])]
+        ay, r, o, it, st = smo_pair(sub, na, c, tol, max_iter)
+        _arr(alpha_y, np.float64)[off:off + na + nb] = ay
+        _arr(rho, np.float64)[p] = r
+        _arr(obj, np.float64)[p] = o
+        _arr(n_iter, np.int32)[p] = it
+        _arr(status, np.int32)[p] = st
+
+
+def _k_svm_vote(self, dec, ld, rows, n_classes, class_labels, points, out, raster_w):
+    assert 2 <= n_classes <= 256 and ld >= n_classes * (n_classes - 1) // 2
+    win = vote(_mat(dec, ld, rows, n_classes * (n_classes - 1) // 2), n_classes)
+    lab = win.astype(np.uint8) if class_labels is None else _arr(class_labels, np.uint8)[win]
+    o = _arr(out, np.uint8)
+    if points is None:
+        o[:rows] = lab
+    else:
+        pts = _arr(points, np.int32)[: 2 * rows].reshape(rows, 2)
+        o[pts[:, 1].astype(np.int64) * raster_w + pts[:, 0]] = lab
+
+
+for _name, _fn in list(globals().items()):
+    if _name.startswith("_k_svm_"):
+        setattr(EmuBackend, _name[1:], _fn)
