@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("HYPEL_LIB_PATH") or os.path.join(_HERE, "csrc", "libh
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
 GEMM_BM = 128
-ABI_VERSION = 7  # include/hypel.h HYPEL_ABI_VERSION: a library built from other headers is refused at load time
+ABI_VERSION = 8  # include/hypel.h HYPEL_ABI_VERSION: a library built from other headers is refused at load time
 
 SEG_DTYPE = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("k", "<i4"), ("reserved", "<i4")])
 GROUP_DTYPE = np.dtype([("c_off", "<i8"), ("seg_begin", "<i4"), ("seg_count", "<i4"), ("rows", "<i4"),
@@ -45,6 +45,9 @@ TILE_PLAIN = 1  # include/hypel.h HYPEL_TILE_PLAIN: K-slice partial (no bias / a
 OUT_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2, np.dtype(np.uint8): 3}
 # include/hypel.h hypel_svm_pair_t, HYPEL_SVM_*
 SVM_PAIR_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<i4"), ("out_off", "<i8")])
+# include/hypel.h hypel_svm_job_t: a pair + the element offset of its plane of K + its C (hypel_svm_smo_grid)
+SVM_JOB_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<i4"), ("out_off", "<i8"),
+                          ("k_off", "<i8"), ("c", "<f8")])
 SVM_RBF, SVM_POLY = 0, 1
 SVM_CONVERGED, SVM_NOT_CONVERGED = 0, 1
 SVM_MAX_ITER_LIMIT = 1000000
@@ -167,6 +170,10 @@ SIGNATURES = {
     "svm_kernel_apply_f32": [_P, _I64, _I64, _I32, _I32, _F64, _F64, _I32, _P, _P],
     "svm_smo_ovo": [_P, _I64, _P, _I32, _I32, _F64, _F64, _I32, _P, _P, _P, _P, _P, _P],
     "svm_vote": [_P, _I64, _I64, _I32, _P, _P, _P, _I64],
+    "svm_kernel_planes_f32": [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _I64],
+    "svm_smo_grid": [_P, _I64, _P, _P, _I32, _I32, _F64, _I32, _P, _P, _P, _P, _P, _P],
+    "svm_scatter_coef_f32": [_P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P, _I64, _P],
+    "svm_vote_score": [_P, _I64, _I64, _I32, _I32, _I32, _P, _P],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

@@ -6,9 +6,14 @@ under --base_log_path, next to which utilities/latex_table_from_conf_set*.py exp
 Differences from the reference, all on purpose:
  - the estimator, which the reference picks by editing comments (:46-50), is a flag: --estimator svc_rbf (its GRSS2013
    line :49, gamma 1e-09, C 10000; --svc_gamma / --svc_c / --svc_tol) or svc_poly (its :48, degree 1, gamma "scale");
- - RandomForestClassifier (:46) and --hyperparamopt (:126-136) are refused by name: a forest's result depends on
-   scikit-learn's random stream and cannot be held to a fixture, and the grid search needs scikit-learn's
-   StratifiedShuffleSplit index stream on the machine that runs it;
+ - RandomForestClassifier (:46) is refused by name: a forest's result depends on scikit-learn's random stream and
+   cannot be held to a fixture;
+ - the reference's search (:126-136, GridSearchCV(SVC(), C x gamma) over StratifiedShuffleSplit(2, 0.1, 42)) runs on
+   the device under a NEW flag, --svc_grid (hypelcnn_amd.classic.model_selection): after the baseline fit and its three
+   files it searches the flattened training data, prints the reference's line and writes svc_grid_<loader>_run<i>.json;
+   --svc_grid_c / --svc_grid_gamma take lo:hi:n decades (defaults: the reference's -2:10:13 and -9:3:13),
+   --svc_grid_refit refits on the best cell and serves --fullscene from that estimator.  --hyperparamopt itself stays
+   refused: its contract in the reference is scikit-learn's own GridSearchCV object, which this project does not return;
  - --fullscene writes result_raw.tif / result_colorized.tif under --output_path, not the reference's hard-wired ".."
    (:111); patches are cut on the device (hypel_gather_patches_f32) and predicted in chunks sized from free memory,
    independent of --batch_size;
@@ -16,6 +21,7 @@ Differences from the reference, all on purpose:
 import argparse
 import json
 import os
+import sys
 import time
 
 import numpy
@@ -40,6 +46,14 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--svc_gamma", nargs="?", type=float, default=1e-09, help="RBF gamma (svc_rbf)")
     parser.add_argument("--svc_c", nargs="?", type=float, default=None, help="C (default: 10000 svc_rbf, 1 svc_poly)")
     parser.add_argument("--svc_tol", nargs="?", type=float, default=1e-3, help="Stopping tolerance of the solver")
+    parser.add_argument("--svc_grid", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, searches C x gamma on the device after the baseline fit (reference :126-136).")
+    # (a decade range such as -2:10:13 starts with '-' and is no number, so argparse would take it for an option:
+    #  main() hands these two flags over as --flag=value, see join_decade_values; a further flag of this form belongs there)
+    parser.add_argument("--svc_grid_c", type=str, default="-2:10:13", help="C decades lo:hi:n")
+    parser.add_argument("--svc_grid_gamma", type=str, default="-9:3:13", help="gamma decades lo:hi:n")
+    parser.add_argument("--svc_grid_refit", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, refits on the best cell; --fullscene then uses that estimator.")
 
 
 def create_estimator(flags, backend=None):
@@ -124,6 +138,47 @@ def perform_full_scene_classification(data_path, loader_name, neighborhood, esti
     return scene_as_image
 
 
+def parse_decades(text, flag):
+    """'lo:hi:n' -> numpy.logspace(lo, hi, n), the form of the reference's two ranges (:127-128)"""
+    try:
+        lo, hi, n = text.split(":")
+        lo, hi, n = float(lo), float(hi), int(n)
+    except ValueError:
+        raise ValueError(f"{flag} {text!r}: decades as lo:hi:n, e.g. -2:10:13") from None
+    if n < 1:
+        raise ValueError(f"{flag} {text!r}: n >= 1")
+    return numpy.logspace(lo, hi, n)
+
+
+last_grid_search = None  # the GridSearchSVC of the most recent --svc_grid run (also estimator.grid_search_)
+
+
+def perform_grid_search(flags, data, labels, run_index, backend=None):
+    """reference :126-136 on the device; the reference's print line, and the result as a JSON file next to the metrics."""
+    from hypelcnn_amd.classic.model_selection import GridSearchSVC, StratifiedShuffleSplit
+    global last_grid_search
+    param_grid = {"C": parse_decades(flags.svc_grid_c, "--svc_grid_c"),
+                  "gamma": parse_decades(flags.svc_grid_gamma, "--svc_grid_gamma")}
+    cv = StratifiedShuffleSplit(n_splits=2, test_size=0.1, random_state=42)
+    start_time = time.time()
+    grid = GridSearchSVC(param_grid, cv, tol=flags.svc_tol, refit=flags.svc_grid_refit, backend=backend).fit(data, labels)
+    print("Completed grid search(%.3f sec)" % (time.time() - start_time))
+    print("The best parameters are %s with a score of %0.2f" % (grid.best_params_, grid.best_score_))
+    res = grid.cv_results_
+    nan_to_none = lambda a: [None if numpy.isnan(v) else float(v) for v in a]  # noqa: E731 -- JSON has no NaN
+    out = {"params": res["params"], "mean_test_score": nan_to_none(res["mean_test_score"]),
+           "rank_test_score": res["rank_test_score"].tolist(), "best_index": grid.best_index_,
+           "best_params": grid.best_params_, "best_score": grid.best_score_, "n_splits": grid.n_splits_,
+           "unconverged_cells": [i for i, v in enumerate(res["mean_test_score"]) if numpy.isnan(v)]}
+    for split in range(grid.n_splits_):
+        out[f"split{split}_test_score"] = nan_to_none(res[f"split{split}_test_score"])
+    os.makedirs(flags.base_log_path, exist_ok=True)
+    with open(os.path.join(flags.base_log_path, f"svc_grid_{flags.loader_name}_run{run_index}.json"), "w") as grid_file:
+        json.dump(out, grid_file)
+    last_grid_search = grid
+    return grid
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     add_parse_cmds_for_loaders(parser)
@@ -133,13 +188,26 @@ def build_parser():
     return parser
 
 
+def join_decade_values(argv):
+    """`--svc_grid_c -2:10:13`: argparse takes a value that starts with '-' and is not a number for an option and leaves
+    the flag empty, so the two decade flags are handed over in their `--flag=value` form."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    out = []
+    while argv:
+        token = argv.pop(0)
+        if token in ("--svc_grid_c", "--svc_grid_gamma") and argv:
+            token += "=" + argv.pop(0)
+        out.append(token)
+    return out
+
+
 def main(argv=None, backend=None):
-    flags, _ = build_parser().parse_known_args(argv)
+    flags, _ = build_parser().parse_known_args(join_decade_values(argv))
     if flags.hyperparamopt:
         raise NotImplementedError(
-            "--hyperparamopt (reference classic_ml_trainer.py:126-136, GridSearchCV over StratifiedShuffleSplit) is not "
-            "built: it needs scikit-learn's split index stream on the machine that runs it; search on the host and pass "
-            "the result as --svc_gamma / --svc_c")
+            "--hyperparamopt (reference classic_ml_trainer.py:126-136) is not built: its contract is scikit-learn's own "
+            "GridSearchCV object; the same search, with the same grid and splits, runs on the device under --svc_grid "
+            "(--svc_grid_c / --svc_grid_gamma / --svc_grid_refit)")
     results = []
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)
@@ -155,6 +223,11 @@ def main(argv=None, backend=None):
         overall_accuracy, average_accuracy, kappa = scores(conf_matrix)
         print_output(estimator.get_params(), average_accuracy, conf_matrix, kappa, overall_accuracy, run_index,
                      flags.loader_name, flags.base_log_path)
+        if flags.svc_grid:
+            grid = perform_grid_search(flags, flatten_data(training.data), training.labels, run_index, backend)
+            if flags.svc_grid_refit:
+                estimator = grid.best_estimator_
+            estimator.grid_search_ = grid
         scene = None
         if flags.fullscene:
             scene = perform_full_scene_classification(flags.path, flags.loader_name, flags.neighborhood, estimator,

@@ -5,6 +5,11 @@
 //   kernel_apply   inner products -> kernel values in place, one streaming pass
 //   smo_ovo        libsvm's C-SVC SMO, one workgroup per class pair, all pairs in one launch
 //   vote           pairwise decisions -> labels by libsvm's voting rule, scattered into a raster or written in order
+// and the grid search over (C, gamma) (hypelcnn_amd/classic/model_selection.py):
+//   kernel_planes  inner products -> one plane of kernel values per gamma, out of place, one pass
+//   smo_grid       smo_ovo's solver on every (gamma, C, class pair) job of a chunk of the grid in one launch
+//   scatter_coef   the multipliers of one gamma's jobs -> a dense coefficient matrix over all training rows
+//   vote_score     vote's rule per (row, cell) -> the number of correct rows per cell
 #include "common.h"
 
 namespace {
@@ -108,6 +113,52 @@ __global__ void __launch_bounds__(SVM_THREADS) svm_kernel_apply_kernel(float* __
     }
 }
 
+// ---- G -> n_gamma planes of K, out of place ---------------------------------------------------------------------------
+// the grid search's form of kernel_apply: g is read once and left as it is, plane k = svm_kernel_value(g, gammas[k]).
+// The distance is the same expression for every gamma, so the compiler evaluates it once per element.
+template <bool VEC>
+__global__ void __launch_bounds__(SVM_THREADS) svm_kernel_planes_kernel(const float* __restrict__ g, int64_t ld,
+                                                                        int64_t rows, int cols,
+                                                                        const double* __restrict__ gammas, int n_gamma,
+                                                                        const double* __restrict__ rn,
+                                                                        const double* __restrict__ cn,
+                                                                        float* __restrict__ out, int64_t plane_stride) {
+    if constexpr (VEC) {
+        const int qpr = (cols + 3) >> 2;
+        const int64_t total = rows * qpr;
+        for (int64_t i = (int64_t)blockIdx.x * SVM_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * SVM_THREADS) {
+            const int64_t r = i / qpr;
+            const int c = (int)(i - r * qpr) << 2;
+            const int64_t at = r * ld + c;
+            const float4 v = *reinterpret_cast<const float4*>(g + at);
+            const float* e = reinterpret_cast<const float*>(&v);
+            const double a = rn[r];
+            double b[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) b[k] = c + k < cols ? cn[c + k] : 0.0;
+            for (int p = 0; p < n_gamma; ++p) {
+                const double gamma = gammas[p];
+                float4 w = v;  // (pad columns of the last quad: g's own values, as kernel_apply leaves them)
+                float* o = reinterpret_cast<float*>(&w);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c + k < cols) o[k] = svm_kernel_value(e[k], HYPEL_SVM_RBF, gamma, 0.0, 0, a, b[k]);
+                *reinterpret_cast<float4*>(out + p * plane_stride + at) = w;
+            }
+        }
+    } else {
+        const int64_t total = rows * cols;
+        for (int64_t i = (int64_t)blockIdx.x * SVM_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * SVM_THREADS) {
+            const int64_t r = i / cols;
+            const int c = (int)(i - r * cols);
+            const float v = g[r * ld + c];
+            const double a = rn[r], b = cn[c];
+            for (int p = 0; p < n_gamma; ++p)
+                out[p * plane_stride + r * ld + c] = svm_kernel_value(v, HYPEL_SVM_RBF, gammas[p], 0.0, 0, a, b);
+        }
+    }
+}
+
 // ---- SMO -----------------------------------------------------------------------------------------------------------
 struct MaxIdx {
     double v;
@@ -133,28 +184,25 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-// One workgroup = one class pair.  Element t of the pair is row a0 + t of K (y = +1) for t < na, row b0 + t - na
-// (y = -1) otherwise.  alpha / gradient / diagonal live in `st` (LDS or the caller's workspace, by the same pointer);
-// element t is only ever touched by thread t % SVM_THREADS, except for the two-variable update by thread 0, which the
-// barriers order.
-__global__ void __launch_bounds__(SVM_THREADS) svm_smo_ovo_kernel(const float* __restrict__ K, int64_t ldk,
-                                                                  const hypel_svm_pair_t* __restrict__ pairs, double C,
-                                                                  double tol, int max_iter, double* __restrict__ alpha_y,
-                                                                  double* __restrict__ rho_out, double* __restrict__ obj_out,
-                                                                  int32_t* __restrict__ iter_out,
-                                                                  int32_t* __restrict__ status_out, double* __restrict__ ws,
-                                                                  int use_lds) {
-    extern __shared__ double svm_lds[];
+// One workgroup = one pair problem (hypel_svm_smo_ovo: one class pair of a fit; hypel_svm_smo_grid: one class pair of one
+// (gamma, C) cell), solved by this one body so that the two entry points cannot drift.  Element t of the pair is row
+// a0 + t of K (y = +1) for t < na, row b0 + t - na (y = -1) otherwise.  alpha / gradient / diagonal live in `alpha`
+// (LDS or the caller's workspace, by the same pointer); element t is only ever touched by thread t % SVM_THREADS, except
+// for the two-variable update by thread 0, which the barriers order.  Results go to alpha_y[pr.out_off ...] and to
+// slot `out` of the per-problem arrays.
+__device__ __forceinline__ void svm_smo_solve(const float* __restrict__ K, int64_t ldk, const hypel_svm_pair_t pr,
+                                              double C, double tol, int max_iter, double* alpha,
+                                              double* __restrict__ alpha_y, double* __restrict__ rho_out,
+                                              double* __restrict__ obj_out, int32_t* __restrict__ iter_out,
+                                              int32_t* __restrict__ status_out, int64_t out) {
     __shared__ MaxIdx part_a[SVM_WAVES];
     __shared__ MaxIdx part_b[SVM_WAVES];
     __shared__ double part_g2[SVM_WAVES];
     __shared__ double upd[2];
     __shared__ double fin[6][SVM_WAVES];
 
-    const hypel_svm_pair_t pr = pairs[blockIdx.x];
     const int na = pr.na, l = pr.na + pr.nb;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double* alpha = use_lds ? svm_lds : ws + 3 * pr.out_off;
     double* G = alpha + l;
     double* QD = G + l;
     auto row_of = [&](int t) -> int64_t { return t < na ? (int64_t)pr.a0 + t : (int64_t)pr.b0 + (t - na); };
@@ -318,11 +366,43 @@ __global__ void __launch_bounds__(SVM_THREADS) svm_smo_ovo_kernel(const float* _
             n_free += fin[3][w];
             obj += fin[4][w];
         }
-        rho_out[blockIdx.x] = n_free > 0.0 ? sum_free / n_free : (ub + lb) / 2.0;
-        obj_out[blockIdx.x] = obj / 2.0;
-        iter_out[blockIdx.x] = iter;
-        status_out[blockIdx.x] = status;
+        rho_out[out] = n_free > 0.0 ? sum_free / n_free : (ub + lb) / 2.0;
+        obj_out[out] = obj / 2.0;
+        iter_out[out] = iter;
+        status_out[out] = status;
     }
+}
+
+__global__ void __launch_bounds__(SVM_THREADS) svm_smo_ovo_kernel(const float* __restrict__ K, int64_t ldk,
+                                                                  const hypel_svm_pair_t* __restrict__ pairs, double C,
+                                                                  double tol, int max_iter, double* __restrict__ alpha_y,
+                                                                  double* __restrict__ rho_out, double* __restrict__ obj_out,
+                                                                  int32_t* __restrict__ iter_out,
+                                                                  int32_t* __restrict__ status_out, double* __restrict__ ws,
+                                                                  int use_lds) {
+    extern __shared__ double svm_lds[];
+    const hypel_svm_pair_t pr = pairs[blockIdx.x];
+    svm_smo_solve(K, ldk, pr, C, tol, max_iter, use_lds ? svm_lds : ws + 3 * pr.out_off, alpha_y, rho_out, obj_out,
+                  iter_out, status_out, blockIdx.x);
+}
+
+// The grid search's launch: block b solves job order[b] (order NULL: job b) -- a pair of one (gamma, C) cell on that
+// gamma's plane of K, with that cell's C.  A job that reaches the cap ends NOT_CONVERGED like a pair of smo_ovo; nothing
+// a job does can stop another.
+__global__ void __launch_bounds__(SVM_THREADS) svm_smo_grid_kernel(const float* __restrict__ K, int64_t ldk,
+                                                                   const hypel_svm_job_t* __restrict__ jobs,
+                                                                   const int32_t* __restrict__ order, double tol,
+                                                                   int max_iter, double* __restrict__ alpha_y,
+                                                                   double* __restrict__ rho_out, double* __restrict__ obj_out,
+                                                                   int32_t* __restrict__ iter_out,
+                                                                   int32_t* __restrict__ status_out, double* __restrict__ ws,
+                                                                   int use_lds) {
+    extern __shared__ double svm_lds[];
+    const int64_t j = order ? order[blockIdx.x] : (int64_t)blockIdx.x;
+    const hypel_svm_job_t jb = jobs[j];
+    const hypel_svm_pair_t pr{jb.a0, jb.na, jb.b0, jb.nb, jb.out_off};
+    svm_smo_solve(K + jb.k_off, ldk, pr, jb.c, tol, max_iter, use_lds ? svm_lds : ws + 3 * jb.out_off, alpha_y, rho_out,
+                  obj_out, iter_out, status_out, j);
 }
 
 // ---- votes ---------------------------------------------------------------------------------------------------------
@@ -353,6 +433,79 @@ __global__ void __launch_bounds__(SVM_THREADS) svm_vote_kernel(const float* __re
         const uint8_t label = class_labels ? class_labels[best] : (uint8_t)best;
         if (points) out[(int64_t)points[2 * r + 1] * raster_w + points[2 * r]] = label;
         else out[r] = label;
+    }
+}
+
+// ---- grid search: multipliers -> dense coefficients, decisions -> correct rows per cell -----------------------------------
+// coef[r][ci * npp + p] = alpha_y of training row r in pair p of cell ci (0 where r is in neither class of the pair, and
+// in the pad columns p >= n_pairs); bias = -rho.  Every element of both outputs is written: no pre-zeroing.
+__global__ void __launch_bounds__(SVM_THREADS) svm_scatter_coef_kernel(const double* __restrict__ alpha_y,
+                                                                       const double* __restrict__ rho,
+                                                                       const hypel_svm_pair_t* __restrict__ pairs,
+                                                                       int n_pairs, int n_c, int64_t cell_stride, int l,
+                                                                       int npp, float* __restrict__ coef, int64_t ldc,
+                                                                       float* __restrict__ bias) {
+    const int n_cols = n_c * npp;
+    const int64_t total = (int64_t)l * n_cols;
+    const int64_t first = (int64_t)blockIdx.x * SVM_THREADS + threadIdx.x, step = (int64_t)gridDim.x * SVM_THREADS;
+    for (int64_t i = first; i < total; i += step) {
+        const int r = (int)(i / n_cols);
+        const int col = (int)(i - (int64_t)r * n_cols);
+        const int ci = col / npp, p = col - ci * npp;
+        float v = 0.0f;
+        if (p < n_pairs) {
+            const hypel_svm_pair_t pr = pairs[p];
+            const double* ay = alpha_y + ci * cell_stride + pr.out_off;
+            if (r >= pr.a0 && r < pr.a0 + pr.na) v = (float)ay[r - pr.a0];
+            else if (r >= pr.b0 && r < pr.b0 + pr.nb) v = (float)ay[pr.na + (r - pr.b0)];
+        }
+        coef[(int64_t)r * ldc + col] = v;
+    }
+    for (int64_t col = first; col < n_cols; col += step) {
+        const int ci = (int)col / npp, p = (int)col - ci * npp;
+        bias[col] = p < n_pairs ? (float)-rho[(int64_t)ci * n_pairs + p] : 0.0f;
+    }
+}
+
+// svm_vote_kernel's rule on cell blockIdx.y of dec[rows][n_cells * npp]; the rows whose winner is truth[r] are counted in
+// the block (wave shuffle, then LDS) and reach correct[cell] as one atomicAdd per block and cell
+__global__ void __launch_bounds__(SVM_THREADS) svm_vote_score_kernel(const float* __restrict__ dec, int64_t ld,
+                                                                     int64_t rows, int n_classes, int npp,
+                                                                     const int32_t* __restrict__ truth,
+                                                                     int32_t* __restrict__ correct) {
+    extern __shared__ uint8_t votes[];
+    __shared__ int part[SVM_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cell = blockIdx.y;
+    int hit = 0;
+    for (int64_t r0 = (int64_t)blockIdx.x * SVM_THREADS; r0 < rows; r0 += (int64_t)gridDim.x * SVM_THREADS) {
+        const int64_t r = r0 + tid;
+        if (r < rows) {  // (a thread reads only its own counters: no barrier inside)
+            for (int c = 0; c < n_classes; ++c) votes[c * SVM_THREADS + tid] = 0;
+            const float* d = dec + r * ld + (int64_t)cell * npp;
+            int p = 0;
+            for (int a = 0; a < n_classes; ++a)
+                for (int b = a + 1; b < n_classes; ++b, ++p) {
+                    const int w = d[p] > 0.0f ? a : b;
+                    votes[w * SVM_THREADS + tid] += 1;
+                }
+            int best = 0, best_n = votes[tid];
+            for (int c = 1; c < n_classes; ++c) {
+                const int n = votes[c * SVM_THREADS + tid];
+                if (n > best_n) best_n = n, best = c;
+            }
+            hit += best == truth[r];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) hit += __shfl_down(hit, o, 64);
+    if (lane == 0) part[wave] = hit;
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+#pragma unroll
+        for (int w = 0; w < SVM_WAVES; ++w) n += part[w];
+        if (n) atomicAdd(correct + cell, n);
     }
 }
 
@@ -417,5 +570,74 @@ extern "C" int hypel_svm_vote(const float* dec, int64_t ld, int64_t rows, int32_
                        (size_t)n_classes * SVM_THREADS, (hipStream_t)stream, dec, ld, rows, n_classes, class_labels, points,
                        out, raster_w);
     HYPEL_CHECK_LAUNCH("hypel_svm_vote");
+    return 0;
+}
+
+extern "C" int hypel_svm_kernel_planes_f32(const float* g, int64_t ld, int64_t rows, int32_t cols, int32_t kind,
+                                           const double* gammas, int32_t n_gamma, const double* row_norms,
+                                           const double* col_norms, float* out, int64_t plane_stride,
+                                           hypel_stream_t stream) {
+    HYPEL_REQUIRE(kind == HYPEL_SVM_RBF, "hypel_svm_kernel_planes_f32: rbf only (the grid search is over SVC(), whose "
+                                         "kernel is rbf; poly is hypel_svm_kernel_apply_f32's)");
+    HYPEL_REQUIRE(g && out && gammas && row_norms && col_norms && rows >= 0 && cols > 0 && ld >= cols && n_gamma > 0,
+                  "hypel_svm_kernel_planes_f32");
+    HYPEL_REQUIRE(plane_stride >= rows * ld, "hypel_svm_kernel_planes_f32: planes overlap");
+    const float* g_end = g + rows * ld;
+    const float* o_end = out + (n_gamma - 1) * plane_stride + rows * ld;
+    HYPEL_REQUIRE(o_end <= g || g_end <= out, "hypel_svm_kernel_planes_f32: out of place (g is left intact)");
+    if (rows == 0) return 0;
+    const bool vec = (ld & 3) == 0 && (plane_stride & 3) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const int64_t items = vec ? rows * ((cols + 3) / 4) : rows * (int64_t)cols;
+    const int grid = hypel_grid_1d(items, SVM_THREADS);
+    if (vec)
+        hipLaunchKernelGGL(svm_kernel_planes_kernel<true>, dim3(grid), dim3(SVM_THREADS), 0, (hipStream_t)stream, g, ld, rows,
+                           cols, gammas, n_gamma, row_norms, col_norms, out, plane_stride);
+    else
+        hipLaunchKernelGGL(svm_kernel_planes_kernel<false>, dim3(grid), dim3(SVM_THREADS), 0, (hipStream_t)stream, g, ld,
+                           rows, cols, gammas, n_gamma, row_norms, col_norms, out, plane_stride);
+    HYPEL_CHECK_LAUNCH("hypel_svm_kernel_planes_f32");
+    return 0;
+}
+
+extern "C" int hypel_svm_smo_grid(const float* k, int64_t ldk, const hypel_svm_job_t* jobs, const int32_t* order,
+                                  int32_t n_jobs, int32_t l_max, double tol, int32_t max_iter, double* alpha_y, double* rho,
+                                  double* obj, int32_t* n_iter, int32_t* status, double* ws, hypel_stream_t stream) {
+    HYPEL_REQUIRE(k && jobs && alpha_y && rho && obj && n_iter && status, "hypel_svm_smo_grid");
+    HYPEL_REQUIRE(n_jobs >= 0 && l_max > 0 && ldk > 0 && tol > 0.0, "hypel_svm_smo_grid");
+    HYPEL_REQUIRE(max_iter > 0 && max_iter <= HYPEL_SVM_MAX_ITER_LIMIT,
+                  "hypel_svm_smo_grid: the iteration cap is bounded (a solver must not spin on a shared device)");
+    if (n_jobs == 0) return 0;
+    const size_t need = (size_t)3 * l_max * sizeof(double);
+    const int use_lds = need <= (size_t)SVM_LDS_BYTES;
+    HYPEL_REQUIRE(use_lds || ws, "hypel_svm_smo_grid: a pair beyond the LDS budget needs the workspace");
+    hipLaunchKernelGGL(svm_smo_grid_kernel, dim3(n_jobs), dim3(SVM_THREADS), use_lds ? need : 0, (hipStream_t)stream, k, ldk,
+                       jobs, order, tol, max_iter, alpha_y, rho, obj, n_iter, status, ws, use_lds);
+    HYPEL_CHECK_LAUNCH("hypel_svm_smo_grid");
+    return 0;
+}
+
+extern "C" int hypel_svm_scatter_coef_f32(const double* alpha_y, const double* rho, const hypel_svm_pair_t* pairs,
+                                          int32_t n_pairs, int32_t n_c, int64_t cell_stride, int32_t l, int32_t npp,
+                                          float* coef, int64_t ldc, float* bias, hypel_stream_t stream) {
+    HYPEL_REQUIRE(alpha_y && rho && pairs && coef && bias, "hypel_svm_scatter_coef_f32");
+    HYPEL_REQUIRE(n_pairs > 0 && n_c > 0 && l > 0 && npp >= n_pairs && cell_stride >= 0, "hypel_svm_scatter_coef_f32");
+    HYPEL_REQUIRE((int64_t)n_c * npp <= INT32_MAX && ldc >= (int64_t)n_c * npp, "hypel_svm_scatter_coef_f32: ldc < n_c * npp");
+    hipLaunchKernelGGL(svm_scatter_coef_kernel, dim3(hypel_grid_1d((int64_t)l * n_c * npp, SVM_THREADS)), dim3(SVM_THREADS), 0,
+                       (hipStream_t)stream, alpha_y, rho, pairs, n_pairs, n_c, cell_stride, l, npp, coef, ldc, bias);
+    HYPEL_CHECK_LAUNCH("hypel_svm_scatter_coef_f32");
+    return 0;
+}
+
+extern "C" int hypel_svm_vote_score(const float* dec, int64_t ld, int64_t rows, int32_t n_classes, int32_t n_cells,
+                                    int32_t npp, const int32_t* truth, int32_t* correct, hypel_stream_t stream) {
+    HYPEL_REQUIRE(dec && truth && correct && rows >= 0, "hypel_svm_vote_score");
+    HYPEL_REQUIRE(n_classes >= 2 && n_classes <= 255,
+                  "hypel_svm_vote_score: 2..255 classes (256 byte counters per class + the block's partial sums fit 64 KB of LDS)");
+    HYPEL_REQUIRE(npp >= n_classes * (n_classes - 1) / 2, "hypel_svm_vote_score: npp < number of pairs");
+    HYPEL_REQUIRE(n_cells > 0 && n_cells <= 65535 && ld >= (int64_t)n_cells * npp, "hypel_svm_vote_score: ld < n_cells * npp");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(svm_vote_score_kernel, dim3(hypel_grid_1d(rows, SVM_THREADS, 64), n_cells), dim3(SVM_THREADS),
+                       (size_t)n_classes * SVM_THREADS, (hipStream_t)stream, dec, ld, rows, n_classes, npp, truth, correct);
+    HYPEL_CHECK_LAUNCH("hypel_svm_vote_score");
     return 0;
 }

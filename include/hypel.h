@@ -30,7 +30,7 @@ extern "C" {
 
 typedef void* hypel_stream_t; /* hipStream_t */
 
-#define HYPEL_ABI_VERSION 7  /* bump whenever a prototype, a struct layout or the meaning of a flag changes */
+#define HYPEL_ABI_VERSION 8  /* bump whenever a prototype, a struct layout or the meaning of a flag changes */
 
 /* activation codes (leaky_relu: HYPELCNNModel.py:39, DUALCNNModel.py:18, shadow_data_models.py:53;
  * relu: tf_slim default, CONCNNModel.py; sigmoid: HYPELCNNModel.py:93; tanh: shadow_data_models.py:86) */
@@ -648,11 +648,30 @@ int hypel_caps_mask_bwd(const float* gout, int64_t ldg, const float* labels, int
  * hypel_svm_vote: dec[r][p] (pair order (0,1), (0,2) ... as svm_predict_values) -> label: dec > 0 votes for the lower
  *   class of the pair, anything else for the higher; the FIRST class with the maximal count wins.  The label is
  *   class_labels[winner] (NULL: the winner's index), written to out[y * raster_w + x] for points[r] = (x, y) -- the
- *   whole-scene path, like hypel_argmax_scatter -- or to out[r] when points is NULL. */
+ *   whole-scene path, like hypel_argmax_scatter -- or to out[r] when points is NULL.
+ *
+ * Grid search over (C, gamma) (ABI 8; hypelcnn_amd/classic/model_selection.py).  The inner products of a split do not
+ * depend on gamma or C, every (gamma, C, class pair) problem is independent, and scoring stays on the device:
+ * hypel_svm_kernel_planes_f32: g (read once, left intact) -> plane p at out + p * plane_stride, same ld, = what
+ *   hypel_svm_kernel_apply_f32 writes in place for gammas[p] (a device array), bit for bit.  HYPEL_SVM_RBF only.
+ * hypel_svm_smo_grid: hypel_svm_smo_ovo's solver (the same device function), one workgroup per job.  A job is a class
+ *   pair (the hypel_svm_pair_t fields) on the plane of K at element offset k_off from k, with its own c.  Workgroup b
+ *   solves job order[b] (order NULL: job b), so the issue order is the caller's while alpha_y[out_off ...], rho[j],
+ *   obj[j], n_iter[j] and status[j] stay at the job's own index j; for the same K, pair, c, tol and max_iter they are
+ *   bit-identical to hypel_svm_smo_ovo's.  Same bounded loop, same LDS / ws rule (job j at ws + 3 * out_off); a job
+ *   at the cap ends with HYPEL_SVM_NOT_CONVERGED and stops nothing else.
+ * hypel_svm_scatter_coef_f32: the n_c cells of one gamma (cell ci: alpha_y + ci * cell_stride, pair p at the pair
+ *   table's out_off; rho[ci * n_pairs + p]) -> coef[l][n_c * npp] fp32 over ALL training rows, zero where a row is not
+ *   in the pair or its multiplier is zero and in the pad columns p >= n_pairs, and bias[n_c * npp] = -rho.  The
+ *   decisions of n_c cells are then one hypel_seg_gemm_f32: K_test plane [n_test][l] . coef + bias.
+ * hypel_svm_vote_score: hypel_svm_vote's rule on every (row, cell) of dec[rows][n_cells * npp]; correct[cell] += the
+ *   number of rows whose winner is truth[r] (class index; 2..255 classes).  Reduced in the block, one atomicAdd per block and cell;
+ *   the caller zeroes correct.  No labels are written. */
 enum { HYPEL_SVM_RBF = 0, HYPEL_SVM_POLY = 1 };
 enum { HYPEL_SVM_CONVERGED = 0, HYPEL_SVM_NOT_CONVERGED = 1 };
 #define HYPEL_SVM_MAX_ITER_LIMIT 1000000
 typedef struct { int32_t a0; int32_t na; int32_t b0; int32_t nb; int64_t out_off; } hypel_svm_pair_t;
+typedef struct { int32_t a0; int32_t na; int32_t b0; int32_t nb; int64_t out_off; int64_t k_off; double c; } hypel_svm_job_t;
 int hypel_svm_center_norms_f32(float* x, int64_t ld, int64_t rows, int32_t cols, const float* mean, double* norms,
                                hypel_stream_t stream);
 int hypel_svm_kernel_apply_f32(float* g, int64_t ld, int64_t rows, int32_t cols, int32_t kind, double gamma, double coef0,
@@ -662,6 +681,17 @@ int hypel_svm_smo_ovo(const float* k, int64_t ldk, const hypel_svm_pair_t* pairs
                       int32_t* status, double* ws, hypel_stream_t stream);
 int hypel_svm_vote(const float* dec, int64_t ld, int64_t rows, int32_t n_classes, const uint8_t* class_labels,
                    const int32_t* points, uint8_t* out, int64_t raster_w, hypel_stream_t stream);
+int hypel_svm_kernel_planes_f32(const float* g, int64_t ld, int64_t rows, int32_t cols, int32_t kind, const double* gammas,
+                                int32_t n_gamma, const double* row_norms, const double* col_norms, float* out,
+                                int64_t plane_stride, hypel_stream_t stream);
+int hypel_svm_smo_grid(const float* k, int64_t ldk, const hypel_svm_job_t* jobs, const int32_t* order, int32_t n_jobs,
+                       int32_t l_max, double tol, int32_t max_iter, double* alpha_y, double* rho, double* obj,
+                       int32_t* n_iter, int32_t* status, double* ws, hypel_stream_t stream);
+int hypel_svm_scatter_coef_f32(const double* alpha_y, const double* rho, const hypel_svm_pair_t* pairs, int32_t n_pairs,
+                               int32_t n_c, int64_t cell_stride, int32_t l, int32_t npp, float* coef, int64_t ldc,
+                               float* bias, hypel_stream_t stream);
+int hypel_svm_vote_score(const float* dec, int64_t ld, int64_t rows, int32_t n_classes, int32_t n_cells, int32_t npp,
+                         const int32_t* truth, int32_t* correct, hypel_stream_t stream);
 
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
