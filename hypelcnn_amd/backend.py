@@ -51,6 +51,7 @@ SVM_JOB_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<
 SVM_RBF, SVM_POLY = 0, 1
 SVM_CONVERGED, SVM_NOT_CONVERGED = 0, 1
 SVM_MAX_ITER_LIMIT = 1000000
+SCENE_RANK_WS_WORDS = 772  # include/hypel.h HYPEL_SCENE_RANK_WS_WORDS: uint32 of workspace per band
 COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
                              ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 
@@ -174,6 +175,10 @@ SIGNATURES = {
     "svm_smo_grid": [_P, _I64, _P, _P, _I32, _I32, _F64, _I32, _P, _P, _P, _P, _P, _P],
     "svm_scatter_coef_f32": [_P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P, _I64, _P],
     "svm_vote_score": [_P, _I64, _I64, _I32, _I32, _I32, _P, _P],
+    "scene_extrema": [_P, _I32, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I32],
+    "scene_rank_select_u16": [_P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P],
+    "scene_prepare_f32": [_P, _I32, _I64, _I64, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P],
+    "scene_masked_sums": [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I32],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

@@ -229,15 +229,42 @@ class SceneArrays:
     def __init__(self):
         self.casi = self.lidar = self.points = self.labels = None
         self.shape = None
+        self.scenes = None
 
-    def feed(self, data_set, targets, backend):
+    @staticmethod
+    def _resident(data_set, dev):
+        """(casi, lidar) of one scene in HBM: the tensors a device-prepared data set already holds
+        (common/device_scene.py -- no host round trip), else an upload of its NumPy arrays."""
+        if getattr(data_set, "casi_dev", None) is not None:
+            return data_set.casi_dev, data_set.lidar_dev
+        casi = torch.from_numpy(numpy.ascontiguousarray(data_set.casi, dtype=numpy.float32)).to(dev)
+        lidar = None
+        if data_set.lidar is not None:
+            lidar = torch.from_numpy(numpy.ascontiguousarray(data_set.lidar, dtype=numpy.float32)).to(dev)
+        return casi, lidar
+
+    def feed(self, data_set, targets, backend, seed=1234, stream=0):
         dev = backend.device
         self.backend = backend
-        casi = numpy.ascontiguousarray(data_set.casi, dtype=numpy.float32)
-        self.casi = torch.from_numpy(casi).to(dev)
-        self.lidar = None
-        if data_set.lidar is not None:
-            self.lidar = torch.from_numpy(numpy.ascontiguousarray(data_set.lidar, dtype=numpy.float32)).to(dev)
+        members = getattr(data_set, "_data_sets", None)
+        if members is not None:
+            # MultiDataSet (loader/GULFPORTALTDataLoader.py): every sample is cut from a member drawn per call.  The
+            # DISTINCT member scenes stay resident; `member_scene` maps a drawn member to its scene
+            distinct = []
+            for m in members:
+                if not any(m is d for d in distinct):
+                    distinct.append(m)
+            self.scenes = [self._resident(d, dev) for d in distinct]
+            self.member_scene = [next(i for i, d in enumerate(distinct) if d is m) for m in members]
+            # the member draws: seeded from the iterator's seed, its kind (`stream`) and the number of targets, so that
+            # the training, validation and test iterators of one run do not walk the same member sequence
+            entropy = numpy.random.SeedSequence([int(seed), int(stream), len(targets)])
+            self._member_rng = numpy.random.RandomState(entropy.generate_state(1)[0])
+            self.last_members = None
+            self.casi, self.lidar = self.scenes[0]
+        else:
+            self.scenes = None
+            self.casi, self.lidar = self._resident(data_set, dev)
         t = numpy.asarray(targets)
         self.points = torch.from_numpy(numpy.ascontiguousarray(t[:, :2], dtype=numpy.int32)).to(dev)
         self.labels = torch.from_numpy(numpy.ascontiguousarray(t[:, 2]).astype(numpy.int64)).to(dev)
@@ -248,6 +275,14 @@ class SceneArrays:
     def __len__(self):
         return 0 if self.points is None else self.points.shape[0]
 
+    def _gather_from(self, casi, lidar, pts, out):
+        from hypelcnn_amd.backend import Ref
+        hp, wp, cc = casi.shape
+        cl = 0 if lidar is None else int(lidar.shape[2])
+        self.backend.call("gather_patches_f32", Ref(casi.reshape(-1)), None if lidar is None else Ref(lidar.reshape(-1)),
+                          int(hp), int(wp), int(cc), cl, Ref(pts.reshape(-1)), int(pts.shape[0]), int(out.shape[1]),
+                          Ref(out.reshape(-1)))
+
     def gather(self, idx):
         from hypelcnn_amd.backend import Ref
         b = int(idx.shape[0])
@@ -256,6 +291,22 @@ class SceneArrays:
         out = torch.empty((b, p, p, c), dtype=torch.float32, device=self.casi.device)
         hp, wp, cc = self.casi.shape
         cl = 0 if self.lidar is None else int(self.lidar.shape[2])
+        if self.scenes is not None:
+            # one launch per distinct scene over that scene's share of the batch; the member of every sample is drawn
+            # on the host from the seeded generator (the reference's random.randint per get_data_point).  Per scene and
+            # batch this costs one small host-to-device copy (the rows of its share) and one index_copy_: accepted for
+            # a mode that exists for one loader; a second points table per scene would remove both
+            self.last_members = self._member_rng.randint(0, len(self.member_scene), size=b)
+            scene_of = numpy.asarray(self.member_scene)[self.last_members]
+            for k, (casi, lidar) in enumerate(self.scenes):
+                rows = numpy.nonzero(scene_of == k)[0]
+                if rows.size == 0:
+                    continue
+                where = torch.from_numpy(rows).to(out.device)
+                part = torch.empty((rows.size, p, p, c), dtype=torch.float32, device=out.device)
+                self._gather_from(casi, lidar, pts.index_select(0, where).contiguous(), part)
+                out.index_copy_(0, where, part)
+            return out, pts
         if self.casi_scale == 2:
             self.backend.call("gather_patches_2x_f32", Ref(self.casi.reshape(-1)), Ref(self.lidar.reshape(-1)), int(wp),
                               int(self.lidar.shape[1]), int(cc), cl, self.neighborhood, Ref(pts.reshape(-1)), b, int(p),
@@ -307,7 +358,7 @@ class BatchIterator:
         """Generator-style data set (importer/GeneratorImporter.py): patches are cut from the resident scene."""
         self.backend = backend
         self.arrays = SceneArrays()
-        self.arrays.feed(data_set, targets, backend)
+        self.arrays.feed(data_set, targets, backend, seed=self.seed, stream=1 if self.shuffle else 0)
         self._reset()
 
     def _reset(self):
@@ -855,6 +906,19 @@ def shuffle_test_data_using_ratio(train_set, test_data_ratio):
         tr, te = _stratified_split(train_set[:, 0:1], train_set[:, 2], test_size=test_data_ratio, random_state=0)
         test_set, train_set = train_set[te], train_set[tr]
     return test_set, train_set
+
+
+def load_shadow_map_common(data_set, neighborhood, shadow_file_name):
+    """reference :567-571: the shadow map under the scene's padding and the per-band lit / shadow ratio of `data_set`
+    (None without one).  A device-prepared scene (common/device_scene.py) is reduced where it lives."""
+    from hypelcnn_amd.common.tiff_io import imread
+    shadow_map = numpy.pad(imread(shadow_file_name), neighborhood, mode="symmetric")
+    if data_set is None:
+        return shadow_map, None
+    if getattr(data_set, "casi_dev", None) is not None:
+        from hypelcnn_amd.common.device_scene import device_shadow_ratio
+        return shadow_map, device_shadow_ratio(data_set, shadow_map)
+    return shadow_map, calculate_shadow_ratio(data_set.casi, shadow_map, numpy.logical_not(shadow_map).astype(int))
 
 
 def calculate_shadow_ratio(casi, shadow_map, shadow_map_inverse):

@@ -1,7 +1,7 @@
 """A DataLoader that synthesises a scene instead of reading TIFFs.
 
-The reference's loaders (GRSS2013/2018, GULFPORT, AVON) need the contest rasters and `tifffile`, neither of
-which exists in the build or test environment, so every benchmark and end-to-end test runs on this plugin.
+The file-backed loaders (GRSS2013/2018, GULFPORT, GULFPORTALT, AVON) need the contest rasters, which do not exist
+in the build or test environment, so the benchmarks and most end-to-end tests run on this plugin.
 `path` selects the geometry, e.g. "grss2013" (144 HSI bands + LiDAR, 15 classes), "grss2018" (48 + LiDAR, 20),
 "avon" (360 bands, no LiDAR, 2 classes), optionally followed by ":key=value" overrides
 (h, w, bands, classes, lidar, seed, samples, gan_ckpt=<npz checkpoint of a shadow GAN for the generator-based

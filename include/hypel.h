@@ -693,6 +693,36 @@ int hypel_svm_scatter_coef_f32(const double* alpha_y, const double* rho, const h
 int hypel_svm_vote_score(const float* dec, int64_t ld, int64_t rows, int32_t n_classes, int32_t n_cells, int32_t npp,
                          const int32_t* truth, int32_t* correct, hypel_stream_t stream);
 
+/* ---- scene preparation (BasicDataSet.__init__, common_nn_ops.py:45-72; AVONDataLoader's percentile clip) -------
+ * The source raster is `src` + element strides: sample (y, x, b) of the [h, w, bands] scene is src[y*sy + x*sx + b*sb],
+ * dtype HYPEL_DTYPE_* -- a transposed view of a file, or a window of its bands, is read in place.  Inputs are finite.
+ *
+ * hypel_scene_extrema: out_min[b] / out_max[b] (source dtype) = min / max over the scene of
+ *   (T)(min(v, clip[b]) - sub[b]), computed in the source dtype (integers wrap); clip and sub are optional [bands]
+ *   arrays of the source dtype.  ws: 2 * ws_slices * bands elements of the source dtype.
+ * hypel_scene_rank_select_u16: out_lo[b] / out_hi[b] = the values at ranks rank_lo <= rank_hi (0-based, ascending) of
+ *   band b's h*w samples, exactly.  ws: bands * HYPEL_SCENE_RANK_WS_WORDS uint32 (cleared by the call).
+ * hypel_scene_prepare_f32: out [h+2*pad][w+2*pad][bands] float32 = float32((T)(min(v, clip[b]) - lo[b])) / scale[b]
+ *   with v taken under numpy.pad(mode="symmetric") (any pad >= 0: the reflection has period 2h / 2w); clip, lo (source
+ *   dtype) and scale (float32) are optional; the division is IEEE, correctly rounded (scale 0 gives NaN / inf).
+ * hypel_scene_masked_sums: scene [hp][wp][bands] float32, map [hp][wp] uint8; sums[0*bands + b] = fp64 sum of band b
+ *   over map != 0 (what calculate_shadow_ratio keeps as "in shadow"; for a 0 / 1 shadow map this is map == 1, for a
+ *   map that marks shadow with another value, 255 say, only != 0 follows the reference), sums[1*bands + b] over
+ *   map == 0; counts[2] the
+ *   pixel counts.  One fixed summation order: two calls give identical bits.  ws: ws_slices * 2 * (bands + 1) doubles. */
+#define HYPEL_SCENE_RANK_WS_WORDS 772
+int hypel_scene_extrema(const void* src, int32_t dtype, int64_t h, int64_t w, int32_t bands, int64_t sy, int64_t sx,
+                        int64_t sb, const void* clip, const void* sub, void* out_min, void* out_max, void* ws,
+                        int32_t ws_slices, hypel_stream_t stream);
+int hypel_scene_rank_select_u16(const uint16_t* src, int64_t h, int64_t w, int32_t bands, int64_t sy, int64_t sx,
+                                int64_t sb, int64_t rank_lo, int64_t rank_hi, uint16_t* out_lo, uint16_t* out_hi,
+                                uint32_t* ws, hypel_stream_t stream);
+int hypel_scene_prepare_f32(const void* src, int32_t dtype, int64_t h, int64_t w, int32_t bands, int64_t sy, int64_t sx,
+                            int64_t sb, int32_t pad, const void* clip, const void* lo, const float* scale, float* out,
+                            hypel_stream_t stream);
+int hypel_scene_masked_sums(const float* scene, const uint8_t* map, int64_t hp, int64_t wp, int32_t bands, double* sums,
+                            int64_t* counts, double* ws, int32_t ws_slices, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
