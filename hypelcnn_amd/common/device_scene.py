@@ -3,8 +3,8 @@ everything BasicDataSet.__init__ does to them -- symmetric padding, per-band ext
 plus AVON's per-band percentile clip and the lit/shadow band sums happens where the patch gather will read the result.
 
 `DeviceBasicDataSet` is a BasicDataSet whose scene lives in `casi_dev` / `lidar_dev` (torch tensors on the backend's
-device); `.casi` / `.lidar` download it on first use for the host-side consumers (samplers, InMemoryImporter,
-get_data_point)."""
+device); `.casi` / `.lidar` download it on first use for the host-side consumers (InMemoryImporter, get_data_point,
+the host samplers -- gan_sampling_methods.get_sample_pairs_device pairs on the device instead)."""
 import numpy
 import torch
 

@@ -47,15 +47,22 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--task", nargs="?", type=int, default=0)
 
 
-def read_hsi_data(loader, data_set, shadow_map, pairing_method, sampling_method_map):
-    """reference gan_common.py:385-392"""
-    normal, shadow = sampling_method_map[pairing_method].get_sample_pairs(data_set, loader, shadow_map)
+def read_hsi_data(loader, data_set, shadow_map, pairing_method, sampling_method_map, backend=None):
+    """reference gan_common.py:385-392.  A scene prepared on the device (common/device_scene.py) is paired there when
+    the sampler can (gan_sampling_methods.get_sample_pairs_device): the pairs come back as device tensors of the casi
+    bands and the scene is never downloaded.  Every other data set or sampler takes the host path."""
+    from hypelcnn_amd.common.device_scene import DeviceBasicDataSet
+    sampler = sampling_method_map[pairing_method]
+    if isinstance(data_set, DeviceBasicDataSet) and hasattr(sampler, "get_sample_pairs_device"):
+        return sampler.get_sample_pairs_device(data_set, loader, shadow_map, backend or data_set.backend, hsi_only=True)
+    normal, shadow = sampler.get_sample_pairs(data_set, loader, shadow_map)
     return normal[..., :data_set.get_casi_band_count()], shadow[..., :data_set.get_casi_band_count()]
 
 
 class PairIterator:
     """load_op (reference :147-168): paired (normal, shadow) spectra resident on the device, shuffle_and_repeat over
-    `epoch` epochs, per-sample regulariser swap (perform_shadow_augmentation_random :171-182), batch(drop_remainder)."""
+    `epoch` epochs, per-sample regulariser swap (perform_shadow_augmentation_random :171-182), batch(drop_remainder).
+    `normal` / `shadow`: NumPy arrays, or float32 tensors -- those already on `device` are kept as they are."""
 
     def __init__(self, normal, shadow, batch_size, iteration_count, shadow_ratio, reg_support_rate, device, seed=1234,
                  backend=None):

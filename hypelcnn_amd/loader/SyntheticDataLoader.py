@@ -6,7 +6,9 @@ in the build or test environment, so the benchmarks and most end-to-end tests ru
 "avon" (360 bands, no LiDAR, 2 classes), optionally followed by ":key=value" overrides
 (h, w, bands, classes, lidar, seed, samples, gan_ckpt=<npz checkpoint of a shadow GAN for the generator-based
 shadow augmenters>, base_dir=<directory that get_model_base_dir reports, e.g. where TFRecord exports live>,
-dtype=uint16|int16|uint8 to quantise the scene to that integer dtype, as the contest rasters are stored; default float32).  Each class has its own smooth spectrum and height, pixels are
+dtype=uint16|int16|uint8 to quantise the scene to that integer dtype, as the contest rasters are stored; default float32,
+device=1 to prepare the scene on the compute device as the file-backed loaders do -- on `backend`, else a visible HIP
+device, else the host).  Each class has its own smooth spectrum and height, pixels are
 class spectrum + noise laid out in blobs, so that a classifier can actually learn the scene."""
 import numpy
 
@@ -44,6 +46,7 @@ class SyntheticDataLoader(DataLoader):
             cfg[k] = v if k in ("gan_ckpt", "base_dir", "dtype") else (float(v) if k == "samples" else int(v))
         self.cfg = cfg
         self._targets = None
+        self.backend = None  # device=1: scene preparation on this backend, else a visible HIP device, else the host
 
     def _scene(self):
         c = self.cfg
@@ -85,8 +88,13 @@ class SyntheticDataLoader(DataLoader):
                                        normalize=normalize)
             data_set.shadow_creator_dict = {}
             return data_set
-        data_set = BasicDataSet(shadow_creator_dict=None, casi=casi, lidar=lidar, neighborhood=neighborhood,
-                                normalize=normalize)
+        if self.cfg.get("device"):
+            from hypelcnn_amd.common.device_scene import make_basic_data_set
+            data_set = make_basic_data_set(self.backend, shadow_creator_dict=None, casi=casi, lidar=lidar,
+                                           neighborhood=neighborhood, normalize=normalize)
+        else:
+            data_set = BasicDataSet(shadow_creator_dict=None, casi=casi, lidar=lidar, neighborhood=neighborhood,
+                                    normalize=normalize)
         # the shadow augmenters the reference's loaders register (loader/GRSS2013DataLoader.py:24-34): the per-band
         # ratio struct always, the generator-based ones when a trained shadow GAN checkpoint is given
         from functools import partial
@@ -111,6 +119,9 @@ class SyntheticDataLoader(DataLoader):
         if getattr(self, "_shadow_map", None) is None:
             self._scene()
         shadow_map = numpy.pad(self._shadow_map, neighborhood, mode="symmetric")
+        if getattr(data_set, "casi_dev", None) is not None:
+            from hypelcnn_amd.common.device_scene import device_shadow_ratio
+            return shadow_map, device_shadow_ratio(data_set, shadow_map)
         ratio = None if data_set is None else calculate_shadow_ratio(
             data_set.casi, shadow_map, numpy.logical_not(shadow_map).astype(int))
         return shadow_map, ratio
@@ -127,6 +138,13 @@ class SyntheticDataLoader(DataLoader):
         n_test = max(1, int(n_used * test_data_ratio))
         return SampleSet(validation_targets=rows[:n_val], test_targets=rows[n_val:n_val + n_test],
                          training_targets=rows[n_val + n_test:])
+
+    def read_targets(self, target_image_path):
+        """The file-backed loaders read a class raster here (TargetBasedSampler asks for the classification result
+        under the data directory); the synthetic scene's own label map stands in for whichever file is named."""
+        if getattr(self, "_labels", None) is None:
+            self._labels = self._scene()[2]
+        return read_targets_from_image(self._labels, self.get_class_count())
 
     def get_class_count(self):
         return range(0, self.cfg["classes"])

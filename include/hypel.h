@@ -723,6 +723,36 @@ int hypel_scene_prepare_f32(const void* src, int32_t dtype, int64_t h, int64_t w
 int hypel_scene_masked_sums(const float* scene, const uint8_t* map, int64_t hp, int64_t wp, int32_t bands, double* sums,
                             int64_t* counts, double* ws, int32_t ws_slices, hypel_stream_t stream);
 
+/* ---- shadow / lit pixel pairing (gan/gan_sampling_methods.py; csrc/pairs.hip) ---------------------------------------
+ * What the samplers do to the shadow map, where the scene lives: the map is a uint8 [h][w] raster in HBM, the results
+ * are the int32 [n][2] = (x, y) point lists hypel_gather_patches_f32 cuts the pairs from.  No atomics: two calls
+ * write identical bytes.
+ *
+ * hypel_mask_dilate_l1_u8 replaces ndimage.binary_dilation(shadow_map, iterations=radius) (NeighborhoodBasedSampler,
+ *   :29-30): out[y][x] = 1 where some pixel with map != 0 lies within L1 distance `radius` (>= 1) of (x, y), else 0;
+ *   pixels outside the raster count as 0.  Two launches whatever the radius: a row pass leaves the horizontal distance
+ *   to the nearest set pixel in ws (int32 [h][w]), a column pass takes min(|dy| + ws[y + dy][x]) <= radius.
+ * hypel_pair_masks_u8 replaces the branch of the samplers' pixel loops (:41-46, :72-77): shadow[i] = map[i] == 1;
+ *   lit[i] = map[i] != 1 when reach and margin are NULL (RandomBasedSampler), else
+ *   reach[i] && !margin[i] && map[i] != 1 with reach / margin the dilations by neighborhood_size / margin (the ring the
+ *   reference forms by a subtraction, visited by the `elif`); n = h * w.
+ * hypel_mask_compact_points_i32 replaces the index bookkeeping of those loops (:36-46, :67-77): points[k] = (x, y) of
+ *   the k-th pixel with mask != 0 in row-major scan order, for k < capacity (rows past `capacity` are not written);
+ *   *count = the number of such pixels.  h * w < 2^31.  ws: ceil(h * w / HYPEL_COMPACT_TILE) int32.  Per-tile counts,
+ *   a prefix sum over the tiles, then a scatter by ballot rank.
+ * hypel_points_expand_i32 replaces numpy.repeat(..., repeats, axis=0) and the remainder vstack (RandomBasedSampler
+ *   :80-82, TargetBasedSampler :171-175) on the point list: out[i] = points[i / repeat] for i < n * repeat, then
+ *   out[n * repeat + j] = points[j] for j < remainder <= n.  repeat >= 0; n * repeat + remainder > 0. */
+#define HYPEL_COMPACT_TILE 4096
+int hypel_mask_dilate_l1_u8(const uint8_t* map, int64_t h, int64_t w, int32_t radius, uint8_t* out, int32_t* ws,
+                            hypel_stream_t stream);
+int hypel_pair_masks_u8(const uint8_t* map, const uint8_t* reach, const uint8_t* margin, int64_t n, uint8_t* shadow,
+                        uint8_t* lit, hypel_stream_t stream);
+int hypel_mask_compact_points_i32(const uint8_t* mask, int64_t h, int64_t w, int32_t* points, int64_t capacity,
+                                  int32_t* count, int32_t* ws, hypel_stream_t stream);
+int hypel_points_expand_i32(const int32_t* points, int64_t n, int32_t repeat, int64_t remainder, int32_t* out,
+                            hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
