@@ -53,6 +53,8 @@ SVM_CONVERGED, SVM_NOT_CONVERGED = 0, 1
 SVM_MAX_ITER_LIMIT = 1000000
 SCENE_RANK_WS_WORDS = 772  # include/hypel.h HYPEL_SCENE_RANK_WS_WORDS: uint32 of workspace per band
 COMPACT_TILE = 4096  # include/hypel.h HYPEL_COMPACT_TILE: pixels per int32 of hypel_mask_compact_points_i32's workspace
+SUMMARY_SLICE = 32768  # include/hypel.h HYPEL_SUMMARY_SLICE: elements per slice of hypel_tensor_summary_f32
+SUMMARY_MAX_LIMITS = 2048  # include/hypel.h HYPEL_SUMMARY_MAX_LIMITS
 COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
                              ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 
@@ -184,6 +186,7 @@ SIGNATURES = {
     "pair_masks_u8": [_P, _P, _P, _I64, _P, _P],
     "mask_compact_points_i32": [_P, _I64, _I64, _P, _I64, _P, _P],
     "points_expand_i32": [_P, _I64, _I32, _I64, _P],
+    "tensor_summary_f32": [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _I32],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

@@ -10,7 +10,8 @@
   * StopAtStepHook(last_step=required_steps - 1), NaN-loss guard (stop, do not raise).
   * Checkpoints every `save_checkpoint_steps` into log_dir (keep 20), keyed by the TF variable names
     (nn_core/*, global_step, training_optimizer/*); the newest one is restored on start = implicit resume.
-  * Summaries: JSON lines in log_dir/summaries.jsonl instead of TensorBoard event files.
+  * Summaries: JSON lines in log_dir/summaries.jsonl; with --tensorboard_events also a TensorBoard event file
+    (common/tb_events.py) under the reference's tags, the --log_model_params histograms computed on the device.
 """
 import glob
 import json
@@ -34,8 +35,12 @@ def set_run_seed(seed=1234):
 
 
 def add_classification_summaries(cross_entropy, learning_rate, log_all_model_variables, testing_nn_params,
-                                 validation_nn_params):
-    """Returns a callable producing the summary record the reference writes to TensorBoard (:16-28)."""
+                                 validation_nn_params, tensorboard_events=False):
+    """Returns a callable producing the summary record the reference writes to TensorBoard (:16-28).
+    tensorboard_events: run_monitored_session also writes every record as an Event; the variable histograms of
+    log_all_model_variables then come from the device (record["histograms"], kept out of the JSON line) and
+    `variable_norms` is the square root of their sum_squares, so no variable is copied to the host."""
+    summarizer = []
 
     def collect(sess, step):
         rec = {"step": int(step), "training_cross_entropy": cross_entropy.eval(),
@@ -47,23 +52,65 @@ def add_classification_summaries(cross_entropy, learning_rate, log_all_model_var
             m = validation_nn_params.metrics
             rec.update(validation_overall_accuracy=m.accuracy, validation_average_accuracy=m.mean_per_class_accuracy,
                        validation_kappa=m.kappa, validation_confusion=m.confusion.tolist())
-        if log_all_model_variables:
+        if log_all_model_variables and tensorboard_events:
+            if is_chief():
+                if not summarizer:
+                    from hypelcnn_amd.common.device_summary import VariableSummarizer
+                    summarizer.append(VariableSummarizer(sess))
+                histograms = summarizer[0].run()
+                rec["variable_norms"] = {n: float(numpy.sqrt(histograms[n]["sum_squares"]))
+                                         for n in sess.variable_names()}
+                rec["histograms"] = (summarizer[0].limits, {n: histograms[n] for n in sess.variable_names()})
+        elif log_all_model_variables:
             rec["variable_norms"] = {n: float(numpy.linalg.norm(sess.get_variable(n))) for n in sess.variable_names()}
         return rec
 
+    collect.tensorboard_events = bool(tensorboard_events)
     return collect
 
 
+SCALAR_TAGS = ("training_cross_entropy", "training_learning_rate", "test_overall_accuracy",
+               "validation_overall_accuracy", "validation_average_accuracy", "validation_kappa")
+CONFUSION_TAGS = ("test_confusion", "validation_confusion")
+TEXT_TAGS = ("flags", "algorithm_params")
+
+
+def record_to_summary_values(record, histograms=None):
+    """The Summary.Value messages of one summary record under the reference's tags: scalars, the confusion matrices as
+    [C, C] string tensors, the start-up texts as <pre>...</pre> (common_nn_ops.py:588-600), one histogram per variable.
+    A variable with non-finite elements gets a printed line instead of a histogram (TensorFlow's op raises there)."""
+    from hypelcnn_amd.common import tb_events
+    values = [tb_events.scalar_value(tag, record[tag]) for tag in SCALAR_TAGS if tag in record]
+    values += [tb_events.matrix_text_value(tag, record[tag]) for tag in CONFUSION_TAGS if tag in record]
+    values += [tb_events.text_value(tag, "<pre>" + record[tag] + "</pre>") for tag in TEXT_TAGS if tag in record]
+    if histograms is not None:
+        limits, per_variable = histograms
+        for name, h in per_variable.items():
+            if h["nonfinite"]:
+                print(f"Histogram of {name} skipped at step {record.get('step', 0)}: {h['nonfinite']} non-finite values")
+                continue
+            values.append(tb_events.histogram_value(name, h["min"], h["max"], h["num"], h["sum"], h["sum_squares"],
+                                                    limits, h["buckets"]))
+    return values
+
+
 class SummaryWriter:
-    def __init__(self, log_dir):
+    def __init__(self, log_dir, tensorboard_events=False):
         self.path = os.path.join(log_dir, "summaries.jsonl") if log_dir and is_chief() else None
+        self.events = None
         if self.path:
             os.makedirs(log_dir, exist_ok=True)
+            if tensorboard_events:
+                from hypelcnn_amd.common.tb_events import EventFileWriter
+                self.events = EventFileWriter(log_dir)
 
     def add(self, record):
+        histograms = record.pop("histograms", None)
         if self.path:
             with open(self.path, "a") as f:
                 f.write(json.dumps(record) + "\n")
+        if self.events is not None:
+            self.events.add_event(record.get("step", 0), record_to_summary_values(record, histograms))
 
 
 def latest_checkpoint(log_dir):
@@ -174,7 +221,7 @@ def run_monitored_session(cross_entropy, log_dir, class_range, save_checkpoint_s
                           testing_tensor, validation_nn_params, validation_tensor, importer, flags_as_json_str,
                           alg_params_as_json_str, summary_fn=None):
     sess = train_step.ctx.session()
-    writer = SummaryWriter(log_dir)
+    writer = SummaryWriter(log_dir, getattr(summary_fn, "tensorboard_events", False))
     ckpt = latest_checkpoint(log_dir)
     if ckpt is not None:
         restore_checkpoint(sess, ckpt)

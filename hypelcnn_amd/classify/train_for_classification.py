@@ -59,7 +59,7 @@ def perform_an_episode(flags, algorithm_params, model, base_log_path, backend=No
     if not flags.perform_validation:
         validation_nn_params = None
     summary_fn = add_classification_summaries(cross_entropy, learning_rate, flags.log_model_params, testing_nn_params,
-                                              validation_nn_params)
+                                              validation_nn_params, tensorboard_events=flags.tensorboard_events)
     start = time.time()
     result = run_monitored_session(cross_entropy, base_log_path, class_range, flags.save_checkpoint_steps,
                                    flags.validation_steps, train_step, required_steps, augmentation_info,
@@ -90,6 +90,7 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--validation_steps", nargs="?", type=int, default=40000)
     parser.add_argument("--all_data_shuffle_ratio", nargs="?", type=float, default=None)
     parser.add_argument("--log_model_params", nargs="?", const=True, type=b, default=False)
+    parser.add_argument("--tensorboard_events", nargs="?", const=True, type=b, default=False)
 
 
 def get_log_suffix(flags):

@@ -89,12 +89,16 @@ def _open(path, mode, compressed):
     return gzip.open(path, mode) if compressed else open(path, mode)
 
 
+def write_record(f, payload):
+    head = struct.pack("<Q", len(payload))
+    f.write(head + struct.pack("<I", mask_crc(crc32c(head))) + payload + struct.pack("<I", mask_crc(crc32c(payload))))
+
+
 def write_records(path, payloads, compressed=False):
     n = 0
     with _open(path, "wb", compressed) as f:
         for p in payloads:
-            head = struct.pack("<Q", len(p))
-            f.write(head + struct.pack("<I", mask_crc(crc32c(head))) + p + struct.pack("<I", mask_crc(crc32c(p))))
+            write_record(f, p)
             n += 1
     return n
 

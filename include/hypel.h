@@ -753,6 +753,32 @@ int hypel_mask_compact_points_i32(const uint8_t* mask, int64_t h, int64_t w, int
 int hypel_points_expand_i32(const int32_t* points, int64_t n, int32_t repeat, int64_t remainder, int32_t* out,
                             hypel_stream_t stream);
 
+/* ---- tensor summaries (tf.summary.histogram of the model variables; csrc/summary.hip) -------------------------------
+ * hypel_tensor_summary_f32 summarises n_segs float32 tensors that are segments of ONE device buffer, where they live:
+ * segment s is base[table[2s] ... table[2s] + table[2s + 1]) (int64 element offset >= 0 and size >= 0, any alignment,
+ * any order, gaps allowed).  Per segment, with TensorFlow's histogram::Histogram::Add applied to every FINITE element
+ * cast to double:
+ *   stats[5s + 0..4] = min, max, num, sum, sum_squares (min / max start at +DBL_MAX / -DBL_MAX, num counts the finite
+ *                      elements);
+ *   nonfinite[s]     = the number of NaN / +-Inf elements, which take part in nothing else;
+ *   buckets[s * n_limits + b] = the number of finite elements v with b = upper_bound(limits, v), the index of the first
+ *                      limit strictly greater than v (clamped to n_limits - 1; TensorFlow's table ends in DBL_MAX).
+ * limits: n_limits ascending doubles in device memory, 1 <= n_limits <= HYPEL_SUMMARY_MAX_LIMITS.  The bucket of an
+ * element is estimated from its logarithm for TensorFlow's default table (1e-12 * 1.1^k, mirrored around 0.0) and then
+ * corrected by comparisons against the table itself, so it is exact for ANY ascending table (slower for others).
+ * Counts, min, max, num and nonfinite are exact.  sum / sum_squares are fp64 sums over a fixed partition (slices of
+ * HYPEL_SUMMARY_SLICE elements, one block each) reduced in a fixed order, no floating-point atomics: two calls on the
+ * same input give identical bits.
+ * ws: HYPEL_SUMMARY_WS_DOUBLES(n_segs, ws_slices) doubles; ws_slices = the sum over the segments of
+ * ceil(size / HYPEL_SUMMARY_SLICE), which the caller knows from the table it built.  A table that needs another
+ * number of slices than ws_slices is refused on the device: every nonfinite[s] is then -1 and nothing else is valid. */
+#define HYPEL_SUMMARY_SLICE 32768
+#define HYPEL_SUMMARY_MAX_LIMITS 2048
+#define HYPEL_SUMMARY_WS_DOUBLES(n_segs, ws_slices) ((int64_t)(n_segs) + 1 + 6 * (int64_t)(ws_slices))
+int hypel_tensor_summary_f32(const float* base, const int64_t* table, int32_t n_segs, const double* limits,
+                             int32_t n_limits, double* stats, int64_t* nonfinite, int64_t* buckets, double* ws,
+                             int32_t ws_slices, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
