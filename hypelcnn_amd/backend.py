@@ -55,6 +55,11 @@ SCENE_RANK_WS_WORDS = 772  # include/hypel.h HYPEL_SCENE_RANK_WS_WORDS: uint32 o
 COMPACT_TILE = 4096  # include/hypel.h HYPEL_COMPACT_TILE: pixels per int32 of hypel_mask_compact_points_i32's workspace
 SUMMARY_SLICE = 32768  # include/hypel.h HYPEL_SUMMARY_SLICE: elements per slice of hypel_tensor_summary_f32
 SUMMARY_MAX_LIMITS = 2048  # include/hypel.h HYPEL_SUMMARY_MAX_LIMITS
+# include/hypel.h HYPEL_FOREST_*: rows sorted per column for the bin edges, edges per column, classes of the LDS
+# histogram, depth cap of the level loop
+FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = 16384, 255, 32, 64
+# include/hypel.h hypel_forest_node_t: a leaf has left = -1 - (its row of the leaf table)
+FOREST_NODE_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<f4"), ("left", "<i4"), ("right", "<i4")])
 COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
                              ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 
@@ -187,6 +192,14 @@ SIGNATURES = {
     "mask_compact_points_i32": [_P, _I64, _I64, _P, _I64, _P, _P],
     "points_expand_i32": [_P, _I64, _I32, _I64, _P],
     "tensor_summary_f32": [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _I32],
+    "forest_bin_edges_f32": [_P, _I64, _I64, _I32, _P, _I32, _P, _P],
+    "forest_bin_u8": [_P, _I64, _I64, _I32, _P, _P, _P, _I64],
+    "forest_split_hist": [_P, _I64, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P],
+    "forest_split_apply": [_P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32,
+                           _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "forest_predict_rows": [_P, _I64, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I64, _P],
+    "forest_predict_scene": [_P, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P,
+                             _I64],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

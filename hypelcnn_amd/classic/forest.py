@@ -1,0 +1,337 @@
+"""Random forest of histogram trees grown and served on the device (reference classify/classic_ml_trainer.py:46,
+`RandomForestClassifier(n_estimators=50, max_features=int(2 * sqrt(144)))`; include/hypel.h, hypel_forest_*).
+
+fit: every column is quantised once to at most 256 bins (hypel_forest_bin_edges_f32, hypel_forest_bin_u8); all trees
+then grow together, level by level: hypel_forest_split_hist scores every (active node, candidate column) over bin
+boundaries with integer class histograms, hypel_forest_split_apply picks the best, writes the node and partitions the
+node's rows.  The host reads one counter per level to size the next launch; the loop is bounded by the depth cap.
+Randomness is the project's data-side rule -- a seeded host generator, small device tables:
+numpy.random.Generator(PCG64(seed)) draws the bootstrap counts, the row permutation of the edge subsample and each
+level's candidate table (in active-node order, without replacement per node).  Nothing of scikit-learn's stream is
+reproduced.  On purpose, unlike scikit-learn: thresholds lie on bin edges, candidates are not redrawn when all of a node's
+are invalid, growth is level-wise (node numbers are breadth-first per tree).
+
+predict: hypel_forest_predict_rows walks every tree per row and averages the leaf rows in fp64.  predict_scene walks the
+trees straight on the padded scene (hypel_forest_predict_scene) where the data set has one resolution, else it cuts
+patches chunk by chunk and uses the row kernel.  There is no CPU fallback: the `backend` argument exists so that the
+tests can run this file on their numpy emulation of the same entry points."""
+import numpy as np
+import torch
+
+from hypelcnn_amd.backend import (FOREST_EDGE_ROWS, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH, FOREST_MAX_EDGES,
+                                  FOREST_NODE_DTYPE, Ref)
+
+
+def _round_up(v, m):
+    return (int(v) + m - 1) // m * m
+
+
+def round_down_f32(thr):
+    """The largest float32 not above each float64 threshold: for a float32 x, x <= thr64 holds exactly when x <= that
+    value (rounding to nearest can land on the sample above the threshold and flip it)."""
+    thr = np.asarray(thr, np.float64)
+    t32 = thr.astype(np.float32)
+    above = t32.astype(np.float64) > thr
+    t32[above] = np.nextafter(t32[above], np.float32(-np.inf))
+    return t32
+
+
+def scene_features(feature, p, wp, cc, cl):
+    """Patch feature index -> hypel_forest_predict_scene's (element offset, array) code; leaves (feature < 0) keep 0."""
+    f = np.maximum(np.asarray(feature, np.int64), 0)
+    c = cc + cl
+    pix, ch = f // c, f % c
+    pixel = (pix // p) * wp + pix % p
+    code = np.where(ch < cc, 2 * (pixel * cc + ch), 2 * (pixel * cl + ch - cc) + 1)
+    return np.where(np.asarray(feature) < 0, 0, code).astype(np.int32)
+
+
+class ForestClassifier:
+    """The subset of sklearn.ensemble.RandomForestClassifier the reference uses, on the device.
+
+    Fitted attributes: classes_, n_features_in_, and the flat node arrays over all trees -- tree t owns nodes
+    tree_offsets_[t] .. tree_offsets_[t + 1]; feature_ (-1: leaf), threshold_ (float32), left_ / right_ (tree-local
+    child numbers like scikit-learn's children_left / children_right, -1: leaf), leaf_ (row of leaf_value_, -1: inner
+    node), value_ [n_nodes, n_classes] (class weight fractions), leaf_value_ = value_ of the leaves; after fit also
+    threshold_bin_, node_count_ (unique rows) and node_weight_."""
+
+    def __init__(self, n_estimators=50, max_features=24, bootstrap=True, max_depth=None, n_bins=256, seed=0,
+                 backend=None, chunk_rows=None):
+        if int(n_estimators) < 1:
+            raise ValueError(f"ForestClassifier(n_estimators={n_estimators}): at least one tree")
+        if not (max_features is None or max_features == "sqrt" or
+                (not isinstance(max_features, str) and int(max_features) >= 1)):
+            raise ValueError(f"ForestClassifier(max_features={max_features!r}): a positive int, 'sqrt' or None")
+        if not 2 <= int(n_bins) <= FOREST_MAX_EDGES + 1:
+            raise ValueError(f"ForestClassifier(n_bins={n_bins}): 2..{FOREST_MAX_EDGES + 1}")
+        if max_depth is not None and not 0 <= int(max_depth) <= FOREST_MAX_DEPTH:
+            raise ValueError(f"ForestClassifier(max_depth={max_depth}): 0..{FOREST_MAX_DEPTH} (the level loop is bounded)")
+        self.n_estimators, self.max_features, self.bootstrap = int(n_estimators), max_features, bool(bootstrap)
+        self.max_depth, self.n_bins, self.seed = None if max_depth is None else int(max_depth), int(n_bins), int(seed)
+        self._be = backend
+        self.chunk_rows = chunk_rows  # rows per serving launch (default: 256 MB of rows)
+
+    def _level_done(self, level, active, n_active, cand, score, best_bin, valid):
+        """Called after every level of fit with the level's device tables (a subclass may copy them); nothing here."""
+
+    def _nodes_renumbered(self, model_node):
+        """Called once per fit: model_node[device node number] = the node's place in the fitted arrays."""
+
+    def get_params(self):
+        return {"bootstrap": self.bootstrap, "max_depth": self.max_depth, "max_features": self.max_features,
+                "n_bins": self.n_bins, "n_estimators": self.n_estimators, "seed": self.seed}
+
+    def _backend(self):
+        if self._be is None:
+            from hypelcnn_amd.backend import HipBackend
+            self._be = HipBackend()
+        return self._be
+
+    def _rows(self, X):
+        """[n, features] (numpy or tensor) -> flat fp32 device tensor [n, features]"""
+        be = self._backend()
+        t = torch.from_numpy(np.ascontiguousarray(X)) if isinstance(X, np.ndarray) else X
+        if t.dim() != 2:
+            raise ValueError(f"ForestClassifier: X must be [rows, features], got {tuple(t.shape)}")
+        return t.to(be.device).float().contiguous().view(-1), int(t.shape[0]), int(t.shape[1])
+
+    def _resolve_max_features(self, f):
+        if self.max_features is None:
+            return f
+        if self.max_features == "sqrt":
+            return max(1, int(np.sqrt(f)))
+        return min(int(self.max_features), f)
+
+    def _check_classes(self, classes):
+        n_cls = len(classes)
+        if n_cls > 255:
+            raise ValueError(f"ForestClassifier: {n_cls} classes; labels are written as uint8 (the scene raster of "
+                             f"--fullscene is uint8), so at most 255 classes")
+        if n_cls > FOREST_MAX_CLASSES:
+            raise ValueError(f"ForestClassifier: {n_cls} classes; the class histogram of a node lives in LDS, at most "
+                             f"{FOREST_MAX_CLASSES} classes (HYPEL_FOREST_MAX_CLASSES)")
+
+    # ---- fit ---------------------------------------------------------------------------------------------------
+    def fit(self, X, y):
+        be = self._backend()
+        y = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y).reshape(-1)
+        self.classes_, yi = np.unique(y, return_inverse=True)
+        self._check_classes(self.classes_)
+        n_cls = len(self.classes_)
+        x, n, f = self._rows(X)
+        if n != len(y):
+            raise ValueError(f"ForestClassifier.fit: {n} rows, {len(y)} labels")
+        n_trees = self.n_estimators
+        mf = self._resolve_max_features(f)
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        if self.bootstrap:
+            weight = np.stack([np.bincount(rng.integers(0, n, n), minlength=n) for _ in range(n_trees)]).astype(np.int32)
+        else:
+            weight = np.ones((n_trees, n), np.int32)
+        perm = rng.permutation(n).astype(np.int32)
+        self.bootstrap_counts_ = weight
+
+        # edges and bins
+        edges, n_edges = be.empty(f * FOREST_MAX_EDGES), be.zeros(f, torch.int32)
+        perm_d = be.upload(perm[:min(n, FOREST_EDGE_ROWS)])
+        be.call("forest_bin_edges_f32", Ref(x), f, n, f, Ref(perm_d), self.n_bins, Ref(edges), Ref(n_edges))
+        ldn = _round_up(n, 4)
+        bins = be.zeros(f * ldn, torch.uint8)
+        be.call("forest_bin_u8", Ref(x), f, n, f, Ref(edges), Ref(n_edges), Ref(bins), ldn)
+        self._edges, self._n_edges, self._bins, self._ldn = edges, n_edges, bins, ldn
+
+        # the order array: tree after tree, the tree's unique in-bag rows in ascending order
+        in_bag = [np.flatnonzero(weight[t] > 0).astype(np.int32) for t in range(n_trees)]
+        uniq = np.array([len(v) for v in in_bag], np.int64)
+        starts = np.concatenate([[0], np.cumsum(uniq)[:-1]])
+        order = [be.upload(np.concatenate(in_bag)), be.zeros(int(uniq.sum()), torch.int32)]
+        capacity = int((2 * uniq - 1).sum())
+        y_d, w_d = be.upload(yi.astype(np.int32)), be.upload(weight)
+        i32 = {k: be.zeros(capacity, torch.int32)
+               for k in ("feature", "thr_bin", "left", "right", "node_tree", "node_count", "node_weight")}
+        threshold, value = be.zeros(capacity), be.zeros(capacity * n_cls, torch.float64)
+        active = be.upload(np.stack([np.arange(n_trees), starts, uniq, np.arange(n_trees)], 1).astype(np.int32))
+        n_active, n_nodes, level = n_trees, n_trees, 0
+        cap = FOREST_MAX_DEPTH if self.max_depth is None else self.max_depth
+        while n_active > 0 and level <= cap:
+            if mf == f:
+                cand = np.tile(np.arange(f, dtype=np.int32), (n_active, 1))
+            else:
+                cand = np.stack([rng.choice(f, mf, replace=False) for _ in range(n_active)]).astype(np.int32)
+            cand_d = be.upload(cand)
+            score = be.zeros(n_active * mf, torch.float64)
+            best_bin, valid = be.zeros(n_active * mf, torch.int32), be.zeros(n_active * mf, torch.int32)
+            split_ws, nxt, counter = (be.zeros(n_active, torch.int32), be.zeros(8 * n_active, torch.int32),
+                                      be.zeros(1, torch.int32))
+            src, dst = order[level % 2], order[(level + 1) % 2]
+            be.call("forest_split_hist", Ref(bins), ldn, Ref(y_d), Ref(w_d), n, n_cls, Ref(src), Ref(active), n_active,
+                    Ref(cand_d), mf, f, Ref(score), Ref(best_bin), Ref(valid))
+            be.call("forest_split_apply", Ref(bins), ldn, Ref(y_d), Ref(w_d), n, n_cls, Ref(src), Ref(dst), Ref(active),
+                    n_active, Ref(cand_d), mf, f, Ref(score), Ref(best_bin), Ref(valid), Ref(edges), level, cap, n_nodes,
+                    capacity, Ref(i32["feature"]), Ref(i32["thr_bin"]), Ref(threshold), Ref(i32["left"]),
+                    Ref(i32["right"]), Ref(i32["node_tree"]), Ref(i32["node_count"]), Ref(i32["node_weight"]), Ref(value),
+                    Ref(split_ws), Ref(nxt), Ref(counter))
+            n_next = int(counter.cpu()[0])  # (the one small read per level; it also orders the buffers' lifetimes)
+            if n_next < 0:
+                raise RuntimeError("ForestClassifier.fit: node arrays too small (hypel_forest_split_apply)")
+            self._level_done(level, active, n_active, cand, score, best_bin, valid)
+            active, n_active, n_nodes, level = nxt, n_next, n_nodes + n_next, level + 1
+        self.n_levels_ = level
+
+        # device numbering is breadth-first over all trees at once; the model keeps each tree's nodes together
+        got = {k: v.cpu().numpy()[:n_nodes] for k, v in i32.items()}
+        by_tree = np.argsort(got["node_tree"], kind="stable")
+        new_id = np.empty(n_nodes, np.int64)
+        new_id[by_tree] = np.arange(n_nodes)
+        self._nodes_renumbered(new_id)
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(got["node_tree"], minlength=n_trees))]).astype(np.int32)
+        first = offsets[got["node_tree"][by_tree]]
+        child = lambda a: np.where(a[by_tree] >= 0, new_id[np.maximum(a[by_tree], 0)] - first, -1).astype(np.int32)  # noqa: E731
+        self.threshold_bin_ = got["thr_bin"][by_tree]
+        self.node_count_, self.node_weight_ = got["node_count"][by_tree], got["node_weight"][by_tree]
+        self._set_model(f, got["feature"][by_tree], threshold.cpu().numpy()[:n_nodes][by_tree], child(got["left"]),
+                        child(got["right"]), offsets,
+                        value.cpu().numpy()[:n_nodes * n_cls].reshape(n_nodes, n_cls)[by_tree])
+        return self
+
+    # ---- the served model ----------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, classes, n_features, feature, threshold, left, right, tree_offsets, value, backend=None):
+        """A served model from flat node arrays (see the class docstring; scikit-learn's tree_.feature, .threshold,
+        .children_left, .children_right and .value[:, 0, :] of every estimator, concatenated).  float64 thresholds are
+        rounded DOWN to float32."""
+        self = cls(n_estimators=len(tree_offsets) - 1, backend=backend)
+        self.classes_ = np.asarray(classes)
+        self._check_classes(self.classes_)
+        self._set_model(int(n_features), np.asarray(feature), np.asarray(threshold), np.asarray(left), np.asarray(right),
+                        np.asarray(tree_offsets), np.asarray(value, np.float64))
+        return self
+
+    def _set_model(self, n_features, feature, threshold, left, right, tree_offsets, value):
+        be = self._backend()
+        off = np.asarray(tree_offsets, np.int64)
+        n_nodes, n_cls = len(feature), len(self.classes_)
+        if len(off) < 2 or off[0] != 0 or off[-1] != n_nodes or (np.diff(off) < 1).any():
+            raise ValueError("ForestClassifier: tree_offsets must run from 0 to the node count, one node per tree at least")
+        if not (len(threshold) == len(left) == len(right) == n_nodes and value.shape == (n_nodes, n_cls)):
+            raise ValueError("ForestClassifier: node arrays of different lengths")
+        left, right = left.astype(np.int64), right.astype(np.int64)
+        is_leaf = left < 0
+        feature = np.where(is_leaf, -1, feature).astype(np.int32)
+        local = np.arange(n_nodes) - np.repeat(off[:-1], np.diff(off))
+        size = np.repeat(np.diff(off), np.diff(off))
+        inner = ~is_leaf
+        ok = ((left[inner] > local[inner]) & (left[inner] < size[inner]) & (right[inner] > local[inner]) &
+              (right[inner] < size[inner]) & (feature[inner] >= 0) & (feature[inner] < n_features))
+        if not ok.all() or (right[is_leaf] >= 0).any():
+            raise ValueError("ForestClassifier: a child must lie after its parent inside its tree, a split feature inside "
+                             "the row")
+        thr = round_down_f32(np.where(is_leaf, 0.0, threshold)) if threshold.dtype != np.float32 else \
+            np.where(is_leaf, np.float32(0), threshold).astype(np.float32)
+        self.n_features_in_ = n_features
+        self.n_estimators = len(off) - 1
+        self.feature_, self.threshold_, self.left_, self.right_ = feature, thr, left.astype(np.int32), right.astype(np.int32)
+        self.tree_offsets_, self.value_ = off.astype(np.int32), value
+        self.leaf_ = np.where(is_leaf, np.cumsum(is_leaf) - 1, -1).astype(np.int32)
+        self.leaf_value_ = np.ascontiguousarray(value[is_leaf])
+        base = np.repeat(off[:-1], np.diff(off))
+        self._abs = [np.where(is_leaf, -1, a + base).astype(np.int32) for a in (left, right)]
+        self._dev = {"tree_off": be.upload(self.tree_offsets_[:-1]), "nodes": be.upload(self._node_records(feature)),
+                     "leaf_value": be.upload(self.leaf_value_)}
+        self._scene_key, self._scene_nodes = None, None
+        self._labels_u8 = None
+        if self.classes_.dtype.kind in "iu" and self.classes_.min() >= 0 and self.classes_.max() <= 255:
+            self._labels_u8 = be.upload(self.classes_.astype(np.uint8))
+
+    def arrays(self):
+        """The arguments of from_arrays that describe the nodes."""
+        return {"feature": self.feature_, "threshold": self.threshold_, "left": self.left_, "right": self.right_,
+                "tree_offsets": self.tree_offsets_, "value": self.value_}
+
+    def _node_records(self, feature):
+        """hypel_forest_node_t of every node; `feature` is what an inner node reads (a column, or a scene code)"""
+        rec = np.zeros(len(self.feature_), FOREST_NODE_DTYPE)
+        inner = self.leaf_ < 0
+        rec["feature"], rec["threshold"] = np.where(inner, feature, 0), np.where(inner, self.threshold_, 0)
+        rec["left"], rec["right"] = np.where(inner, self._abs[0], -1 - self.leaf_), np.where(inner, self._abs[1], 0)
+        return rec
+
+    def _model_args(self, nodes):
+        d = self._dev
+        return (Ref(d["tree_off"]), self.n_estimators, Ref(nodes), len(self.feature_), Ref(d["leaf_value"]),
+                len(self.leaf_value_), len(self.classes_))
+
+    def _fitted(self):
+        if not hasattr(self, "feature_"):
+            raise RuntimeError("ForestClassifier: fit first")
+
+    # ---- predict -----------------------------------------------------------------------------------------------
+    def _chunk(self, n):
+        if self.chunk_rows:
+            return max(1, min(int(self.chunk_rows), n))
+        return max(1, min(n, (1 << 28) // (4 * self.n_features_in_)))
+
+    def _run(self, X, want_proba):
+        be = self._backend()
+        self._fitted()
+        n = X.shape[0]
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"ForestClassifier: X has {X.shape[1]} features, the model was fitted on {self.n_features_in_}")
+        n_cls = len(self.classes_)
+        idx = be.zeros(_round_up(n, 4), torch.uint8)
+        proba = be.zeros(n * n_cls, torch.float64) if want_proba else None
+        step = self._chunk(n)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            x, m, f = self._rows(X[r0:r1])
+            be.call("forest_predict_rows", Ref(x), f, m, f, *self._model_args(self._dev["nodes"]), None, None,
+                    Ref(idx, r0), 0, None if proba is None else Ref(proba, r0 * n_cls))
+            be.synchronize()  # x dies here
+        return idx.cpu().numpy()[:n], None if proba is None else proba.cpu().numpy().reshape(n, n_cls)
+
+    def predict(self, X):
+        return self.classes_[self._run(X, False)[0]]
+
+    def predict_proba(self, X):
+        return self._run(X, True)[1]
+
+    def predict_scene(self, arrays, raster, raster_w, direct=None):
+        """Whole-scene path: `arrays` is a common_nn_ops.SceneArrays fed with the padded scene and the (x, y) targets,
+        `raster` a flat uint8 device tensor that receives classes_[winner] at y * raster_w + x.  direct=None takes
+        hypel_forest_predict_scene where the data set is the single-resolution kind hypel_gather_patches_f32 serves and
+        the chunked gather + hypel_forest_predict_rows otherwise (GRSS2018's 2x layout, multi-scene sets); False forces
+        the gather path."""
+        be = self._backend()
+        self._fitted()
+        if self._labels_u8 is None:
+            raise ValueError("ForestClassifier.predict_scene: class labels must be integers in 0..255 for the uint8 raster")
+        n = len(arrays)
+        p, _, c = arrays.shape
+        if p * p * c != self.n_features_in_:
+            raise ValueError(f"ForestClassifier.predict_scene: patches of {p * p * c} features, the model has "
+                             f"{self.n_features_in_}")
+        single = arrays.scenes is None and arrays.casi_scale == 1
+        if direct is None:
+            direct = single
+        if direct:
+            if not single:
+                raise ValueError("ForestClassifier.predict_scene(direct=True): a single-resolution, single-scene data set")
+            hp, wp, cc = (int(v) for v in arrays.casi.shape)
+            cl = 0 if arrays.lidar is None else int(arrays.lidar.shape[2])
+            if self._scene_key != (p, wp, cc, cl):  # translated once per scene geometry
+                self._scene_nodes = be.upload(self._node_records(scene_features(self.feature_, p, wp, cc, cl)))
+                self._scene_key = (p, wp, cc, cl)
+            be.call("forest_predict_scene", Ref(arrays.casi.reshape(-1)),
+                    None if arrays.lidar is None else Ref(arrays.lidar.reshape(-1)), hp, wp, cc, cl,
+                    Ref(arrays.points.reshape(-1)), n, p, *self._model_args(self._scene_nodes), Ref(self._labels_u8),
+                    Ref(raster), int(raster_w))
+            be.synchronize()
+            return
+        step = self._chunk(n)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            patches, pts = arrays.gather(torch.arange(r0, r1, device=be.device))
+            f = self.n_features_in_
+            be.call("forest_predict_rows", Ref(patches.reshape(-1)), f, r1 - r0, f, *self._model_args(self._dev["nodes"]),
+                    Ref(self._labels_u8), Ref(pts.reshape(-1)), Ref(raster), int(raster_w), None)
+            be.synchronize()  # the patches die here

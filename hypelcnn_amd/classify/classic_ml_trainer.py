@@ -1,13 +1,18 @@
-"""Classic-ML baseline (reference classify/classic_ml_trainer.py:20-157): a kernel SVC on flattened patches, trained and
-served on the device by hypelcnn_amd.classic.svc.SVC, with the reference's flow, flag names and output files --
+"""Classic-ML baseline (reference classify/classic_ml_trainer.py:20-157): a kernel SVC or a random forest on flattened
+patches, trained and served on the device by hypelcnn_amd.classic.svc.SVC / hypelcnn_amd.classic.forest.ForestClassifier,
+with the reference's flow, flag names and output files --
 `confusion_matrix_<loader>_run<i>.csv`, `metrics_<loader>_run<i>.txt` (OA,AA,KAPPA) and `params_<loader>_run<i>.json`
 under --base_log_path, next to which utilities/latex_table_from_conf_set*.py expects the CNN's.
 
 Differences from the reference, all on purpose:
  - the estimator, which the reference picks by editing comments (:46-50), is a flag: --estimator svc_rbf (its GRSS2013
    line :49, gamma 1e-09, C 10000; --svc_gamma / --svc_c / --svc_tol) or svc_poly (its :48, degree 1, gamma "scale");
- - RandomForestClassifier (:46) is refused by name: a forest's result depends on scikit-learn's random stream and
-   cannot be held to a fixture;
+ - the reference's live line (:46, RandomForestClassifier(n_estimators=50, max_features=int(2 * sqrt(144)))) is
+   --estimator forest: a forest of histogram trees grown and served on the device (--forest_trees 50,
+   --forest_max_features 24, --forest_bins 256, --forest_seed 0 + the run index), with a random stream of its own,
+   thresholds on bin edges, no candidate redraw and level-wise growth.  scikit-learn's estimator itself,
+   asked for by name (RandomForestClassifier, random_forest, rf, ExtraTreesClassifier), stays refused: its result is
+   its random stream's, which this project does not reproduce;
  - the reference's search (:126-136, GridSearchCV(SVC(), C x gamma) over StratifiedShuffleSplit(2, 0.1, 42)) runs on
    the device under a NEW flag, --svc_grid (hypelcnn_amd.classic.model_selection): after the baseline fit and its three
    files it searches the flattened training data, prints the reference's line and writes svc_grid_<loader>_run<i>.json;
@@ -16,7 +21,8 @@ Differences from the reference, all on purpose:
    refused: its contract in the reference is scikit-learn's own GridSearchCV object, which this project does not return;
  - --fullscene writes result_raw.tif / result_colorized.tif under --output_path, not the reference's hard-wired ".."
    (:111); patches are cut on the device (hypel_gather_patches_f32) and predicted in chunks sized from free memory,
-   independent of --batch_size;
+   independent of --batch_size; the forest walks its trees straight on the padded scene where the data set has one
+   resolution (hypel_forest_predict_scene);
  - OA / AA / kappa come from the confusion matrix on the host (sklearn.metrics' definitions, :56-59)."""
 import argparse
 import json
@@ -32,7 +38,7 @@ from hypelcnn_amd.common.common_nn_ops import SceneArrays, create_colored_image,
 from hypelcnn_amd.common.tiff_io import imwrite
 from hypelcnn_amd.importer.InMemoryImporter import InMemoryImporter
 
-ESTIMATORS = ("svc_rbf", "svc_poly")
+ESTIMATORS = ("svc_rbf", "svc_poly", "forest")
 
 
 def add_parse_cmds_for_app(parser):
@@ -42,10 +48,16 @@ def add_parse_cmds_for_app(parser):
                         help="If true, performs full scene classification.")
     parser.add_argument("--split_count", nargs="?", type=int, default=1, help="Split count")
     parser.add_argument("--estimator", nargs="?", type=str, default="svc_rbf",
-                        help="svc_rbf (reference :49) or svc_poly (reference :48)")
+                        help="svc_rbf (reference :49), svc_poly (reference :48) or forest (reference :46)")
     parser.add_argument("--svc_gamma", nargs="?", type=float, default=1e-09, help="RBF gamma (svc_rbf)")
     parser.add_argument("--svc_c", nargs="?", type=float, default=None, help="C (default: 10000 svc_rbf, 1 svc_poly)")
     parser.add_argument("--svc_tol", nargs="?", type=float, default=1e-3, help="Stopping tolerance of the solver")
+    parser.add_argument("--forest_trees", nargs="?", type=int, default=50, help="Trees of the forest (forest)")
+    parser.add_argument("--forest_max_features", nargs="?", type=int, default=24,
+                        help="Candidate features per node (forest; the reference's int(2 * sqrt(144)))")
+    parser.add_argument("--forest_bins", nargs="?", type=int, default=256, help="Bins per feature, 2..256 (forest)")
+    parser.add_argument("--forest_seed", nargs="?", type=int, default=0,
+                        help="Seed of the forest's random stream; episode i of --split_count uses seed + i")
     parser.add_argument("--svc_grid", nargs="?", const=True, type=type_ensure_strtobool, default=False,
                         help="If true, searches C x gamma on the device after the baseline fit (reference :126-136).")
     # (a decade range such as -2:10:13 starts with '-' and is no number, so argparse would take it for an option:
@@ -56,14 +68,18 @@ def add_parse_cmds_for_app(parser):
                         help="If true, refits on the best cell; --fullscene then uses that estimator.")
 
 
-def create_estimator(flags, backend=None):
+def create_estimator(flags, backend=None, run_index=0):
     from hypelcnn_amd.classic.svc import SVC
     name = flags.estimator
     if name in ("random_forest", "rf", "RandomForestClassifier", "ExtraTreesClassifier"):
         raise NotImplementedError(
-            f"--estimator {name}: RandomForestClassifier (reference classic_ml_trainer.py:46) is not built: its result "
-            f"depends on scikit-learn's random stream, so it cannot be held to a fixture, and tree building is a different "
-            f"kind of kernel; use one of {ESTIMATORS}")
+            f"--estimator {name}: scikit-learn's RandomForestClassifier (reference classic_ml_trainer.py:46) is not built: "
+            f"its result is that of scikit-learn's random stream, which is not reproduced here; --estimator forest grows "
+            f"the same kind of forest on the device with a seeded stream of its own; use one of {ESTIMATORS}")
+    if name == "forest":
+        from hypelcnn_amd.classic.forest import ForestClassifier
+        return ForestClassifier(n_estimators=flags.forest_trees, max_features=flags.forest_max_features,
+                                n_bins=flags.forest_bins, seed=flags.forest_seed + run_index, backend=backend)
     if name == "svc_rbf":
         return SVC(kernel="rbf", gamma=flags.svc_gamma, C=10000.0 if flags.svc_c is None else flags.svc_c,
                    tol=flags.svc_tol, backend=backend)
@@ -208,6 +224,8 @@ def main(argv=None, backend=None):
             "--hyperparamopt (reference classic_ml_trainer.py:126-136) is not built: its contract is scikit-learn's own "
             "GridSearchCV object; the same search, with the same grid and splits, runs on the device under --svc_grid "
             "(--svc_grid_c / --svc_grid_gamma / --svc_grid_refit)")
+    if flags.svc_grid and flags.estimator == "forest":
+        raise ValueError("--svc_grid searches the SVC's C x gamma: not with --estimator forest")
     results = []
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)
@@ -215,7 +233,7 @@ def main(argv=None, backend=None):
             loader_name=flags.loader_name, path=flags.path, test_data_ratio=0, train_data_ratio=0.1,
             neighborhood=flags.neighborhood, normalize=False)
         start_time = time.time()
-        estimator = create_estimator(flags, backend)
+        estimator = create_estimator(flags, backend, run_index)
         estimator.fit(flatten_data(training.data), training.labels)
         print("Completed training(%.3f sec)" % (time.time() - start_time))
         predicted = estimator.predict(flatten_data(validation.data))

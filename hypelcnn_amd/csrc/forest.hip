@@ -1,0 +1,552 @@
+// Random forest of histogram trees, grown and served on the device (include/hypel.h, hypel_forest_*;
+// hypelcnn_amd/classic/forest.py).
+//
+//   * bin_edges_kernel   : one workgroup per feature column.  The sampled rows of the column are sorted in LDS (bitonic,
+//                          at most HYPEL_FOREST_EDGE_ROWS values), the quantile ranks are read off, duplicates collapse.
+//   * bin_u8_kernel      : bin(x) = the number of edges < x, feature-major uint8.
+//   * split_hist_kernel  : one workgroup per (active node, candidate slot): hist[bin][class] += weight with LDS integer
+//                          atomics, a prefix sum over the bins per class, one score per bin boundary, the best boundary.
+//   * split_apply_kernel : one workgroup per active node: the best slot, the node record, the stable partition of the
+//                          node's segment of the order array (from one buffer into the other).
+//   * level_compact_kernel: one workgroup: a prefix sum over the nodes that split gives the children their node numbers
+//                          and their places in the next level's active list, in active-node order.
+//   * predict_kernel     : one row (or one scene pixel) per lane, one wavefront per block: the walk diverges per lane,
+//                          so a block holds no second wavefront that would wait on the slowest; a node is one
+//                          16-byte record, so a step is two dependent loads (the node, the value); the class sums
+//                          are fp64 in LDS, one column per lane, sized by n_classes so that LDS does not cap the
+//                          wavefronts per CU that hide those loads.
+// Integer atomics only (sums of int32 weights are exact and commute); every choice among equals is a total order
+// (score, then feature index, then bin) and every list is built by a prefix sum, so two runs write identical bytes.
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+
+#define ST ((hipStream_t)stream)
+
+namespace {
+
+constexpr int MAXE = HYPEL_FOREST_MAX_EDGES;
+constexpr int MAXC = HYPEL_FOREST_MAX_CLASSES;
+constexpr int EDGE_ROWS = HYPEL_FOREST_EDGE_ROWS;
+constexpr int SORT_THREADS = 1024;
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+
+__global__ __launch_bounds__(SORT_THREADS) void bin_edges_kernel(const float* __restrict__ x, int64_t ld, int64_t n,
+                                                                 int n_s, const int32_t* __restrict__ perm, int n_bins,
+                                                                 float* __restrict__ edges,
+                                                                 int32_t* __restrict__ n_edges) {
+    __shared__ float s[EDGE_ROWS];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    int m = 1;
+    while (m < n_s) m <<= 1;
+    for (int i = tid; i < m; i += SORT_THREADS) {
+        float v = INFINITY;
+        if (i < n_s) {
+            int64_t r = perm[i];
+            if (r < 0 || r >= n) r = 0;  // (a permutation of the rows by contract; never read outside x)
+            v = x[r * ld + f] + 0.0f;    // -0.0 -> +0.0: equal values have equal bits, whatever the sort does with them
+        }
+        s[i] = v;
+    }
+    __syncthreads();
+    for (int k = 2; k <= m; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < m; i += SORT_THREADS) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const float a = s[i], b = s[p];
+                    const bool up = (i & k) == 0;
+                    if (up ? a > b : a < b) {
+                        s[i] = b;
+                        s[p] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    float* e = edges + (int64_t)f * MAXE;
+    if (tid == 0) {
+        const float top = s[n_s - 1];
+        int ne = 0;
+        for (int j = 1; j < n_bins; ++j) {
+            const float v = s[(int)(((int64_t)j * n_s) / n_bins)];
+            if (v >= top) break;  // an edge at the column maximum sends nothing to the right
+            if (ne == 0 || v != e[ne - 1]) e[ne++] = v;
+        }
+        n_edges[f] = ne;
+        for (int j = ne; j < MAXE; ++j) e[j] = INFINITY;
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void bin_u8_kernel(const float* __restrict__ x, int64_t ld, int64_t n,
+                                                         int64_t row_blocks, const float* __restrict__ edges,
+                                                         const int32_t* __restrict__ n_edges, uint8_t* __restrict__ bins,
+                                                         int64_t ldn) {
+    __shared__ float e[MAXE + 1];
+    const int64_t f = blockIdx.x / row_blocks, rb = blockIdx.x - f * row_blocks;
+    for (int j = threadIdx.x; j < MAXE; j += THREADS) e[j] = edges[f * MAXE + j];
+    __syncthreads();
+    const int64_t i = rb * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float v = x[i * ld + f];
+    int lo = 0, hi = min(max(n_edges[f], 0), MAXE);  // the first edge >= v = the number of edges < v
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] < v)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    bins[f * ldn + i] = (uint8_t)lo;
+}
+
+// (valid, score descending, feature ascending, bin ascending): a total order, so any reduction tree picks the same one
+struct Pick {
+    double score;
+    int feature, bin, valid;
+};
+
+__device__ __forceinline__ bool better(const Pick& a, const Pick& b) {
+    if (a.valid != b.valid) return a.valid > b.valid;
+    if (a.score != b.score) return a.score > b.score;
+    if (a.feature != b.feature) return a.feature < b.feature;
+    return a.bin < b.bin;
+}
+
+__device__ __forceinline__ Pick block_best(Pick p, Pick* red) {
+    red[threadIdx.x] = p;
+    __syncthreads();
+    for (int d = THREADS / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d && better(red[threadIdx.x + d], red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + d];
+        __syncthreads();
+    }
+    const Pick out = red[0];
+    __syncthreads();
+    return out;
+}
+
+__device__ __forceinline__ double boundary_score(int64_t sl, int nl, int64_t sr, int nr) {
+#pragma clang fp contract(off)
+    const double a = (double)sl / (double)nl;
+    const double b = (double)sr / (double)nr;
+    return a + b;
+}
+
+__global__ __launch_bounds__(THREADS) void split_hist_kernel(const uint8_t* __restrict__ bins, int64_t ldn,
+                                                             const int32_t* __restrict__ y,
+                                                             const int32_t* __restrict__ weight, int64_t n, int C,
+                                                             const int32_t* __restrict__ order,
+                                                             const int32_t* __restrict__ active,
+                                                             const int32_t* __restrict__ cand, int mf,
+                                                             double* __restrict__ score, int32_t* __restrict__ best_bin,
+                                                             int32_t* __restrict__ valid) {
+    __shared__ int hist[(MAXE + 1) * MAXC];
+    __shared__ Pick red[THREADS];
+    const int tid = threadIdx.x;
+    const int64_t a = blockIdx.x / mf;
+    const int tree = active[4 * a], start = active[4 * a + 1], count = active[4 * a + 2];
+    const int f = cand[blockIdx.x];
+    if (count < 2) {  // (uniform over the block) one unique sample: a leaf
+        if (tid == 0) {
+            score[blockIdx.x] = 0.0;
+            best_bin[blockIdx.x] = -1;
+            valid[blockIdx.x] = 0;
+        }
+        return;
+    }
+    for (int i = tid; i < (MAXE + 1) * C; i += THREADS) hist[i] = 0;
+    __syncthreads();
+    const uint8_t* bf = bins + (int64_t)f * ldn;
+    const int32_t* wt = weight + (int64_t)tree * n;
+    for (int i = tid; i < count; i += THREADS) {
+        const int s = order[start + i];
+        atomicAdd(&hist[(int)bf[s] * C + y[s]], wt[s]);
+    }
+    __syncthreads();
+    if (tid < C) {  // inclusive prefix over the bins, one class per lane
+        int acc = 0;
+        for (int b = 0; b <= MAXE; ++b) {
+            acc += hist[b * C + tid];
+            hist[b * C + tid] = acc;
+        }
+    }
+    __syncthreads();
+    Pick p = {0.0, f, tid, 0};
+    if (tid < MAXE) {  // boundary tid: bins <= tid go left
+        int64_t sl = 0, sr = 0;
+        int nl = 0, nr = 0;
+        for (int k = 0; k < C; ++k) {
+            const int l = hist[tid * C + k], r = hist[MAXE * C + k] - l;
+            nl += l;
+            nr += r;
+            sl += (int64_t)l * l;
+            sr += (int64_t)r * r;
+        }
+        if (nl > 0 && nr > 0) {
+            p.score = boundary_score(sl, nl, sr, nr);
+            p.valid = 1;
+        }
+    }
+    p = block_best(p, red);
+    if (tid == 0) {
+        score[blockIdx.x] = p.valid ? p.score : 0.0;
+        best_bin[blockIdx.x] = p.valid ? p.bin : -1;
+        valid[blockIdx.x] = p.valid;
+    }
+}
+
+struct NodeOut {
+    int32_t *feature, *thr_bin, *left, *right, *node_tree, *node_count, *node_weight;
+    float* threshold;
+    double* value;
+};
+
+__global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __restrict__ bins, int64_t ldn,
+                                                              const int32_t* __restrict__ y,
+                                                              const int32_t* __restrict__ weight, int64_t n, int C,
+                                                              const int32_t* __restrict__ order_in,
+                                                              int32_t* __restrict__ order_out,
+                                                              const int32_t* __restrict__ active,
+                                                              const int32_t* __restrict__ cand, int mf,
+                                                              const double* __restrict__ score,
+                                                              const int32_t* __restrict__ best_bin,
+                                                              const int32_t* __restrict__ valid,
+                                                              const float* __restrict__ edges, int at_cap, NodeOut o,
+                                                              int32_t* __restrict__ split_ws) {
+    __shared__ int cls[MAXC];
+    __shared__ Pick red[THREADS];
+    __shared__ int wcount[2 * WAVES];
+    __shared__ int n_left_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t a = blockIdx.x;
+    const int tree = active[4 * a], start = active[4 * a + 1], count = active[4 * a + 2], node = active[4 * a + 3];
+    const int32_t* wt = weight + (int64_t)tree * n;
+    if (tid < MAXC) cls[tid] = 0;
+    if (tid == 0) n_left_s = 0;
+    __syncthreads();
+    for (int i = tid; i < count; i += THREADS) {
+        const int s = order_in[start + i];
+        atomicAdd(&cls[y[s]], wt[s]);
+    }
+    Pick p = {0.0, INT_MAX, INT_MAX, 0};
+    for (int s = tid; s < mf; s += THREADS) {
+        const int64_t at = a * mf + s;
+        const Pick q = {score[at], cand[at], best_bin[at], valid[at]};
+        if (q.valid && better(q, p)) p = q;
+    }
+    p = block_best(p, red);  // (its barriers also publish cls)
+    int nw = 0, classes_present = 0;
+    for (int k = 0; k < C; ++k) {
+        nw += cls[k];
+        classes_present += cls[k] > 0;
+    }
+    const bool leaf = count < 2 || classes_present < 2 || !p.valid || at_cap;
+    if (tid == 0) {
+        o.node_tree[node] = tree;
+        o.node_count[node] = count;
+        o.node_weight[node] = nw;
+        o.feature[node] = leaf ? -1 : p.feature;
+        o.thr_bin[node] = leaf ? -1 : p.bin;
+        o.threshold[node] = leaf ? 0.0f : edges[(int64_t)p.feature * MAXE + p.bin];
+        o.left[node] = -1;
+        o.right[node] = -1;
+    }
+    if (tid < C) o.value[(int64_t)node * C + tid] = (double)cls[tid] / (double)nw;
+    if (leaf) {
+        if (tid == 0) split_ws[a] = 0;
+        return;
+    }
+    // stable partition of order_in[start .. start + count) by bin <= p.bin into order_out at the same place
+    const uint8_t* bf = bins + (int64_t)p.feature * ldn;
+    int mine = 0;
+    for (int i = tid; i < count; i += THREADS) mine += (int)bf[order_in[start + i]] <= p.bin;
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
+    if (lane == 0 && mine) atomicAdd(&n_left_s, mine);
+    __syncthreads();
+    const int n_left = n_left_s;
+    int run_l = 0, run_r = 0;
+    for (int base = 0; base < count; base += THREADS) {
+        const int i = base + tid;
+        const bool live = i < count;
+        const int s = live ? order_in[start + i] : 0;
+        const bool go_left = live && (int)bf[s] <= p.bin;
+        const unsigned long long bl = __ballot(go_left), br = __ballot(live && !go_left);
+        if (lane == 0) {
+            wcount[wave] = __popcll(bl);
+            wcount[WAVES + wave] = __popcll(br);
+        }
+        __syncthreads();
+        int before_l = 0, before_r = 0, all_l = 0, all_r = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            const int cl = wcount[w], cr = wcount[WAVES + w];
+            if (w < wave) {
+                before_l += cl;
+                before_r += cr;
+            }
+            all_l += cl;
+            all_r += cr;
+        }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (go_left)
+            order_out[start + run_l + before_l + __popcll(bl & below)] = s;
+        else if (live)
+            order_out[start + n_left + run_r + before_r + __popcll(br & below)] = s;
+        run_l += all_l;
+        run_r += all_r;
+        __syncthreads();
+    }
+    if (tid == 0) split_ws[a] = n_left;
+}
+
+__global__ __launch_bounds__(THREADS) void level_compact_kernel(const int32_t* __restrict__ active, int n_active,
+                                                                const int32_t* __restrict__ split_ws, int node_base,
+                                                                int node_capacity, int32_t* __restrict__ left,
+                                                                int32_t* __restrict__ right,
+                                                                int32_t* __restrict__ next_active,
+                                                                int32_t* __restrict__ counter) {
+    __shared__ int wcount[WAVES];
+    __shared__ int overflow;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) overflow = 0;
+    int run = 0;
+    for (int base = 0; base < n_active; base += THREADS) {
+        const int a = base + tid;
+        const int n_left = a < n_active ? split_ws[a] : 0;
+        const bool sp = n_left > 0;
+        const unsigned long long b = __ballot(sp);
+        if (lane == 0) wcount[wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            if (w < wave) before += wcount[w];
+            all += wcount[w];
+        }
+        if (sp) {
+            const int r = run + before + __popcll(b & ((1ull << lane) - 1ull));
+            const int tree = active[4 * a], start = active[4 * a + 1], count = active[4 * a + 2], node = active[4 * a + 3];
+            const int l = node_base + 2 * r;
+            if (l + 1 < node_capacity) {
+                left[node] = l;
+                right[node] = l + 1;
+                int32_t* q = next_active + 8 * (int64_t)r;
+                q[0] = tree;
+                q[1] = start;
+                q[2] = n_left;
+                q[3] = l;
+                q[4] = tree;
+                q[5] = start + n_left;
+                q[6] = count - n_left;
+                q[7] = l + 1;
+            } else {
+                overflow = 1;
+            }
+        }
+        run += all;
+        __syncthreads();
+    }
+    if (tid == 0) counter[0] = overflow ? -1 : 2 * run;
+}
+
+struct Model {
+    const int32_t* tree_off;
+    const int4* nodes;  // hypel_forest_node_t: one 16-byte load per step of the walk
+    const double* leaf_value;
+    int n_trees, n_nodes, n_classes;
+};
+static_assert(sizeof(hypel_forest_node_t) == sizeof(int4), "hypel_forest_node_t is loaded as one int4");
+
+struct RowReader {
+    const float* row;
+    __device__ __forceinline__ float operator()(int feature) const { return row[feature]; }
+};
+
+struct SceneReader {  // feature = 2 * (element offset from the window origin's pixel) + (1: lidar)
+    const float *casi, *lidar;
+    __device__ __forceinline__ float operator()(int feature) const {
+        return (feature & 1) ? lidar[feature >> 1] : casi[feature >> 1];
+    }
+};
+
+constexpr int PRED_LANES = 64;
+
+template <class Reader>
+__device__ __forceinline__ void walk_and_vote(const Model& m, const Reader& read, double* acc, int lane,
+                                              const uint8_t* __restrict__ class_labels, uint8_t* __restrict__ out,
+                                              double* __restrict__ proba) {
+    const int C = m.n_classes;
+    for (int k = 0; k < C; ++k) acc[k * PRED_LANES + lane] = 0.0;
+    for (int t = 0; t < m.n_trees; ++t) {
+        int4 rec = m.nodes[m.tree_off[t]];  // (feature, threshold bits, left, right); left < 0: leaf row -1 - left
+        for (int step = 0; rec.z >= 0 && step < m.n_nodes; ++step)  // (bounded: a child's index exceeds its parent's)
+            rec = m.nodes[read(rec.x) <= __int_as_float(rec.y) ? rec.z : rec.w];
+        if (rec.z < 0) {
+            const double* row = m.leaf_value + (int64_t)(-1 - rec.z) * C;
+            for (int k = 0; k < C; ++k) acc[k * PRED_LANES + lane] += row[k];
+        }
+    }
+    int best = 0;
+    double bv = -1.0;
+    for (int k = 0; k < C; ++k) {
+        const double v = acc[k * PRED_LANES + lane] / (double)m.n_trees;
+        if (proba) proba[k] = v;
+        if (v > bv) {  // the first maximum
+            bv = v;
+            best = k;
+        }
+    }
+    *out = class_labels ? class_labels[best] : (uint8_t)best;
+}
+
+__global__ __launch_bounds__(PRED_LANES) void predict_rows_kernel(const float* __restrict__ x, int64_t ld, int64_t n,
+                                                                  Model m, const uint8_t* __restrict__ class_labels,
+                                                                  const int32_t* __restrict__ points,
+                                                                  uint8_t* __restrict__ out, int64_t raster_w,
+                                                                  double* __restrict__ proba) {
+    extern __shared__ double acc[];  // [n_classes][PRED_LANES]
+    const int64_t i = (int64_t)blockIdx.x * PRED_LANES + threadIdx.x;
+    if (i >= n) return;
+    const RowReader read = {x + i * ld};
+    uint8_t* o = points ? out + (int64_t)points[2 * i + 1] * raster_w + points[2 * i] : out + i;
+    walk_and_vote(m, read, acc, threadIdx.x, class_labels, o, proba ? proba + i * m.n_classes : nullptr);
+}
+
+__global__ __launch_bounds__(PRED_LANES) void predict_scene_kernel(const float* __restrict__ casi,
+                                                                   const float* __restrict__ lidar, int64_t wp, int cc,
+                                                                   int cl, const int32_t* __restrict__ points, int64_t n,
+                                                                   Model m, const uint8_t* __restrict__ class_labels,
+                                                                   uint8_t* __restrict__ out, int64_t raster_w) {
+    extern __shared__ double acc[];  // [n_classes][PRED_LANES]
+    const int64_t i = (int64_t)blockIdx.x * PRED_LANES + threadIdx.x;
+    if (i >= n) return;
+    const int64_t px = points[2 * i], py = points[2 * i + 1];
+    const int64_t origin = py * wp + px;
+    const SceneReader read = {casi + origin * cc, lidar ? lidar + origin * cl : nullptr};
+    walk_and_vote(m, read, acc, threadIdx.x, class_labels, out + py * raster_w + px, nullptr);
+}
+
+}  // namespace
+
+extern "C" int hypel_forest_bin_edges_f32(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* perm,
+                                          int32_t n_bins, float* edges, int32_t* n_edges, hypel_stream_t stream) {
+    HYPEL_REQUIRE(x && perm && edges && n_edges, "hypel_forest_bin_edges_f32");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && n_bins >= 2 && n_bins <= MAXE + 1, "hypel_forest_bin_edges_f32");
+    const int n_s = (int)(n < EDGE_ROWS ? n : EDGE_ROWS);
+    hipLaunchKernelGGL(bin_edges_kernel, dim3(f), dim3(SORT_THREADS), 0, ST, x, ld, n, n_s, perm, n_bins, edges, n_edges);
+    HYPEL_CHECK_LAUNCH("hypel_forest_bin_edges_f32");
+    return 0;
+}
+
+extern "C" int hypel_forest_bin_u8(const float* x, int64_t ld, int64_t n, int32_t f, const float* edges,
+                                   const int32_t* n_edges, uint8_t* bins, int64_t ldn, hypel_stream_t stream) {
+    HYPEL_REQUIRE(x && edges && n_edges && bins, "hypel_forest_bin_u8");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && ldn >= n, "hypel_forest_bin_u8");
+    const int64_t row_blocks = (n + THREADS - 1) / THREADS;
+    HYPEL_REQUIRE(row_blocks * f < ((int64_t)1 << 31), "hypel_forest_bin_u8");
+    hipLaunchKernelGGL(bin_u8_kernel, dim3((unsigned)(row_blocks * f)), dim3(THREADS), 0, ST, x, ld, n, row_blocks, edges,
+                       n_edges, bins, ldn);
+    HYPEL_CHECK_LAUNCH("hypel_forest_bin_u8");
+    return 0;
+}
+
+extern "C" int hypel_forest_split_hist(const uint8_t* bins, int64_t ldn, const int32_t* y, const int32_t* weight,
+                                       int64_t n, int32_t n_classes, const int32_t* order, const int32_t* active,
+                                       int32_t n_active, const int32_t* cand, int32_t max_features, int32_t f,
+                                       double* score, int32_t* best_bin, int32_t* valid, hypel_stream_t stream) {
+    HYPEL_REQUIRE(bins && y && weight && order && active && cand && score && best_bin && valid,
+                  "hypel_forest_split_hist");
+    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_hist");
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_hist");
+    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_hist");
+    HYPEL_REQUIRE((int64_t)n_active * max_features < ((int64_t)1 << 31), "hypel_forest_split_hist");
+    hipLaunchKernelGGL(split_hist_kernel, dim3((unsigned)((int64_t)n_active * max_features)), dim3(THREADS), 0, ST, bins,
+                       ldn, y, weight, n, n_classes, order, active, cand, max_features, score, best_bin, valid);
+    HYPEL_CHECK_LAUNCH("hypel_forest_split_hist");
+    return 0;
+}
+
+extern "C" int hypel_forest_split_apply(const uint8_t* bins, int64_t ldn, const int32_t* y, const int32_t* weight,
+                                        int64_t n, int32_t n_classes, const int32_t* order_in, int32_t* order_out,
+                                        const int32_t* active, int32_t n_active, const int32_t* cand,
+                                        int32_t max_features, int32_t f, const double* score, const int32_t* best_bin,
+                                        const int32_t* valid, const float* edges, int32_t level, int32_t max_depth,
+                                        int32_t node_base, int32_t node_capacity, int32_t* feature, int32_t* thr_bin,
+                                        float* threshold, int32_t* left, int32_t* right, int32_t* node_tree,
+                                        int32_t* node_count, int32_t* node_weight, double* value, int32_t* split_ws,
+                                        int32_t* next_active, int32_t* counter, hypel_stream_t stream) {
+    HYPEL_REQUIRE(bins && y && weight && order_in && order_out && order_in != order_out && active && cand,
+                  "hypel_forest_split_apply");
+    HYPEL_REQUIRE(score && best_bin && valid && edges && feature && thr_bin && threshold && left && right,
+                  "hypel_forest_split_apply");
+    HYPEL_REQUIRE(node_tree && node_count && node_weight && value && split_ws && next_active && counter,
+                  "hypel_forest_split_apply");
+    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_apply");
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_apply");
+    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_apply");
+    HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, "hypel_forest_split_apply");
+    HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, "hypel_forest_split_apply");
+    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    hipLaunchKernelGGL(split_apply_kernel, dim3(n_active), dim3(THREADS), 0, ST, bins, ldn, y, weight, n, n_classes,
+                       order_in, order_out, active, cand, max_features, score, best_bin, valid, edges,
+                       (int)(level >= max_depth), o, split_ws);
+    hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
+                       node_capacity, left, right, next_active, counter);
+    HYPEL_CHECK_LAUNCH("hypel_forest_split_apply");
+    return 0;
+}
+
+static int forest_model(const char* name, Model* m, const int32_t* tree_off, int32_t n_trees,
+                        const hypel_forest_node_t* nodes, int32_t n_nodes, const double* leaf_value, int32_t n_leaves,
+                        int32_t n_classes) {
+    HYPEL_REQUIRE(tree_off && nodes && leaf_value, name);
+    HYPEL_REQUIRE(n_trees > 0 && n_nodes >= n_trees && n_leaves > 0 && n_leaves <= n_nodes, name);
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, name);
+    *m = Model{tree_off, reinterpret_cast<const int4*>(nodes), leaf_value, n_trees, n_nodes, n_classes};
+    return 0;
+}
+
+extern "C" int hypel_forest_predict_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off,
+                                         int32_t n_trees, const hypel_forest_node_t* nodes, int32_t n_nodes,
+                                         const double* leaf_value, int32_t n_leaves, int32_t n_classes,
+                                         const uint8_t* class_labels, const int32_t* points, uint8_t* out,
+                                         int64_t raster_w, double* proba, hypel_stream_t stream) {
+    Model m;
+    if (forest_model("hypel_forest_predict_rows", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves,
+                     n_classes))
+        return -1;
+    HYPEL_REQUIRE(x && out, "hypel_forest_predict_rows");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && (!points || raster_w > 0), "hypel_forest_predict_rows");
+    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
+    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_predict_rows");
+    hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
+                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, m, class_labels,
+                       points, out, raster_w, proba);
+    HYPEL_CHECK_LAUNCH("hypel_forest_predict_rows");
+    return 0;
+}
+
+extern "C" int hypel_forest_predict_scene(const float* casi, const float* lidar, int64_t hp, int64_t wp, int32_t cc,
+                                          int32_t cl, const int32_t* points, int64_t n, int32_t p,
+                                          const int32_t* tree_off, int32_t n_trees,
+                                          const hypel_forest_node_t* scene_nodes, int32_t n_nodes,
+                                          const double* leaf_value, int32_t n_leaves, int32_t n_classes,
+                                          const uint8_t* class_labels, uint8_t* out, int64_t raster_w,
+                                          hypel_stream_t stream) {
+    Model m;
+    if (forest_model("hypel_forest_predict_scene", &m, tree_off, n_trees, scene_nodes, n_nodes, leaf_value, n_leaves,
+                     n_classes))
+        return -1;
+    HYPEL_REQUIRE(casi && points && out && (cl == 0 || lidar), "hypel_forest_predict_scene");
+    HYPEL_REQUIRE(n > 0 && p > 0 && hp >= p && wp >= p && cc > 0 && cl >= 0 && raster_w > 0,
+                  "hypel_forest_predict_scene");
+    // the largest element offset a translated feature can carry must fit the int32 it is packed into
+    HYPEL_REQUIRE(((int64_t)(p - 1) * wp + p) * (cc > cl ? cc : cl) < ((int64_t)1 << 30), "hypel_forest_predict_scene");
+    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
+    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_predict_scene");
+    hipLaunchKernelGGL(predict_scene_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
+                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, casi, cl ? lidar : nullptr,
+                       wp, cc, cl, points, n, m, class_labels, out, raster_w);
+    HYPEL_CHECK_LAUNCH("hypel_forest_predict_scene");
+    return 0;
+}

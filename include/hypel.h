@@ -779,6 +779,91 @@ int hypel_tensor_summary_f32(const float* base, const int64_t* table, int32_t n_
                              int32_t n_limits, double* stats, int64_t* nonfinite, int64_t* buckets, double* ws,
                              int32_t ws_slices, hypel_stream_t stream);
 
+/* ---- random forest of histogram trees (reference classify/classic_ml_trainer.py:46; csrc/forest.hip;
+ * hypelcnn_amd/classic/forest.py) ---------------------------------------------------------------------------------------
+ * Training rows are x [n][ld] float32 (finite), labels y int32 [n] in 0..n_classes-1, n_classes <=
+ * HYPEL_FOREST_MAX_CLASSES (the LDS histogram [256][n_classes] int32 of hypel_forest_split_hist).  Every column is
+ * quantised once; splits are searched over bin boundaries with integer class histograms.  Integer atomics only, every
+ * choice among equals is a total order and every list is built by a prefix sum: two runs write identical bytes.
+ *
+ * hypel_forest_bin_edges_f32: one workgroup per column c < f.  With n_s = min(n, HYPEL_FOREST_EDGE_ROWS), the values
+ *   x[perm[i]][c] + 0.0f, i < n_s, are sorted (perm: int32 [>= n_s], distinct rows in [0, n) -- beyond the cap a seeded
+ *   subsample); for j = 1 .. n_bins-1 the value v at rank floor(j * n_s / n_bins) becomes an edge unless it equals the
+ *   previous edge or the largest sampled value.  edges [f][HYPEL_FOREST_MAX_EDGES] ascending, unused slots +inf;
+ *   n_edges [f].  2 <= n_bins <= 256.
+ * hypel_forest_bin_u8: bins[c * ldn + i] = the number of edges of column c that are < x[i][c] (feature-major uint8,
+ *   ldn >= n).  Hence bin <= t  <=>  x <= edges[c][t] for t < n_edges[c]: a grown node stores the raw float32 edge and
+ *   is served by the rule x[feature] <= threshold.
+ * Growth is level by level over all trees at once.  order (int32) holds, tree after tree, the tree's unique in-bag
+ * rows; weight int32 [n_trees][n] their bootstrap multiplicity.  An active node is four int32: (tree, start, count,
+ * node) = a segment order[start .. start + count) and the node's number.  cand int32 [n_active][max_features] are
+ * the node's candidate columns, distinct per node (drawn on the host), 1 <= max_features <= f.
+ * hypel_forest_split_hist: one workgroup per (active node a, slot s), record a * max_features + s: hist[bin][class] +=
+ *   weight over the node's rows for column cand[a][s]; for every boundary t in 0..254 with both sides non-empty
+ *   (weights nL, nR > 0; "left" = bin <= t)  score = (double)sum_k L_k^2 / (double)nL + (double)sum_k R_k^2 /
+ *   (double)nR, the sums of squares exact in int64, each of the two divisions and the addition rounded once, no
+ *   contraction.  Written: the largest score, its (lowest) bin, valid = 1; (0.0, -1, 0) when no boundary is valid or
+ *   count < 2.
+ * hypel_forest_split_apply: one workgroup per active node.  The best valid slot is the one with the largest score,
+ *   then the lower column index, then the lower bin.  The node is a LEAF when count < 2, fewer than two classes have
+ *   weight, no slot is valid, or level >= max_depth (<= HYPEL_FOREST_MAX_DEPTH); candidates are NOT redrawn when all
+ *   are invalid (scikit-learn keeps drawing until it has seen every column).  Node record, at index `node`:
+ *   feature (-1 leaf), thr_bin (-1), threshold = edges[feature][thr_bin] (0 for a leaf), left = right = -1 for a leaf,
+ *   node_tree, node_count (unique rows), node_weight, value[node][n_classes] = class weight / node weight in fp64 (one
+ *   division each).  A split node's segment is partitioned stably by bin <= thr_bin from order_in into order_out at the
+ *   same positions (the two buffers alternate level by level; a leaf's segment is not copied).  Then, in active-node
+ *   order, the r-th node that split gets left = node_base + 2r, right = left + 1 and the records (tree, start, nL,
+ *   left), (tree, start + nL, count - nL, right) at next_active[2r], [2r + 1] (room for 2 * n_active records);
+ *   counter[0] = 2 * (number of splits), which the host reads to size the next level, or -1 when a child's number
+ *   would reach node_capacity (nothing is written past it).  split_ws: int32 [n_active].
+ * Serving: a model is one array of hypel_forest_node_t over all trees -- tree t's root is node tree_off[t] (int32
+ *   [n_trees]).  A node with left < 0 is a leaf and ends the walk at row -1 - left of leaf_value (fp64
+ *   [n_leaves][n_classes]); otherwise the walk goes to node `left` when x[feature] <= threshold (float32 compare) and to
+ *   `right` if not; child indices are absolute and greater than their parent's (the walk is also bounded by n_nodes
+ *   steps).  Per row the leaf rows are summed in tree order in fp64, divided by n_trees, and the FIRST maximum wins.
+ *   The serving kernels do NOT check a model on the device: tree_off, child indices, leaf rows and feature values (a
+ *   column < f, or a scene code inside the p x p window) are the caller's to validate, as ForestClassifier._set_model
+ *   does on the host; a model that breaks them is read out of bounds.  The step bound limits the walk's length only.
+ * hypel_forest_predict_rows: rows x [n][ld], feature < f.  The label, class_labels[winner] (NULL: the index), goes to
+ *   out[i], or to out[y * raster_w + x] for points[i] = (x, y) like hypel_svm_vote; proba (optional) fp64
+ *   [n][n_classes] receives the means.
+ * hypel_forest_predict_scene: the same walk and vote for the p x p window with origin points[i] = (x, y) of the padded
+ *   scene casi [hp][wp][cc], lidar [hp][wp][cl] (the arguments of hypel_gather_patches_f32), without cutting the
+ *   patch: the feature field of scene_nodes[node] is 2 * e + a where a = 1 reads lidar and 0 casi, and e is the
+ *   element offset from the window origin's pixel in that array -- (py * wp + px) * cc + ch for patch feature (py * p + px) * (cc + cl) + ch,
+ *   ch < cc; (py * wp + px) * cl + ch - cc otherwise -- translated once when the model is uploaded.  The label goes
+ *   to out[y * raster_w + x]. */
+#define HYPEL_FOREST_EDGE_ROWS 16384
+#define HYPEL_FOREST_MAX_EDGES 255
+#define HYPEL_FOREST_MAX_CLASSES 32
+#define HYPEL_FOREST_MAX_DEPTH 64
+typedef struct { int32_t feature; float threshold; int32_t left; int32_t right; } hypel_forest_node_t;
+int hypel_forest_bin_edges_f32(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* perm, int32_t n_bins,
+                               float* edges, int32_t* n_edges, hypel_stream_t stream);
+int hypel_forest_bin_u8(const float* x, int64_t ld, int64_t n, int32_t f, const float* edges, const int32_t* n_edges,
+                        uint8_t* bins, int64_t ldn, hypel_stream_t stream);
+int hypel_forest_split_hist(const uint8_t* bins, int64_t ldn, const int32_t* y, const int32_t* weight, int64_t n,
+                            int32_t n_classes, const int32_t* order, const int32_t* active, int32_t n_active,
+                            const int32_t* cand, int32_t max_features, int32_t f, double* score, int32_t* best_bin,
+                            int32_t* valid, hypel_stream_t stream);
+int hypel_forest_split_apply(const uint8_t* bins, int64_t ldn, const int32_t* y, const int32_t* weight, int64_t n,
+                             int32_t n_classes, const int32_t* order_in, int32_t* order_out, const int32_t* active,
+                             int32_t n_active, const int32_t* cand, int32_t max_features, int32_t f, const double* score,
+                             const int32_t* best_bin, const int32_t* valid, const float* edges, int32_t level,
+                             int32_t max_depth, int32_t node_base, int32_t node_capacity, int32_t* feature,
+                             int32_t* thr_bin, float* threshold, int32_t* left, int32_t* right, int32_t* node_tree,
+                             int32_t* node_count, int32_t* node_weight, double* value, int32_t* split_ws,
+                             int32_t* next_active, int32_t* counter, hypel_stream_t stream);
+int hypel_forest_predict_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off, int32_t n_trees,
+                              const hypel_forest_node_t* nodes, int32_t n_nodes, const double* leaf_value,
+                              int32_t n_leaves, int32_t n_classes, const uint8_t* class_labels, const int32_t* points,
+                              uint8_t* out, int64_t raster_w, double* proba, hypel_stream_t stream);
+int hypel_forest_predict_scene(const float* casi, const float* lidar, int64_t hp, int64_t wp, int32_t cc, int32_t cl,
+                               const int32_t* points, int64_t n, int32_t p, const int32_t* tree_off, int32_t n_trees,
+                               const hypel_forest_node_t* scene_nodes, int32_t n_nodes, const double* leaf_value,
+                               int32_t n_leaves, int32_t n_classes, const uint8_t* class_labels, uint8_t* out,
+                               int64_t raster_w, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);

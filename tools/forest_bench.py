@@ -1,0 +1,143 @@
+"""Random forest (hypelcnn_amd.classic.forest) on a SyntheticDataLoader scene: fit, per-launch event times, and
+whole-scene serving on a synthetic scene of the real GRSS2013 size (349 x 1905 pixels, 144 + 1 bands) through both
+paths -- hypel_forest_predict_scene straight on the padded scene, next to its byte floor (the scene read once, the
+raster written once, at 6.2 TB/s, the streaming rate DESIGN.md uses), and the chunked hypel_gather_patches_f32 +
+hypel_forest_predict_rows it replaces (floor: every patch written once and read once) -- one JSON line.  Where
+scikit-learn is importable, RandomForestClassifier(n_jobs=16) on the CPU for scale: its fit, and its prediction of
+--sklearn_rows scene rows.
+
+    python tools/forest_bench.py [--path grss2013] [--trees 50] [--max_features 24] [--scene_h 349] [--scene_w 1905]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from hypelcnn_amd.backend import HipBackend  # noqa: E402
+from hypelcnn_amd.classic.forest import ForestClassifier  # noqa: E402
+from hypelcnn_amd.common.common_nn_ops import SceneArrays, get_loader_from_name  # noqa: E402
+from hypelcnn_amd.importer.InMemoryImporter import InMemoryImporter  # noqa: E402
+
+STREAM_BYTES_PER_S = 6.2e12
+
+
+class TimedBackend:
+    """HipBackend whose launches are event-timed one by one (synchronising: for the per-launch table only)."""
+
+    def __init__(self, inner):
+        self.inner, self.log = inner, []
+
+    def __getattr__(self, name):
+        return getattr(self.inner, name)
+
+    def call(self, name, *args):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream())
+        self.inner.call(name, *args)
+        b.record(torch.cuda.current_stream())
+        b.synchronize()
+        self.log.append((name, a.elapsed_time(b) * 1e3))
+
+
+def table(log):
+    rows = {}
+    for name, us in log:
+        r = rows.setdefault(name, {"launches": 0, "us": 0.0, "max_us": 0.0})
+        r["launches"] += 1
+        r["us"] += us
+        r["max_us"] = max(r["max_us"], us)
+    return {k: {kk: (round(vv, 1) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in rows.items()}
+
+
+def timed(fn, repeats=3):
+    """best wall time of `repeats` synchronised calls, after one warm-up"""
+    fn()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--path", default="grss2013")
+    ap.add_argument("--trees", type=int, default=50)
+    ap.add_argument("--max_features", type=int, default=24)
+    ap.add_argument("--neighborhood", type=int, default=2)
+    ap.add_argument("--scene_h", type=int, default=349)
+    ap.add_argument("--scene_w", type=int, default=1905)
+    ap.add_argument("--sklearn", type=int, default=1)
+    ap.add_argument("--sklearn_rows", type=int, default=20000)
+    args = ap.parse_args()
+    tr, _, va, _, _, _, _ = InMemoryImporter().read_data_set("SyntheticDataLoader", args.path, 0.1, 0, args.neighborhood,
+                                                             False)
+    X, y = tr.data.reshape(len(tr.data), -1), tr.labels
+    Xv, yv = va.data.reshape(len(va.data), -1), va.labels
+    hip = HipBackend()
+    kw = dict(n_estimators=args.trees, max_features=args.max_features)
+    result = {"tool": "forest_bench", "config": {"path": args.path, **kw}, "train_rows": int(len(X)),
+              "features": int(X.shape[1])}
+
+    fit_s = timed(lambda: ForestClassifier(backend=hip, **kw).fit(X, y), repeats=2)
+    model = ForestClassifier(backend=hip, **kw).fit(X, y)
+    result.update(fit_s=round(fit_s, 4), nodes=int(len(model.feature_)), levels=int(model.n_levels_),
+                  validation_oa=float((model.predict(Xv) == yv).mean()))
+    log = TimedBackend(hip)
+    ForestClassifier(backend=log, **kw).fit(X, y)
+    result["fit_launches"] = table(log.log)
+    result["fit_launch_sum_s"] = round(sum(us for _, us in log.log) * 1e-6, 4)
+
+    # whole-scene serving on a scene of the real size (the model's features are the same window of the same bands)
+    big = f"{args.path}:h={args.scene_h}:w={args.scene_w}"
+    data_set = get_loader_from_name("SyntheticDataLoader", big).load_data(args.neighborhood, False)
+    h, w = data_set.get_scene_shape()[:2]
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    targets = np.stack([xs.reshape(-1), ys.reshape(-1), np.zeros(xs.size, dtype=int)], axis=1)
+    arrays = SceneArrays()
+    arrays.feed(data_set, targets, hip)
+    raster = torch.zeros(h * w, dtype=torch.uint8, device=hip.device)
+    scene_bytes = 4 * (arrays.casi.numel() + (0 if arrays.lidar is None else arrays.lidar.numel())) + h * w
+    patch_bytes = 2 * 4 * h * w * X.shape[1] + h * w
+    direct_s = timed(lambda: model.predict_scene(arrays, raster, w, direct=True))
+    direct = raster.cpu().numpy().copy()
+    gather_s = timed(lambda: model.predict_scene(arrays, raster, w, direct=False), repeats=1)
+    same = bool(np.array_equal(direct, raster.cpu().numpy()))
+    result["scene"] = {"pixels": int(h * w), "direct_s": round(direct_s, 5), "gather_rows_s": round(gather_s, 5),
+                       "direct_floor_s": round(scene_bytes / STREAM_BYTES_PER_S, 6),
+                       "gather_rows_floor_s": round(patch_bytes / STREAM_BYTES_PER_S, 6),
+                       "direct_over_floor": round(direct_s / (scene_bytes / STREAM_BYTES_PER_S), 1),
+                       "gather_over_direct": round(gather_s / direct_s, 2), "same_raster": same}
+    if args.sklearn:
+        try:
+            from sklearn.ensemble import RandomForestClassifier
+        except ImportError:
+            RandomForestClassifier = None
+        if RandomForestClassifier is not None:
+            t0 = time.perf_counter()
+            sk = RandomForestClassifier(args.trees, max_features=min(args.max_features, X.shape[1]), n_jobs=16,
+                                        random_state=0).fit(X, y)
+            t1 = time.perf_counter()
+            pick = np.random.default_rng(0).choice(h * w, min(args.sklearn_rows, h * w), replace=False)
+            rows = np.stack([data_set.get_data_point(int(px), int(py)).reshape(-1) for px, py, _ in targets[pick]])
+            t2 = time.perf_counter()
+            ref = sk.predict(rows)
+            t3 = time.perf_counter()
+            result["sklearn_cpu"] = {"fit_s": round(t1 - t0, 3), "predict_rows": int(len(rows)),
+                                     "predict_s": round(t3 - t2, 3),
+                                     "scene_predict_s_scaled": round((t3 - t2) * h * w / len(rows), 1),
+                                     "validation_oa": float((sk.predict(Xv) == yv).mean()),
+                                     "label_agreement": float((ref == direct[pick]).mean())}
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
