@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import graph as G
-from .backend import GEMM_BM, MTILE_DTYPE, REDUCE_ENTRY_DTYPE, SEG_DTYPE, Ref
+from .backend import COPY_BLOCK_DTYPE, GEMM_BM, MTILE_DTYPE, REDUCE_ENTRY_DTYPE, SEG_DTYPE, Ref
 from .gemm_tables import SEG_PAIR_FLAG, GemmTables, Launch  # noqa: F401 (re-exported: tests and tools build tables through plan)
 
 STAT_CHUNK_ROWS = 256  # upper bound; see stat_chunk_rows()
@@ -241,6 +241,12 @@ class TowerPlan:
 
     def _ref(self, name, off=0):
         return Ref(self.buffers[name], off)
+
+    def _param_rel(self, ref):
+        """Element distance of `ref` from the flat parameter buffer: the base that table-driven launches address from."""
+        d = ref.ptr() - Ref(self.sess.params).ptr()
+        assert d % 4 == 0
+        return d // 4
 
     def storage_of(self, t):
         own = t.owner
@@ -625,14 +631,8 @@ class TowerPlan:
         need = sum((s_ - 1) * tables.groups[gi][2] * int(ldc) for gi, s_ in slices.items())
         sname = f"kslice:{kid}"
         self._alloc(sname, need)
-        base = Ref(self.sess.params)
-
-        def rel(ref, to):
-            d = ref.ptr() - to.ptr()
-            assert d % 4 == 0
-            return d // 4
-
-        scratch_from_c = rel(self._ref(sname), c_ref)
+        c_rel = self._param_rel(c_ref)
+        scratch_from_c = self._param_rel(self._ref(sname)) - c_rel
         out = GemmTables()
         entries, spos = [], 0
         for gi, (c_off, gs, rows) in enumerate(tables.groups):
@@ -645,12 +645,13 @@ class TowerPlan:
             out.add_group(c_off, parts[0], rows, key=tables.keys[gi], subkey=tables.subkeys[gi], tail=True)
             for i in range(1, s_):
                 out.add_group(scratch_from_c + spos + (i - 1) * region, parts[i], rows, flags=TILE_PLAIN, tail=True)
-            entries.append((rel(self._ref(sname, spos), base), rel(c_ref, base) + c_off, region, region, s_ - 1, 1))
+            entries.append((self._param_rel(self._ref(sname, spos)), c_rel + c_off, region, region, s_ - 1, 1))
             spos += (s_ - 1) * region
         earr = np.array(entries, REDUCE_ENTRY_DTYPE)
         e_t = self.be.upload(earr)
         self.tables.append(e_t)
-        red = Launch("reduce_splits_multi_sized_f32", (base, Ref(e_t), int(len(earr)), int(max(e[3] for e in entries))),
+        red = Launch("reduce_splits_multi_sized_f32", (Ref(self.sess.params), Ref(e_t), int(len(earr)),
+                                                       int(max(e[3] for e in entries))),
                      nbytes=4 * sum(cnt * (S + 2) for (_, _, _, cnt, S, _) in entries), tag="kslice-reduce")
         red.meta = {"kslices": {"tiles": len(entries), "slices": int(sum(slices.values())), "of": tag}}
         return out, red
@@ -877,14 +878,13 @@ class TowerPlan:
         """ONE hypel_copy_blocks_f32 in front of the forward pass (inserted at launch position `pos`): every
         (branch, tap) slice [Cin x cout] of every merged level goes to its offset / column range of the level's packed
         image (the variables keep their TF layouts)."""
-        from .backend import COPY_BLOCK_DTYPE
         base = Ref(self.sess.params)
         ents = []
         for idx, node in enumerate(self.tower.nodes):
             lay = self._level_layouts.get(idx)
             if lay is None or not lay.get("packed"):
                 continue
-            dst0 = (self._ref(lay["buf"]).ptr() - base.ptr()) // 4
+            dst0 = self._param_rel(self._ref(lay["buf"]))
             cin, co, C = lay["cin"], lay["co"], lay["C"]
             ents += [(w_, dst0 + lay["index"][(dy, dx)] * cin * C + col, cin, co, co, C, 0, 0)
                      for dy, dx, w_, col, _ in self._taps(self._columns(node), cin)]
@@ -1673,13 +1673,7 @@ class TowerPlan:
         if not pend:
             return
         base = Ref(self.sess.params)
-        base_ptr = base.ptr()
-
-        def rel(ref):
-            d = ref.ptr() - base_ptr
-            assert d % 4 == 0
-            return d // 4
-
+        rel = self._param_rel
         # scratch for the split slabs of this flush
         need = sum(e["S"] * e["slab"] for e in pend if e["S"] > 1)
         fid = self._wgrad_flushes
@@ -1789,7 +1783,6 @@ class TowerPlan:
             l.meta = {"splits": [int(S) for (_, _, _, _, S, _) in entries]}
             self.bwd.append(l)
         if unpacks:
-            from .backend import COPY_BLOCK_DTYPE
             u_t = self.be.upload(np.array(unpacks, COPY_BLOCK_DTYPE))
             self.tables.append(u_t)
             self.bwd.append(Launch("copy_blocks_f32", (base, Ref(u_t), len(unpacks), max(u[2] * u[3] for u in unpacks)),

@@ -6,7 +6,7 @@ emission is inherited from plan.TowerPlan."""
 import numpy as np
 
 from . import graph as G
-from .backend import REDUCE_ENTRY_DTYPE, Ref
+from .backend import COPY_BLOCK_DTYPE, LOSS_NONE, LOSS_TERM_DTYPE, REDUCE_ENTRY_DTYPE, Ref
 from .gemm_tables import GemmTables, Launch
 from .plan import Storage, TowerPlan, stat_chunk_rows
 
@@ -17,21 +17,17 @@ def gen_kernel_sizes(bands):
 
 # Same-weight applications of one phase as ONE application on the row-concatenated batch (no GAN network has batch
 # statistics, so D([real; fake]), enc([G(x); x; y; G(y)]), G([x; y]) and the feature-discriminator layers on 4N rows are
-# exact; cut_wrapper.py:301-339): fewer, longer launches, >= 2 resident blocks per CU for the generator kernels.
-BATCH_APPS = True
+# exact; cut_wrapper.py:301-339): fewer, longer launches, >= 2 resident blocks per CU for the generator kernels.  At most
+# this many applications share one launch.
 BATCH_APPS_MAX = 8
-# the per-block gradient slabs of every fused generator / dense-stack application of a train op in ONE reduction launch
-SLAB_REDUCE_MULTI = True
-# Two same-shaped networks with DIFFERENT variables (CycleGAN's G_x2y / G_y2x and D_x / D_y, cycle_gan_wrapper.py:82-124) whose
-# applications can run side by side share one launch: each takes its own share of the blocks (hypel_*_apps).  At the
-# Gulfport sizes every one of those applications is a latency chain on a fraction of the chip.
-BATCH_HETERO = True
 
 
 class PhasePlan(TowerPlan):
     """One train op of a GAN step (tfgan RunTrainOpsHook = one session.run): the sub-graph that the phase's loss
     terms depend on, differentiated w.r.t. the variable groups the phase trains.  `outputs` (no loss terms) gives a
     forward-only plan, e.g. "generate fresh fake data for the tensor pool"."""
+
+    _defer_bias_sums = True  # bias-gradient chunk sums wait for the slab-reduction launch of the train op
 
     def nominal_batch(self):
         from . import plan as _P
@@ -42,11 +38,10 @@ class PhasePlan(TowerPlan):
         self.train_groups = set(train_groups)
         self.outputs = list(outputs)
         # GAN-only state (set before TowerPlan.__init__, which runs _build)
-        self._defer_bias_sums = SLAB_REDUCE_MULTI  # bias-gradient chunk sums wait for the one slab-reduction launch
         self._bias_sum_entries = []  # reduce entries of those deferred bias gradients
         self._bias_sum_bufs = 0  # deferred chunk-sum buffers so far (numbers them)
         self._slab_sets = {}  # id(first weight) -> the per-block gradient slabs of one weight set (_defer_slab_reduce)
-        self._slab_apps = []  # *_apps launches whose slab arguments are resolved in _flush_slab_reduces
+        self._slab_launches = []  # backward launches whose slab arguments are resolved in _flush_slab_reduces
         self._slab_bufs = 0  # slab buffers so far (numbers them)
         self._groups = {}  # first member's node index -> the row-concatenated application of a unit (_fwd_group)
         self._gen_fwd = {}  # node index -> generator forward launch (the backward pass may make it keep activations)
@@ -104,17 +99,16 @@ class PhasePlan(TowerPlan):
         # gen(y, only_encoder)): the full launch writes it too (hypel_gan_generator_fwd_tap) and its backward takes the
         # gradient that reached it (hypel_gan_generator_bwd_tap) -- the encoder-only launches of those tensors disappear.
         self._taps, self._tapped = {}, {}  # id(full generator node) -> the encoder output it also produces; id(enc node) -> full node
-        # (only with the dependency-driven schedule of _schedule_units: in tower order an encoder application may precede the
-        # full one it would be read from)
-        if BATCH_APPS and hasattr(self.be, "gan_generator_tap_supported"):
-            fulls = {(id(n.weights[0]), id(n.src)): n for n in self.needed
-                     if isinstance(n, G.GeneratorNode) and not n.only_encoder}
-            for e in self.needed:
-                if isinstance(e, G.GeneratorNode) and e.only_encoder:
-                    f = fulls.get((id(e.weights[0]), id(e.src)))
-                    if f is not None and id(f) not in self._taps and self.be.gan_generator_tap_supported(e.src.c):
-                        self._taps[id(f)] = e.out
-                        self._tapped[id(e)] = f
+        # (the dependency-driven schedule of _schedule_units allows it: in tower order an encoder application may precede
+        # the full one it is read from)
+        fulls = {(id(n.weights[0]), id(n.src)): n for n in self.needed
+                 if isinstance(n, G.GeneratorNode) and not n.only_encoder}
+        for e in self.needed:
+            if isinstance(e, G.GeneratorNode) and e.only_encoder:
+                f = fulls.get((id(e.weights[0]), id(e.src)))
+                if f is not None and id(f) not in self._taps and self.be.gan_generator_tap_supported(e.src.c):
+                    self._taps[id(f)] = e.out
+                    self._tapped[id(e)] = f
         self._grad_needed = set()
         for n in self.needed:
             vs = self._node_vars(n)
@@ -241,8 +235,6 @@ class PhasePlan(TowerPlan):
     def _shape_signature(self, node):
         """Hashable identity of "a network of this shape" for the fused kernels that take several variable sets per launch
         (None: not one of them, or this application cannot join such a launch)."""
-        if not (BATCH_HETERO and SLAB_REDUCE_MULTI and hasattr(self.be, "gan_generator_blocks_apps")):
-            return None
         if isinstance(node, G.GeneratorNode):
             if id(node) in self._taps or not self.be.gan_generator_tap_supported(node.src.c):  # (matrix-core shapes only)
                 return None
@@ -275,8 +267,6 @@ class PhasePlan(TowerPlan):
         group run when the last of their inputs is ready; a grouping that would make the unit graph cyclic (CycleGAN:
         G_xy(G_yx(y)) next to G_xy(x)) is split by depth."""
         order = [(i, n) for i, n in enumerate(self.tower.nodes) if n in self.needed and id(n) not in self._tapped]
-        if not BATCH_APPS:
-            return [[u] for u in order]
         prod = {id(n.out): k for k, (_, n) in enumerate(order)}  # tensor owner -> position of its producer
         for k, (_, n) in enumerate(order):  # an encoder tap is produced by its full generator's launch
             if id(n) in self._taps:
@@ -334,10 +324,7 @@ class PhasePlan(TowerPlan):
                 out.append([order[k] for k in units[u]])
             return out
 
-        tries = [attempt(False), attempt(True)]
-        if BATCH_HETERO:
-            tries += [attempt(False, True), attempt(True, True)]
-        tries = [t for t in tries if t is not None]
+        tries = [t for t in (attempt(False), attempt(True), attempt(False, True), attempt(True, True)) if t is not None]
         return min(tries, key=len) if tries else [[u] for u in order]  # fewest units; ties: the plainer grouping
 
     def _address_order(self, unit):
@@ -365,21 +352,16 @@ class PhasePlan(TowerPlan):
         if all(st.buf == s0.buf and st.ld == s0.ld and st.c == s0.c and st.pixmap is None and
                st.ch_off == s0.ch_off + g * nb * s0.ld for g, st in enumerate(sts)):
             return Storage(s0.buf, nb * len(srcs), s0.ld, None, s0.ch_off, s0.c, 1), False
-        from .backend import COPY_BLOCK_DTYPE
         c = srcs[0].c
         name = f"cat:{tag}"
         self._alloc(name, len(srcs) * nb * c)
-        base = Ref(self.sess.params)
-
-        def rel(ref):
-            return (ref.ptr() - base.ptr()) // 4
-
+        rel = self._param_rel
         ents = [(rel(self._ref(st.buf, st.ch_off)), rel(self._ref(name, g * nb * c)), nb, c, st.ld, c, 0, 0)
                 for g, st in enumerate(sts)]
         t = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
         self.tables.append(t)
-        self.fwd.append(Launch("copy_blocks_f32", (base, Ref(t), len(ents), nb * c), nbytes=8 * len(srcs) * nb * c,
-                               tag="batch-gather"))
+        self.fwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), Ref(t), len(ents), nb * c),
+                               nbytes=8 * len(srcs) * nb * c, tag="batch-gather"))
         return Storage(name, nb * len(srcs), c, None, 0, c, 1), True
 
     def _fwd_group(self, unit):
@@ -497,12 +479,7 @@ class PhasePlan(TowerPlan):
                 for t in srcs:
                     self.grad_written[id(t.owner)] = True
             else:
-                from .backend import COPY_BLOCK_DTYPE
-                base = Ref(self.sess.params)
-
-                def rel(ref):
-                    return (ref.ptr() - base.ptr()) // 4
-
+                rel = self._param_rel
                 c = srcs[0].c
                 scatter = "g:" + grp["cat"].buf
                 ents = []
@@ -514,49 +491,39 @@ class PhasePlan(TowerPlan):
                                  gst.ld, acc, 0))
                 tbl = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
                 self.tables.append(tbl)
-                self.bwd.append(Launch("copy_blocks_f32", (base, Ref(tbl), len(ents), nb0 * c), nbytes=8 * len(ents) * nb0 * c,
-                                       tag="batch-scatter"))
+                self.bwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), Ref(tbl), len(ents), nb0 * c),
+                                       nbytes=8 * len(ents) * nb0 * c, tag="batch-scatter"))
 
     # ---- per-block gradient slabs of the fused kernels: reduced once per train op ----
-    def _defer_slab_reduce(self, launch, pos_w, pos_b, blocks, w0, w_stride, w_count, b0, b_stride, b_count, acc):
-        """The backward kernel `launch` leaves `blocks` filter / bias gradient slabs (arguments pos_w / pos_b).  Instead of
-        one reduction launch per application, every application of one weight set appends its slabs to that set's
-        region and ONE hypel_reduce_splits_wave_multi_f32 at the end of the backward pass sums each region (one entry per
-        weight set and kind: two entries never write the same gradient)."""
-        st = self._slab_sets.setdefault(id(w0), dict(w0=w0, b0=b0, w=(w_stride, w_count), b=(b_stride, b_count), acc=acc,
-                                                     apps=[], blocks=0))
-        st["apps"].append((launch, pos_w, pos_b, st["blocks"]))
-        st["blocks"] += blocks
-
-    def _defer_slab_reduce_apps(self, launch, pos_w, pos_b, pos_ws, pos_bs, bpa, nodes, w_stride, w_count, b_stride, b_count):
-        """The *_apps form: `launch` leaves `bpa` slabs for each of its variable sets (`nodes`: one application node per
-        set).  Every set's slabs still go to that set's own region; the launch reaches set g's first slab by a stride from
-        set 0's (arguments pos_ws / pos_bs), known once the regions are laid out."""
-        sets = self._slab_sets
+    def _defer_slab_reduce(self, launch, nodes, pos_w, pos_b, blocks, w_geom, b_geom, pos_strides=None):
+        """The backward kernel `launch` leaves `blocks` filter / bias gradient slabs (arguments pos_w / pos_b; geometry
+        (stride, count) per slab) for each of its variable sets -- `nodes`: one application node per set, two for the
+        *_apps form.  Instead of one reduction launch per application, every application of one weight set appends its
+        slabs to that set's region and ONE hypel_reduce_splits_wave_multi_f32 at the end of the backward pass sums each
+        region (one entry per weight set and kind: two entries never write the same gradient).  An *_apps launch reaches
+        its second set's first slab by a stride from the first set's (arguments pos_strides), known once the regions are
+        laid out."""
         where = []
         for nd in nodes:
-            w0, b0 = nd.weights[0], nd.biases[0]
-            wacc = self._param_acc(w0)
+            acc = self._param_acc(nd.weights[0])
             for v in nd.weights[1:] + nd.biases:
                 self._param_acc(v)
-            st = sets.setdefault(id(w0), dict(w0=w0, b0=b0, w=(w_stride, w_count), b=(b_stride, b_count), acc=wacc, apps=[],
-                                             blocks=0))
-            where.append((id(w0), st["blocks"]))
-            st["blocks"] += bpa
-        self._slab_apps.append((launch, pos_w, pos_b, pos_ws, pos_bs, where))
+            st = self._slab_sets.setdefault(id(nd.weights[0]), dict(w0=nd.weights[0], b0=nd.biases[0], w=w_geom, b=b_geom,
+                                                                     acc=acc, blocks=0))
+            where.append((st, st["blocks"]))
+            st["blocks"] += blocks
+        self._slab_launches.append((launch, pos_w, pos_b, pos_strides, where))
 
     def _flush_slab_reduces(self):
         sets, self._slab_sets = self._slab_sets, {}
+        launches, self._slab_launches = self._slab_launches, []
         bias_entries, self._bias_sum_entries = self._bias_sum_entries, []
         if not sets and not bias_entries:
             return
-        base = Ref(self.sess.params)
-
-        def rel(ref):
-            return (ref.ptr() - base.ptr()) // 4
-
+        base, rel = Ref(self.sess.params), self._param_rel
         # Two entries of one launch must not write the same output (include/hypel.h): a BN-less layer applied twice as
-        # separate units (no row-concatenated batch) leaves two chunk-sum entries for ONE bias gradient, acc = 0 then 1.
+        # separate units (to its own output: no row-concatenated batch) leaves two chunk-sum entries for ONE bias gradient,
+        # acc = 0 then 1.
         # Entry k of an output goes to round k; every round is its own launch, in order.
         ents, total = [], 0
         later, seen = [], {}
@@ -571,34 +538,24 @@ class PhasePlan(TowerPlan):
                 while len(later) < r:
                     later.append([])
                 later[r - 1].append(e)
-        for k, st in enumerate(sets.values()):
+        for st in sets.values():
             fid = self._slab_bufs
             self._slab_bufs += 1
-            names = st["names"] = {}
             for kind, var in (("w", st["w0"]), ("b", st["b0"])):
                 stride, count = st[kind]
-                names[kind] = f"slabs_{kind}:{fid}"
-                self._alloc(names[kind], st["blocks"] * stride)
-                ents.append((rel(self._ref(names[kind])), rel(self._g(var)), stride, count, st["blocks"], st["acc"]))
+                st[kind + "_buf"] = f"slabs_{kind}:{fid}"
+                self._alloc(st[kind + "_buf"], st["blocks"] * stride)
+                ents.append((rel(self._ref(st[kind + "_buf"])), rel(self._g(var)), stride, count, st["blocks"], st["acc"]))
                 total += count
-            for launch, pos_w, pos_b, b0 in st["apps"]:
-                args = list(launch.args)
-                args[pos_w] = self._ref(names["w"], b0 * st["w"][0])
-                args[pos_b] = self._ref(names["b"], b0 * st["b"][0])
-                launch.args = tuple(args)
-        for launch, pos_w, pos_b, pos_ws, pos_bs, where in self._slab_apps:
-            first = [(self._ref(sets[sid]["names"]["w"], b0 * sets[sid]["w"][0]),
-                      self._ref(sets[sid]["names"]["b"], b0 * sets[sid]["b"][0])) for sid, b0 in where]
+        for launch, pos_w, pos_b, pos_strides, where in launches:
+            first = [(self._ref(st["w_buf"], b0 * st["w"][0]), self._ref(st["b_buf"], b0 * st["b"][0])) for st, b0 in where]
             args = list(launch.args)
             args[pos_w], args[pos_b] = first[0]
-            args[pos_ws] = (first[1][0].ptr() - first[0][0].ptr()) // 4
-            args[pos_bs] = (first[1][1].ptr() - first[0][1].ptr()) // 4
+            if pos_strides is not None:  # the second variable set's first slabs, as element distances from the first set's
+                args[pos_strides[0]] = (first[1][0].ptr() - first[0][0].ptr()) // 4
+                args[pos_strides[1]] = (first[1][1].ptr() - first[0][1].ptr()) // 4
             launch.args = tuple(args)
-        self._slab_apps = []
-        e_t = self.be.upload(np.array(ents, REDUCE_ENTRY_DTYPE))
-        self.tables.append(e_t)
-        self.bwd.append(Launch("reduce_splits_wave_multi_f32", (base, Ref(e_t), len(ents), total), tag="slab-reduce"))
-        for rnd in later:
+        for rnd in [ents] + later:
             e_t = self.be.upload(np.array(rnd, REDUCE_ENTRY_DTYPE))
             self.tables.append(e_t)
             self.bwd.append(Launch("reduce_splits_wave_multi_f32", (base, Ref(e_t), len(rnd), sum(e[3] for e in rnd)),
@@ -609,6 +566,33 @@ class PhasePlan(TowerPlan):
         """element distance of var1 from var0 in the flat parameter buffer"""
         return int(var1.offset) - int(var0.offset)
 
+    # ---- fused stacks (generator, dense stack): what their handlers share ----
+    def _stack_fwd_io(self, idx, node):
+        """(input, its row stride), (new output, its row stride) of a fused stack's forward launch."""
+        s_st = self.storage_of(node.src)
+        st = self._new_value(node.out, f"z:{idx}")
+        return (self._ref(s_st.buf, s_st.ch_off), s_st.ld), (self._ref(st.buf), st.ld)
+
+    def _stack_bwd_io(self, node):
+        """(input, row stride), (output gradient, row stride), (input gradient or None, row stride, accumulate) of a
+        fused stack's backward launch."""
+        s_st = self.storage_of(node.src)
+        z_st = self.storage[id(node.out)]
+        return (self._ref(s_st.buf, s_st.ch_off), s_st.ld), (self._ref("g:" + z_st.buf), z_st.ld), self._grad_ref(node.src)
+
+    def _stack_slabs(self, launch, node, pos_w, blocks, w_geom, b_geom, scratch):
+        """Where the backward launch of a fused stack leaves its per-block filter / bias gradient slabs (arguments pos_w,
+        pos_w + 1): the regions that the train op's slab reduction sums, or shared scratch when the phase does not train
+        these weights."""
+        apps = getattr(node, "app_nodes", None)
+        if self._trains(node.weights):
+            n_apps = len(apps) if apps is not None else 1
+            self._defer_slab_reduce(launch, apps or [node], pos_w, pos_w + 1, blocks // n_apps, w_geom, b_geom,
+                                    (8, 9) if apps is not None else None)  # (hypel.h: slab strides of both *_bwd_apps)
+        else:
+            self._scratch(launch, pos_w, f"scratch_{scratch}_w", blocks * w_geom[0])
+            self._scratch(launch, pos_w + 1, f"scratch_{scratch}_b", blocks * b_geom[0])
+
     # ---- fused generator ----
     def _gen_refs(self, node):
         self._assert_contiguous(node.weights)
@@ -616,46 +600,36 @@ class PhasePlan(TowerPlan):
         return node.weights[0], node.biases[0], sum(w.size for w in node.weights)
 
     def _fwd_generator(self, idx, node):
-        src, out = node.src, node.out
-        s_st = self.storage_of(src)
-        st = self._new_value(out, f"z:{idx}")
+        src = node.src
+        x, z = self._stack_fwd_io(idx, node)
         w0, b0, _ = self._gen_refs(node)
         tap = self._taps.get(id(node))
         apps = getattr(node, "app_nodes", None)
         if apps is not None:  # two generators of one shape, each on its half of the rows
             w1, b1, _ = self._gen_refs(apps[1])
-            l = Launch("gan_generator_fwd_apps", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self.nb // len(apps), len(apps),
-                                                  self._rel(w0, w1), self._rel(b0, b1), src.c, self._p(w0), self._p(b0),
-                                                  int(node.only_encoder), self._ref(st.buf), st.ld, None),
+            l = Launch("gan_generator_fwd_apps", (*x, self.nb // len(apps), len(apps), self._rel(w0, w1), self._rel(b0, b1),
+                                                  src.c, self._p(w0), self._p(b0), int(node.only_encoder), *z, None),
                        nbytes=8 * self.nb * src.c, tag="gen-fwd-apps")
         elif tap is not None:
             # the encoder-only application on the same input is this launch's n_4
             t_st = self._new_value(tap, f"ztap:{idx}")
-            l = Launch("gan_generator_fwd_tap", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self.nb, src.c, self._p(w0),
-                                                 self._p(b0), self._ref(st.buf), st.ld, self._ref(t_st.buf), t_st.ld, None),
-                       nbytes=12 * self.nb * src.c, tag="gen-fwd+enc")
+            l = Launch("gan_generator_fwd_tap", (*x, self.nb, src.c, self._p(w0), self._p(b0), *z, self._ref(t_st.buf),
+                                                 t_st.ld, None), nbytes=12 * self.nb * src.c, tag="gen-fwd+enc")
         else:
-            l = Launch("gan_generator_fwd", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self.nb, src.c, self._p(w0),
-                                             self._p(b0), int(node.only_encoder), self._ref(st.buf), st.ld),
+            l = Launch("gan_generator_fwd", (*x, self.nb, src.c, self._p(w0), self._p(b0), int(node.only_encoder), *z),
                        nbytes=8 * self.nb * src.c, tag="gen-fwd")
         self.fwd.append(l)
         self._gen_fwd[idx] = l  # _bwd_generator turns it into the activation-keeping form when a backward pass follows
 
     def _bwd_generator(self, idx, node):
-        src, out = node.src, node.out
-        s_st = self.storage_of(src)
-        z_st = self.storage[id(out)]
+        src = node.src
+        x, dy, dx = self._stack_bwd_io(node)
         w0, b0, wtotal = self._gen_refs(node)
         apps = getattr(node, "app_nodes", None)
         n_apps = len(apps) if apps is not None else 1
         blocks = self.be.gan_generator_blocks(self.nb) if apps is None else \
             self.be.gan_generator_blocks_apps(self.nb // n_apps, n_apps)
-        dx, lddx, acc = None, 0, 0
-        if self._needs_grad(src):
-            gst, acc = self._grad_target(src)
-            dx, lddx = self._ref(gst.buf, gst.ch_off), gst.ld
         tap = self._taps.get(id(node))
-        tap_grad = tap is not None and self.grad_written.get(id(tap), False)
         keep_n = n_apps * self.be.gan_generator_keep_floats(self.nb // n_apps, src.c, int(node.only_encoder))
         kref = None
         if keep_n > 0:
@@ -671,50 +645,27 @@ class PhasePlan(TowerPlan):
             f.bytes += 4 * keep_n
         if apps is not None:
             w1, b1, _ = self._gen_refs(apps[1])
-            l1 = Launch("gan_generator_bwd_apps", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self._ref("g:" + z_st.buf),
-                                                   z_st.ld, self.nb // n_apps, n_apps, self._rel(w0, w1), self._rel(b0, b1), 0,
-                                                   0, src.c, self._p(w0), self._p(b0), int(node.only_encoder), dx, lddx, acc,
-                                                   None, None, kref),
-                        nbytes=12 * self.nb * src.c + 4 * keep_n, tag="gen-bwd-apps")
-            self.bwd.append(l1)
-            if self._trains(node.weights):
-                self._defer_slab_reduce_apps(l1, 17, 18, 8, 9, blocks // n_apps, apps, wtotal, wtotal, 8, 7)
-            else:
-                self._scratch(l1, 17, "scratch_gen_w", blocks * wtotal)
-                self._scratch(l1, 18, "scratch_gen_b", blocks * 8)
-            return
-        if tap_grad:
+            l1 = Launch("gan_generator_bwd_apps", (*x, *dy, self.nb // n_apps, n_apps, self._rel(w0, w1), self._rel(b0, b1), 0,
+                                                   0, src.c, self._p(w0), self._p(b0), int(node.only_encoder), *dx, None, None,
+                                                   kref), nbytes=12 * self.nb * src.c + 4 * keep_n, tag="gen-bwd-apps")
+            pos_w = 17
+        elif tap is not None and self.grad_written.get(id(tap), False):
             # one backward pass for the full application and the encoder-only one read from it: the gradient that reached
             # the encoder output joins dn_4
             t_st = self.storage[id(tap)]
-            l1 = Launch("gan_generator_bwd_tap", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self._ref("g:" + z_st.buf),
-                                                  z_st.ld, self._ref("g:" + t_st.buf, t_st.ch_off), t_st.ld, self.nb, src.c,
-                                                  self._p(w0), self._p(b0), dx, lddx, acc, None, None, kref),
+            l1 = Launch("gan_generator_bwd_tap", (*x, *dy, self._ref("g:" + t_st.buf, t_st.ch_off), t_st.ld, self.nb, src.c,
+                                                  self._p(w0), self._p(b0), *dx, None, None, kref),
                         nbytes=16 * self.nb * src.c + 4 * keep_n, tag="gen-bwd+enc")
-            pw_pos, pb_pos = 13, 14
+            pos_w = 13
         else:
-            l1 = Launch("gan_generator_bwd", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self._ref("g:" + z_st.buf),
-                                              z_st.ld, self.nb, src.c, self._p(w0), self._p(b0), int(node.only_encoder),
-                                              dx, lddx, acc, None, None), nbytes=12 * self.nb * src.c, tag="gen-bwd")
+            l1 = Launch("gan_generator_bwd", (*x, *dy, self.nb, src.c, self._p(w0), self._p(b0), int(node.only_encoder),
+                                              *dx, None, None), nbytes=12 * self.nb * src.c, tag="gen-bwd")
             if kref is not None:
                 l1.name, l1.args = "gan_generator_bwd_kept", tuple(l1.args) + (kref,)
                 l1.bytes += 4 * keep_n
-            pw_pos, pb_pos = 12, 13
+            pos_w = 12
         self.bwd.append(l1)
-        if self._trains(node.weights):
-            wacc = self._param_acc(w0)
-            if SLAB_REDUCE_MULTI:
-                self._defer_slab_reduce(l1, pw_pos, pb_pos, blocks, w0, wtotal, wtotal, b0, 8, 7, wacc)
-                return
-        self._scratch(l1, pw_pos, "scratch_gen_w", blocks * wtotal)
-        self._scratch(l1, pb_pos, "scratch_gen_b", blocks * 8)
-        if self._trains(node.weights):
-            # filter and bias slabs in one launch
-            l2 = Launch("reduce_splits_pair_f32", (None, wtotal, wtotal, self._g(w0), None, 8, 7, self._g(b0), blocks, wacc),
-                        tag="gen-dw+db")
-            self._scratch(l2, 0, "scratch_gen_w", blocks * wtotal)
-            self._scratch(l2, 4, "scratch_gen_b", blocks * 8)
-            self.bwd.append(l2)
+        self._stack_slabs(l1, node, pos_w, blocks, (wtotal, wtotal), (8, 7), "gen")
 
     # ---- fused fully-connected stack (narrow discriminators) ----
     def _densestack_args(self, node):
@@ -728,75 +679,40 @@ class PhasePlan(TowerPlan):
 
     def _fwd_densestack(self, idx, node):
         src, out = node.src, node.out
-        s_st = self.storage_of(src)
-        st = self._new_value(out, f"z:{idx}")
+        x, z = self._stack_fwd_io(idx, node)
+        w0, b0 = node.weights[0], node.biases[0]
         macs = sum(w.size for w in node.weights)
         apps = getattr(node, "app_nodes", None)
         if apps is not None:  # two critics of one shape, each on its half of the rows
             self._densestack_args(apps[1])
-            self.fwd.append(Launch("dense_stack_fwd_apps", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self.nb // len(apps),
-                                                            len(apps), self._rel(node.weights[0], apps[1].weights[0]),
-                                                            self._rel(node.biases[0], apps[1].biases[0]),
-                                                            *self._densestack_args(node), self._p(node.weights[0]),
-                                                            self._p(node.biases[0]), self._ref(st.buf), st.ld),
-                                   flops=2 * self.nb * macs, nbytes=4 * self.nb * (src.c + out.c),
-                                   tag="dense-stack-fwd-apps"))
-            return
-        self.fwd.append(Launch("dense_stack_fwd", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self.nb,
-                                                   *self._densestack_args(node), self._p(node.weights[0]),
-                                                   self._p(node.biases[0]), self._ref(st.buf), st.ld),
-                               flops=2 * self.nb * macs, nbytes=4 * self.nb * (src.c + out.c), tag="dense-stack-fwd"))
+            l = Launch("dense_stack_fwd_apps", (*x, self.nb // len(apps), len(apps), self._rel(w0, apps[1].weights[0]),
+                                                self._rel(b0, apps[1].biases[0]), *self._densestack_args(node), self._p(w0),
+                                                self._p(b0), *z), tag="dense-stack-fwd-apps")
+        else:
+            l = Launch("dense_stack_fwd", (*x, self.nb, *self._densestack_args(node), self._p(w0), self._p(b0), *z),
+                       tag="dense-stack-fwd")
+        l.flops, l.bytes = 2 * self.nb * macs, 4 * self.nb * (src.c + out.c)
+        self.fwd.append(l)
 
     def _bwd_densestack(self, idx, node):
         src, out = node.src, node.out
-        s_st = self.storage_of(src)
-        z_st = self.storage[id(out)]
+        x, dy, dx = self._stack_bwd_io(node)
         w0, b0 = node.weights[0], node.biases[0]
         wtotal, btotal = sum(w.size for w in node.weights), sum(b.size for b in node.biases)
-        blocks = self.be.dense_stack_blocks(self.nb)
-        dx, lddx, acc = None, 0, 0
-        if self._needs_grad(src):
-            gst, acc = self._grad_target(src)
-            dx, lddx = self._ref(gst.buf, gst.ch_off), gst.ld
         apps = getattr(node, "app_nodes", None)
         if apps is not None:
             n_apps = len(apps)
             blocks = self.be.dense_stack_blocks_apps(self.nb // n_apps, n_apps)
-            l1 = Launch("dense_stack_bwd_apps", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self._ref("g:" + z_st.buf),
-                                                 z_st.ld, self.nb // n_apps, n_apps, self._rel(w0, apps[1].weights[0]),
+            l1 = Launch("dense_stack_bwd_apps", (*x, *dy, self.nb // n_apps, n_apps, self._rel(w0, apps[1].weights[0]),
                                                  self._rel(b0, apps[1].biases[0]), 0, 0, *self._densestack_args(node),
-                                                 self._p(w0), self._p(b0), dx, lddx, acc, None, None),
-                        flops=6 * self.nb * wtotal, nbytes=4 * self.nb * (2 * src.c + out.c), tag="dense-stack-bwd-apps")
-            n_args = len(l1.args)
-            self.bwd.append(l1)
-            if self._trains(node.weights):
-                self._defer_slab_reduce_apps(l1, n_args - 2, n_args - 1, 8, 9, blocks // n_apps, apps, wtotal, wtotal, btotal,
-                                             btotal)
-            else:
-                self._scratch(l1, n_args - 2, "scratch_ds_w", blocks * wtotal)
-                self._scratch(l1, n_args - 1, "scratch_ds_b", blocks * btotal)
-            return
-        l1 = Launch("dense_stack_bwd", (self._ref(s_st.buf, s_st.ch_off), s_st.ld, self._ref("g:" + z_st.buf), z_st.ld,
-                                        self.nb, *self._densestack_args(node), self._p(w0), self._p(b0), dx, lddx, acc, None,
-                                        None), flops=6 * self.nb * wtotal, nbytes=4 * self.nb * (2 * src.c + out.c),
-                    tag="dense-stack-bwd")
-        n_args = len(l1.args)
+                                                 self._p(w0), self._p(b0), *dx, None, None), tag="dense-stack-bwd-apps")
+        else:
+            blocks = self.be.dense_stack_blocks(self.nb)
+            l1 = Launch("dense_stack_bwd", (*x, *dy, self.nb, *self._densestack_args(node), self._p(w0), self._p(b0), *dx,
+                                            None, None), tag="dense-stack-bwd")
+        l1.flops, l1.bytes = 6 * self.nb * wtotal, 4 * self.nb * (2 * src.c + out.c)
         self.bwd.append(l1)
-        if self._trains(node.weights):
-            wacc = self._param_acc(w0)
-            for v in node.weights[1:] + node.biases:
-                self._param_acc(v)
-            if SLAB_REDUCE_MULTI:
-                self._defer_slab_reduce(l1, n_args - 2, n_args - 1, blocks, w0, wtotal, wtotal, b0, btotal, btotal, wacc)
-                return
-        self._scratch(l1, n_args - 2, "scratch_ds_w", blocks * wtotal)
-        self._scratch(l1, n_args - 1, "scratch_ds_b", blocks * btotal)
-        if self._trains(node.weights):
-            l2 = Launch("reduce_splits_pair_f32", (None, wtotal, wtotal, self._g(w0), None, btotal, btotal, self._g(b0),
-                                                   blocks, wacc), tag="ds-dw+db")
-            self._scratch(l2, 0, "scratch_ds_w", blocks * wtotal)
-            self._scratch(l2, 4, "scratch_ds_b", blocks * btotal)
-            self.bwd.append(l2)
+        self._stack_slabs(l1, node, len(l1.args) - 2, blocks, (wtotal, wtotal), (btotal, btotal), "ds")
 
     # ---- feature stack (global l2 normalise per slice, stacked) ----
     def _fwd_featstack(self, idx, node):
@@ -926,19 +842,12 @@ class PhasePlan(TowerPlan):
         self._term_batch.append(t)
 
     def _flush_loss_terms(self):
-        from .backend import LOSS_NONE, LOSS_TERM_DTYPE
         batch, self._term_batch = self._term_batch, []
         if not batch:
             return
-        base = Ref(self.sess.params)
-        base_ptr = base.ptr()
 
         def rel(ref):
-            if ref is None:
-                return LOSS_NONE
-            d = ref.ptr() - base_ptr
-            assert d % 4 == 0
-            return d // 4
+            return LOSS_NONE if ref is None else self._param_rel(ref)
 
         first = self._n_loss_slots
         self._n_loss_slots += len(batch)
@@ -947,7 +856,7 @@ class PhasePlan(TowerPlan):
                          first + k) for k, t in enumerate(batch)], LOSS_TERM_DTYPE)
         e_t = self.be.upload(arr)
         self.tables.append(e_t)
-        l = Launch("loss_terms_slots", (base, Ref(e_t), len(batch), None), tag=f"loss-terms/{len(batch)}")
+        l = Launch("loss_terms_slots", (Ref(self.sess.params), Ref(e_t), len(batch), None), tag=f"loss-terms/{len(batch)}")
         self._loss_slot(l, 3)
         self._term_list.append(l)
 

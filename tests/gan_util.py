@@ -79,3 +79,50 @@ def check_phase_gradients(cfg, ops, params, x, y, tol=2e-4):
             worst = max(worst, err)
             assert err < tol, (phase.name, k, err)
     return worst
+
+
+class TwiceAppliedLayer:
+    """h2 = L(L(x)), L = one fully connected layer [width -> width] with bias and leaky-ReLU(0.2), no normaliser; the train
+    op minimises mean((h2 - 1)^2) w.r.t. L's weights and bias.  The second application reads the first: the two cannot be
+    one row-concatenated application, so the shared bias gets two deferred chunk-sum entries."""
+
+    def __init__(self, backend, nb=6, width=8, seed=11):
+        from hypelcnn_amd import graph as G
+        self.nb = nb
+        tower, x, _ = C.new_gan_tower(width)
+        with G.variable_scope("Model"), G.variable_scope("Discriminator"):
+            h1 = G.fully_connected(x, width, scope="fc", activation_fn=G.leaky_relu(0.2), normalizer_fn=None)
+            h2 = G.fully_connected(h1, width, scope="fc", activation_fn=G.leaky_relu(0.2), normalizer_fn=None)
+        self.sess = C.GanContext(tower, backend).session()
+        self.names = {"w": "Model/Discriminator/fc/weights", "b": "Model/Discriminator/fc/biases"}
+        assert sorted(self.sess.variable_names()) == sorted(self.names.values())
+        rng = np.random.default_rng(seed)
+        self.w = rng.normal(0.0, 0.5, (width, width)).astype(np.float32).astype(np.float64)
+        self.b = rng.normal(0.0, 0.5, width).astype(np.float32).astype(np.float64)
+        self.x = rng.normal(0.0, 1.0, (nb, width)).astype(np.float32).astype(np.float64)
+        self.sess.set_variable(self.names["w"], self.w)
+        self.sess.set_variable(self.names["b"], self.b)
+        self.ct = self.sess.compile_phase(tower, nb, terms=[G.LossTerm("mean_sq", h2, target=1.0)],
+                                          train_groups=["Model/Discriminator"], key="twice")
+
+    def run(self):
+        """(loss, {"w": dW, "b": db}) of the compiled train op."""
+        self.ct.set_input("x", torch.as_tensor(self.x, dtype=torch.float32).to(self.sess.params.device))
+        self.ct.forward_backward()
+        return self.ct.loss_value(), {k: self.sess.get_gradient(n) for k, n in self.names.items()}
+
+    def reference(self):
+        """The same in float64 NumPy."""
+        def lrelu(z):
+            return np.where(z > 0, z, 0.2 * z)
+
+        def dlrelu(z):
+            return np.where(z > 0, 1.0, 0.2)
+
+        z1 = self.x @ self.w + self.b
+        h1 = lrelu(z1)
+        z2 = h1 @ self.w + self.b
+        h2 = lrelu(z2)
+        dz2 = 2.0 * (h2 - 1.0) / h2.size * dlrelu(z2)
+        dz1 = dz2 @ self.w.T * dlrelu(z1)
+        return float(np.mean((h2 - 1.0) ** 2)), {"w": h1.T @ dz2 + self.x.T @ dz1, "b": dz2.sum(0) + dz1.sum(0)}

@@ -29,6 +29,10 @@ def test_phase_gradients_match_oracle(kind, bands, patches):
     sess = ops.ctx.session()
     U.inject(sess, params)
     U.check_phase_gradients(cfg, ops, params, x, y, tol=5e-5)
+    for phase in loss.phases:  # every train op sums its gradient slabs in slab-reduce launches, none per application
+        plan = ops._compiled(sess, phase, n).plan
+        assert not any(l.name == "reduce_splits_pair_f32" for l in plan.fwd + plan.bwd), phase.name
+        assert not plan.train_groups or any(l.tag == "slab-reduce" for l in plan.bwd), phase.name
 
 
 @pytest.mark.parametrize("kind", ["cycle_gan", "cut_x2y"])
@@ -97,87 +101,74 @@ def _phase_launches(ops, sess, n):
     return out
 
 
+# launches per train op of the default plans at n = 6 (the tower-order, one-reduce-per-application form they replaced
+# took more than twice as many for CUT)
+_BATCHED_LAUNCHES = {"cut_x2y": {"gen": 31, "dis": 8, "feat": 25},
+                     "cycle_gan": {"gen": 9, "dis": 6},
+                     "dcl_gan": {"x2y:gen": 31, "x2y:dis": 8, "x2y:feat": 25, "y2x:gen": 31, "y2x:dis": 8, "y2x:feat": 25}}
+
+
 @pytest.mark.parametrize("kind,bands", [("cut_x2y", 24), ("cycle_gan", 16), ("dcl_gan", 16)])
-def test_same_weight_applications_run_as_one_row_concatenated_application(monkeypatch, kind, bands):
-    """Round 4 (plan_gan.PhasePlan._schedule_units): the same-weight applications of a train op -- G([x; y]), enc on the four
+def test_same_weight_applications_run_as_one_row_concatenated_application(kind, bands):
+    """plan_gan.PhasePlan._schedule_units: the same-weight applications of a train op -- G([x; y]), enc on the four
     inputs of CUT, D([real; fake]), the feature-discriminator layers, the feature stack with per-application norms -- run
     as ONE application on the row-concatenated batch, and every per-block gradient slab of the op is summed by one launch.
-    Fewer launches, same losses and gradients as the oracle; the unbatched form stays available and agrees too.
+    Few launches (their number is pinned), same losses and gradients as the oracle.
     CycleGAN's G_xy(G_yx(y)) next to G_xy(x) must NOT be grouped (the unit graph would be cyclic)."""
-    from hypelcnn_amd import plan_gan
     n = 6
     cfg = OG.GanConfig(kind, bands, patches=4 if bands == 16 else 6, max_steps=20)
     params = U.fp32(OG.init_gan_params(kind, bands, np.random.default_rng(2), patches=cfg.patches, dtype=np.float64,
                                        zero_generator=False))
     x, y = _data(n, bands, 4)
-    counts = {}
-    for batched in (True, False):
-        monkeypatch.setattr(plan_gan, "BATCH_APPS", batched)
-        monkeypatch.setattr(plan_gan, "SLAB_REDUCE_MULTI", batched)
-        wrapper, model, loss, ops = U.build(cfg, n, EmuBackend())
-        sess = ops.ctx.session()
-        U.inject(sess, params)
-        U.check_phase_gradients(cfg, ops, params, x, y, tol=5e-5)
-        counts[batched] = _phase_launches(ops, sess, n)
-    tot = {b: sum(len(v) for v in counts[b].values()) for b in counts}
-    assert tot[True] < tot[False], tot
-    gen_b = [l for l in counts[True]["gen" if "gen" in counts[True] else list(counts[True])[0]] if "generator_fwd" in l]
-    gen_u = [l for l in counts[False]["gen" if "gen" in counts[False] else list(counts[False])[0]] if "generator_fwd" in l]
-    if kind == "cut_x2y":
-        # unbatched: six applications.  Batched: G([x; y]) whose n_4 doubles as enc(x), enc(y) (the encoder tap: one
-        # launch writes both, one backward launch takes both gradients), and enc([G(x); G(y)])
-        assert len(gen_u) == 6 and sorted(gen_b) == ["gan_generator_fwd_keep", "gan_generator_fwd_tap"], (gen_u, gen_b)
-        assert "gan_generator_bwd_tap" in counts[True]["gen"] and "gan_generator_fwd_tap" in counts[True]["feat"]
-        assert tot[True] * 2 <= tot[False] + 10, tot
-    if kind == "cycle_gan":
-        # the four generator applications depend on each other pairwise: the same-weight ones cannot share a launch, but
-        # G_x2y(x) | G_y2x(y), then G_y2x(fake_y) | G_x2y(fake_x) -- same shape, different variables -- do (hypel.h: *_apps),
-        # and so do the two critics of either phase
-        assert len(gen_u) == 4 and gen_b == ["gan_generator_fwd_apps"] * 2, (gen_u, gen_b)
-        for ph in ("gen", "dis"):
-            assert counts[True][ph].count("dense_stack_bwd_apps") == 1 and "dense_stack_bwd" not in counts[True][ph]
-        assert counts[True]["gen"].count("gan_generator_bwd_apps") == 2
-        # the batched inputs are neighbouring row blocks of the tower's input slab (tower.input_layout): nothing to gather
-        assert not any(l == "copy_blocks_f32" for v in counts[True].values() for l in v), counts[True]
-        assert sum(l == "reduce_splits_wave_multi_f32" for v in counts[True].values() for l in v) == 2
-
-
-@pytest.mark.parametrize("kind,bands", [("cut_x2y", 24), ("cut_x2y", 144), ("cycle_gan", 144)])
-def test_unbatched_applications_with_the_one_launch_slab_reduction(monkeypatch, kind, bands):
-    """BATCH_APPS off, SLAB_REDUCE_MULTI on (round-4 advisor finding): a BN-less layer applied twice as separate units leaves
-    two chunk-sum entries for ONE bias gradient; they must not share a reduction launch (the emulation asserts that no two
-    entries of a launch write the same output) -- the second entry goes to a second launch, and the gradients stay the
-    oracle's."""
-    from hypelcnn_amd import plan_gan
-    monkeypatch.setattr(plan_gan, "BATCH_APPS", False)
-    monkeypatch.setattr(plan_gan, "SLAB_REDUCE_MULTI", True)
-    n = 6
-    cfg = OG.GanConfig(kind, bands, patches=6, max_steps=20)
-    params = U.fp32(OG.init_gan_params(kind, bands, np.random.default_rng(2), patches=cfg.patches, dtype=np.float64,
-                                       zero_generator=False))
-    x, y = _data(n, bands, 4)
-    wrapper, model, loss, ops = U.build(cfg, n, EmuBackend())
-    U.inject(ops.ctx.session(), params)
-    U.check_phase_gradients(cfg, ops, params, x, y, tol=5e-5)
-
-
-def test_two_variable_sets_in_one_launch_can_be_switched_off(monkeypatch):
-    """HYPEL_GAN_BATCH_HETERO=0: CycleGAN's generators and critics run one launch per variable set again; both forms give
-    the oracle's phase gradients (the default form is covered by test_phase_gradients_match_oracle)."""
-    from hypelcnn_amd import plan_gan
-    n, bands = 6, 16
-    cfg = OG.GanConfig("cycle_gan", bands, patches=4, max_steps=20)
-    params = U.fp32(OG.init_gan_params("cycle_gan", bands, np.random.default_rng(2), patches=4, dtype=np.float64,
-                                       zero_generator=False))
-    x, y = _data(n, bands, 4)
-    monkeypatch.setattr(plan_gan, "BATCH_HETERO", False)
     wrapper, model, loss, ops = U.build(cfg, n, EmuBackend())
     sess = ops.ctx.session()
     U.inject(sess, params)
     U.check_phase_gradients(cfg, ops, params, x, y, tol=5e-5)
-    names = [l for v in _phase_launches(ops, sess, n).values() for l in v]
-    assert not any(l.endswith("_apps") for l in names)
-    assert names.count("gan_generator_bwd_kept") == 4 and names.count("dense_stack_bwd") == 4, names
+    counts = _phase_launches(ops, sess, n)
+    assert {ph: len(v) for ph, v in counts.items()} == _BATCHED_LAUNCHES[kind]
+    gen_b = [l for l in counts["gen" if "gen" in counts else list(counts)[0]] if "generator_fwd" in l]
+    if kind == "cut_x2y":
+        # one application per launch would be six generator forwards (len(gen_u) == 6).  Batched: G([x; y]) whose n_4
+        # doubles as enc(x), enc(y) (the encoder tap: one launch writes both, one backward launch takes both gradients),
+        # and enc([G(x); G(y)])
+        assert sorted(gen_b) == ["gan_generator_fwd_keep", "gan_generator_fwd_tap"], gen_b
+        assert "gan_generator_bwd_tap" in counts["gen"] and "gan_generator_fwd_tap" in counts["feat"]
+    if kind == "cycle_gan":
+        # the four generator applications (len(gen_u) == 4) depend on each other pairwise: the same-weight ones cannot
+        # share a launch, but G_x2y(x) | G_y2x(y), then G_y2x(fake_y) | G_x2y(fake_x) -- same shape, different variables --
+        # do (hypel.h: *_apps), and so do the two critics of either phase
+        assert gen_b == ["gan_generator_fwd_apps"] * 2, gen_b
+        for ph in ("gen", "dis"):
+            assert counts[ph].count("dense_stack_bwd_apps") == 1 and "dense_stack_bwd" not in counts[ph]
+        assert counts["gen"].count("gan_generator_bwd_apps") == 2
+        # the batched inputs are neighbouring row blocks of the tower's input slab (tower.input_layout): nothing to gather
+        assert not any(l == "copy_blocks_f32" for v in counts.values() for l in v), counts
+        assert sum(l == "reduce_splits_wave_multi_f32" for v in counts.values() for l in v) == 2
+
+
+def test_second_slab_reduction_round_for_a_layer_applied_to_its_own_output():
+    """A BN-less activated layer applied to its own output, L(L(x)): the two applications depend on each other, so they
+    cannot run as one row-concatenated application and leave two chunk-sum entries for ONE bias gradient (acc = 0, then
+    1).  They must not share a reduction launch (the emulation asserts that no two entries of a launch write the same
+    output): the second entry goes to a second launch, in order, and the gradients are those of a float64 evaluation."""
+    case = U.TwiceAppliedLayer(EmuBackend())
+    plan = case.ct.plan
+    assert [l.tag for l in plan.fwd + plan.bwd].count("slab-reduce") == 2
+    loss, grads = case.run()  # (runs the emulation's own checks on every launch)
+    ref_loss, ref_grads = case.reference()
+    assert abs(loss - ref_loss) < 5e-5 * max(1.0, abs(ref_loss)), (loss, ref_loss)
+    for k, g in ref_grads.items():
+        assert np.abs(grads[k] - g).max() < 5e-5 * np.abs(g).max(), k
+
+
+def test_single_variable_set_launches_of_a_plain_gan():
+    """One generator, one critic (gan_x2y): nothing to pair, so the plan has the single-variable-set forms of the fused
+    kernels and no *_apps launch (test_phase_gradients_match_oracle checks its numbers)."""
+    n = 6
+    wrapper, model, loss, ops = U.build(OG.GanConfig("gan_x2y", 16, patches=4, max_steps=20), n, EmuBackend())
+    names = [l for v in _phase_launches(ops, ops.ctx.session(), n).values() for l in v]
+    assert "gan_generator_bwd_kept" in names and "dense_stack_bwd" in names, names
+    assert not any(l.endswith("_apps") for l in names), names
 
 
 def test_bias_and_leaky_relu_ride_in_the_product(monkeypatch):

@@ -195,3 +195,17 @@ def test_training_steps_track_oracle_trainer_on_gpu(hip, kind, bands, n):
     for k, v in trainer.params.items():
         got = sess.get_variable(k)
         assert np.abs(got - v).max() < 2e-3 * max(np.abs(v).max(), 1e-3), k
+
+
+def test_two_slab_reduction_rounds_accumulate_into_one_bias_gradient(hip):
+    """L(L(x)) with a BN-less activated layer L (tests/gan_util.TwiceAppliedLayer): the shared bias gradient is written by
+    two hypel_reduce_splits_wave_multi_f32 launches, the second accumulating onto the first.  Loss and gradients against the
+    NumPy emulation of the same plan."""
+    from tests.emu_backend import EmuBackend
+    dev, emu = U.TwiceAppliedLayer(hip), U.TwiceAppliedLayer(EmuBackend())
+    assert [l.tag for l in dev.ct.plan.bwd].count("slab-reduce") == 2
+    loss, grads = dev.run()
+    ref_loss, ref_grads = emu.run()
+    assert abs(loss - ref_loss) < 5e-5 * max(1.0, abs(ref_loss)), (loss, ref_loss)
+    for k, g in ref_grads.items():
+        assert np.abs(grads[k] - g).max() < 5e-5 * np.abs(g).max(), k
