@@ -16,7 +16,7 @@
 //    16x16 accumulator (K = 16 samples x 23 column tiles), so a layer needs only (k / 16 + 3) accumulators and one
 //    small diagonal reduction per block, in a fixed order (no float atomics).
 // fp32 MFMA is a k-ordered fmaf chain: same arithmetic class as the VALU kernels in gan.hip, which stay in charge
-// of bands < 16 and bands > 384 (and of everything under HYPEL_GAN_MFMA=0).
+// of bands < 16 and bands > 368 (and of everything under HYPEL_GAN_MFMA=0).
 #include "common.h"
 
 // No fused multiply-adds outside the MFMAs: whether hipcc contracts `gd * f` into a neighbouring sum depends on the code
@@ -965,7 +965,8 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 // Entry points used by gan.hip's dispatch (same contracts as the VALU kernels there).
 bool hypel_gm_supported(int bands) {
     // HYPEL_GAN_MFMA_MIN: smallest band count that runs here.  Default 16: also the narrow Gulfport stacks (B = 64:
-    // CycleGAN step 0.922 -> 0.887 ms, generator launches 31 -> 26 us) -- gan.hip's kernels keep B < 16 and B > 384
+    // CycleGAN step 0.922 -> 0.887 ms, generator launches 31 -> 26 us) -- gan.hip's kernels keep B < 16 and B > 368
+    // (GM_MAX_BANDS = 384 is what the tiling could hold; gm_bwd_lds(369) = 172 032 bytes is past the 160 KB)
     constexpr int min_bands = 16;
     return bands >= min_bands && bands >= 16 && bands <= GM_MAX_BANDS && gm_bwd_lds(bands) <= 160 * 1024;
 }

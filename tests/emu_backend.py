@@ -702,6 +702,26 @@ class EmuBackend:
 
 
 # ----------------------------------------------------------------------------------------------- GAN kernels
+SPEC = np.float64  # the precision the GAN kernels' definitions below are evaluated in
+
+
+class spec_dtype:
+    """`with spec_dtype(np.float32):` evaluates the same formulas in float32 -- not a specification, a yardstick: how far
+    a plain float32 evaluation lies from the float64 one is what the tolerances of new operand regimes are measured
+    from (tests/gan_kernel_cases.py)."""
+
+    def __init__(self, dtype):
+        self.dtype = dtype
+
+    def __enter__(self):
+        global SPEC
+        self.old, SPEC = SPEC, self.dtype
+
+    def __exit__(self, *exc):
+        global SPEC
+        SPEC = self.old
+
+
 def _gen_layout(bands):
     ks = [bands, bands // 2, bands // 4, bands // 8, bands // 4, bands // 2, bands]
     offs = np.concatenate([[0], np.cumsum(ks)]).astype(int)
@@ -725,7 +745,7 @@ def _conv1d_same_T(g, w):
     n, bands = g.shape
     k = len(w)
     pl = (k - 1) // 2
-    gp = np.zeros((n, bands + k - 1))
+    gp = np.zeros((n, bands + k - 1), g.dtype)
     for j in range(k):
         gp[:, j:j + bands] += w[j] * g
     return gp[:, pl:pl + bands]
@@ -738,7 +758,7 @@ def _gen_forward(x, w, b, bands, only_encoder):
     hidden = 4 if only_encoder else 6
     for i in range(1, hidden + 1):
         c = _conv1d_same(a[-1], w[offs[i - 1]:offs[i]]) + b[i - 1]
-        s = np.where(c > 0, 1.0, 0.1)
+        s = np.where(c > 0, 1.0, 0.1).astype(c.dtype)
         slopes.append(s)
         v = c * s + a[-1]
         if i >= 2:
@@ -768,24 +788,34 @@ def generator_knife_edge_rows(x, w, b, bands, only_encoder, eps=1e-6):
     return np.nonzero(near)[0]
 
 
+def _emu_gm_supported(bands):
+    """mirror of csrc/gan_mfma.hip hypel_gm_supported: 16 <= bands <= 384 AND the backward kernel's LDS (5 row images,
+    6 tap tables, the filter-gradient tiles, the raw taps) within 160 KB -- which holds up to 368 bands"""
+    bp = (bands + 15) // 16 * 16
+    pitch = bp + ((18 - bp % 32) + 32) % 32
+    raw = (_gen_layout(bands)[1][7] + 8 + 3) // 4 * 4
+    lds = 4 * (5 * 16 * pitch + 6 * bp + ((bands + 30) // 16 + 2) * 16 * 17 + 128 + raw)
+    return 16 <= bands <= 384 and lds <= 160 * 1024
+
+
 def _emu_generator_blocks(n):
     return int(max(1, min(512, (n + 3) // 4)))
 
 
 def _k_gan_generator_fwd(self, x, ldx, n, bands, w, b, only_encoder, out, ldo):
-    xs = _mat(x, ldx, n, bands).astype(np.float64)
+    xs = _mat(x, ldx, n, bands).astype(SPEC)
     ks, offs = _gen_layout(bands)
-    wv, bv = _arr(w)[:offs[7]].astype(np.float64), _arr(b)[:7].astype(np.float64)
+    wv, bv = _arr(w)[:offs[7]].astype(SPEC), _arr(b)[:7].astype(SPEC)
     a, _, c7 = _gen_forward(xs, wv, bv, bands, only_encoder)
     _mat(out, ldo, n, bands)[...] = (a[4] if only_encoder else np.tanh(c7)).astype(np.float32)
 
 
 def _k_gan_generator_bwd(self, x, ldx, dout, lddo, n, bands, w, b, only_encoder, dx, lddx, accumulate_dx, pw, pb,
                          d_enc=None, ld_denc=0):
-    xs = _mat(x, ldx, n, bands).astype(np.float64)
-    g = _mat(dout, lddo, n, bands).astype(np.float64)
+    xs = _mat(x, ldx, n, bands).astype(SPEC)
+    g = _mat(dout, lddo, n, bands).astype(SPEC)
     ks, offs = _gen_layout(bands)
-    wv, bv = _arr(w)[:offs[7]].astype(np.float64), _arr(b)[:7].astype(np.float64)
+    wv, bv = _arr(w)[:offs[7]].astype(SPEC), _arr(b)[:7].astype(SPEC)
     a, slopes, c7 = _gen_forward(xs, wv, bv, bands, only_encoder)
     dw, db = np.zeros(offs[7]), np.zeros(8)
     hidden = 4 if only_encoder else 6
@@ -808,7 +838,7 @@ def _k_gan_generator_bwd(self, x, ldx, dout, lddo, n, bands, w, b, only_encoder,
     for i in range(hidden, 0, -1):
         if i == 4 and d_enc is not None:  # encoder tap: the gradient of the encoder-only application's output joins dn_4
             assert not only_encoder
-            da[4] = da[4] + _mat(d_enc, ld_denc, n, bands).astype(np.float64)
+            da[4] = da[4] + _mat(d_enc, ld_denc, n, bands).astype(SPEC)
         gi = da[i]
         da[i - 1] = da[i - 1] + gi
         if i >= 2:
@@ -831,7 +861,7 @@ def _k_gan_generator_bwd(self, x, ldx, dout, lddo, n, bands, w, b, only_encoder,
 
 def _k_gan_loss(self, mode, a, lda, b, ldb, rows, c, target, weight, loss, accumulate_loss, da, ldda, acc_da, db, lddb,
                 acc_db, ws):
-    av = _mat(a, lda, rows, c).astype(np.float64)
+    av = _mat(a, lda, rows, c).astype(SPEC)
     cnt = rows * c
     if mode == 0:
         d = av - target
@@ -855,7 +885,7 @@ def _k_gan_loss(self, mode, a, lda, b, ldb, rows, c, target, weight, loss, accum
 
 
 def _k_l2_reg(self, w, count, scale, loss, accumulate_loss, dw, ws):
-    wv = _arr(w)[:count].astype(np.float64)
+    wv = _arr(w)[:count].astype(SPEC)
     lv = _arr(loss)
     lv[0] = (lv[0] if accumulate_loss else 0.0) + 0.5 * scale * (wv * wv).sum()
     if dw is not None:
@@ -877,12 +907,12 @@ def _k_loss_terms_slots(self, base, terms, n_terms, slots):
             return np.lib.stride_tricks.as_strided(flat, shape=(rows, c), strides=(int(ld) * 4, 4))
 
         if mode == 3:
-            w = _at(base, int(e["a_off"]), rows).astype(np.float64)
+            w = _at(base, int(e["a_off"]), rows).astype(SPEC)
             slot[0] = np.float32(float(e["pscale"]) * (w * w).sum())
             if int(e["da_off"]) != LOSS_NONE:
                 _at(base, int(e["da_off"]), rows)[...] += (float(e["gcoef"]) * w).astype(np.float32)
             continue
-        av = mat(e["a_off"], e["lda"]).astype(np.float64)
+        av = mat(e["a_off"], e["lda"]).astype(SPEC)
         if mode == 0:
             d = av - float(e["target"])
             val, ga, gb = (d * d).sum(), 2 * d, None
@@ -905,11 +935,11 @@ def _k_loss_terms_slots(self, base, terms, n_terms, slots):
 
 def _k_loss_finalize_slots(self, slots, n_slots, loss, accumulate_loss):
     lv = _arr(loss)
-    lv[0] = (lv[0] if accumulate_loss else 0.0) + _arr(slots)[: n_slots * 1024].astype(np.float64).sum()
+    lv[0] = (lv[0] if accumulate_loss else 0.0) + _arr(slots)[: n_slots * 1024].astype(SPEC).sum()
 
 
 def _k_l2norm_fwd(self, x, ldx, rows, c, y, ldy, stat):
-    xv = _mat(x, ldx, rows, c).astype(np.float64)
+    xv = _mat(x, ldx, rows, c).astype(SPEC)
     ss = (xv * xv).sum()
     inv = 1.0 / np.sqrt(max(ss, 1e-12))
     st = _arr(stat)
@@ -918,8 +948,8 @@ def _k_l2norm_fwd(self, x, ldx, rows, c, y, ldy, stat):
 
 
 def _k_l2norm_bwd(self, x, ldx, dy, lddy, rows, c, stat, dx, lddx, accumulate):
-    xv = _mat(x, ldx, rows, c).astype(np.float64)
-    g = _mat(dy, lddy, rows, c).astype(np.float64)
+    xv = _mat(x, ldx, rows, c).astype(SPEC)
+    g = _mat(dy, lddy, rows, c).astype(SPEC)
     st = _arr(stat)
     inv = float(st[1])
     coef = float((g * xv).sum()) * inv ** 3 if st[0] > 1e-12 else 0.0
@@ -954,8 +984,8 @@ def _k_l2norm_segs_bwd(self, x, ldx, dy, lddy, rows, c, parts, segs, stat, dx, l
 
 def _k_nce_loss(self, g, ldg, r, ldr, n, p, e, tau, weight, loss, accumulate_loss, dg, lddg, acc_dg, dr, lddr, acc_dr,
                 ws):
-    gv = _mat(g, ldg, n, p * e).astype(np.float64).reshape(n, p, e)
-    rv = _mat(r, ldr, n, p * e).astype(np.float64).reshape(n, p, e)
+    gv = _mat(g, ldg, n, p * e).astype(SPEC).reshape(n, p, e)
+    rv = _mat(r, ldr, n, p * e).astype(SPEC).reshape(n, p, e)
     logits = np.einsum("npe,nqe->npq", gv, rv) / tau
     flat = logits.reshape(n, -1)
     mx = flat.max(1, keepdims=True)
@@ -984,20 +1014,20 @@ EmuBackend.k_l2norm_segs_fwd = _k_l2norm_segs_fwd
 EmuBackend.k_l2norm_segs_bwd = _k_l2norm_segs_bwd
 def _k_gan_generator_fwd_tap(self, x, ldx, n, bands, w, b, out, ldo, enc_out, ld_enc, keep):
     """Specification of the encoder tap: the full forward, and what the encoder-only forward on the same input writes."""
-    assert 16 <= bands <= 384, "matrix-core kernels only"
+    assert _emu_gm_supported(bands), "matrix-core kernels only"
     _k_gan_generator_fwd(self, x, ldx, n, bands, w, b, 0, out, ldo)
     _k_gan_generator_fwd(self, x, ldx, n, bands, w, b, 1, enc_out, ld_enc)
 
 
 def _k_gan_generator_bwd_tap(self, x, ldx, dout, lddo, d_enc, ld_denc, n, bands, w, b, dx, lddx, acc, pw, pb, keep):
-    assert 16 <= bands <= 384 and d_enc is not None
+    assert _emu_gm_supported(bands) and d_enc is not None
     _k_gan_generator_bwd(self, x, ldx, dout, lddo, n, bands, w, b, 0, dx, lddx, acc, pw, pb, d_enc, ld_denc)
 
 
 EmuBackend.k_gan_generator_fwd = _k_gan_generator_fwd
 EmuBackend.k_gan_generator_fwd_tap = _k_gan_generator_fwd_tap
 EmuBackend.k_gan_generator_bwd_tap = _k_gan_generator_bwd_tap
-EmuBackend.gan_generator_tap_supported = lambda self, bands: 16 <= bands <= 384
+EmuBackend.gan_generator_tap_supported = lambda self, bands: _emu_gm_supported(bands)
 EmuBackend.k_gan_generator_bwd = _k_gan_generator_bwd
 EmuBackend.k_gan_loss = _k_gan_loss
 EmuBackend.k_l2_reg = _k_l2_reg
@@ -1010,8 +1040,8 @@ def _ds_layers(n_layers, widths, act_mask, w, b):
     ws, bs, wo, bo = [], [], 0, 0
     for l in range(n_layers):
         cin, cout = widths[l], widths[l + 1]
-        ws.append(_arr(w)[wo:wo + cin * cout].reshape(cin, cout).astype(np.float64))
-        bs.append(_arr(b)[bo:bo + cout].astype(np.float64))
+        ws.append(_arr(w)[wo:wo + cin * cout].reshape(cin, cout).astype(SPEC))
+        bs.append(_arr(b)[bo:bo + cout].astype(SPEC))
         wo += cin * cout
         bo += cout
     return ws, bs, [bool((act_mask >> l) & 1) for l in range(n_layers)], wo, bo
@@ -1028,7 +1058,7 @@ def _ds_forward(x, ws, bs, lrelu, alpha):
 def _k_dense_stack_fwd(self, x, ldx, n, n_layers, w0, w1, w2, w3, w4, act_mask, alpha, w, b, out, ldo):
     widths = [w0, w1, w2, w3, w4]
     ws, bs, lrelu, _, _ = _ds_layers(n_layers, widths, act_mask, w, b)
-    a = _ds_forward(_mat(x, ldx, n, w0).astype(np.float64), ws, bs, lrelu, alpha)
+    a = _ds_forward(_mat(x, ldx, n, w0).astype(SPEC), ws, bs, lrelu, alpha)
     _mat(out, ldo, n, widths[n_layers])[...] = a[-1].astype(np.float32)
 
 
@@ -1036,8 +1066,8 @@ def _k_dense_stack_bwd(self, x, ldx, dout, lddo, n, n_layers, w0, w1, w2, w3, w4
                        pw, pb):
     widths = [w0, w1, w2, w3, w4]
     ws, bs, lrelu, wtotal, btotal = _ds_layers(n_layers, widths, act_mask, w, b)
-    a = _ds_forward(_mat(x, ldx, n, w0).astype(np.float64), ws, bs, lrelu, alpha)
-    g = _mat(dout, lddo, n, widths[n_layers]).astype(np.float64)
+    a = _ds_forward(_mat(x, ldx, n, w0).astype(SPEC), ws, bs, lrelu, alpha)
+    g = _mat(dout, lddo, n, widths[n_layers]).astype(SPEC)
     dws, dbs = [None] * n_layers, [None] * n_layers
     for l in range(n_layers - 1, -1, -1):
         if lrelu[l]:
@@ -1078,7 +1108,7 @@ EmuBackend.dense_stack_supported = lambda self, widths: _emu_dense_stack_support
 EmuBackend.gan_generator_blocks = lambda self, n: _emu_generator_blocks(n)
 # kept activations: the emulation recomputes (the product's two pairs are bit-identical); a nominal buffer size so that
 # the planner takes the same path as on the device
-EmuBackend.gan_generator_keep_floats = lambda self, n, bands, only_encoder: 16 if 16 <= bands <= 384 else 0
+EmuBackend.gan_generator_keep_floats = lambda self, n, bands, only_encoder: 16 if _emu_gm_supported(bands) else 0
 EmuBackend.k_gan_generator_fwd_keep = lambda self, x, ldx, n, bands, w, b, enc, out, ldo, keep: _k_gan_generator_fwd(
     self, x, ldx, n, bands, w, b, enc, out, ldo)
 EmuBackend.k_gan_generator_bwd_kept = lambda self, x, ldx, dout, lddo, n, bands, w, b, enc, dx, lddx, acc, pw, pb, keep: \

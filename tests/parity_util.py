@@ -4,8 +4,10 @@ run one training step / one inference pass, and compare everything with the orac
 import numpy as np
 import torch
 
+from hypelcnn_amd.backend import Ref
 from hypelcnn_amd.common import common_nn_ops as cno
 from oracle import models as OM, train as OT
+from tests.emu_backend import EmuBackend
 
 
 def to_pixel_major(a):
@@ -282,3 +284,114 @@ def product_kink_decisions_biased(built, ct, ref_pre, alpha_zone=1e-4):
                 force[b.scope] = torch.where(differ, got > 0, pre64 > 0).reshape(ref_pre[b.scope].shape)
             off += b.cout
     return force, n_amb, n_flip
+
+
+# ------------------------------------------------------------------------------ kernel-level parity (C-ABI vs the spec)
+class Both:
+    """Mirror host arrays onto both backends; run the same launch; compare named outputs."""
+
+    def __init__(self, hip):
+        self.hip, self.emu = hip, EmuBackend()
+        self.h, self.e = {}, {}
+
+    def arr(self, name, a):
+        a = np.ascontiguousarray(a)
+        self.e[name] = self.emu.upload(a)
+        self.h[name] = self.hip.upload(a)
+        return name
+
+    def run(self, kernel, *args):
+        def conv(store):
+            out = []
+            for a in args:
+                if isinstance(a, tuple) and len(a) == 2 and isinstance(a[0], str):
+                    out.append(Ref(store[a[0]], a[1]))
+                elif isinstance(a, str) and a in store:
+                    out.append(Ref(store[a]))
+                else:
+                    out.append(a)
+            return out
+        self.emu.call(kernel, *conv(self.e))
+        self.hip.call(kernel, *conv(self.h))
+        self.hip.synchronize()
+
+    def check(self, name, rtol=1e-4, atol=1e-5, dtype=np.float32):
+        got = self.h[name].cpu().numpy().view(dtype) if dtype != np.float32 else self.h[name].cpu().numpy()
+        ref = self.e[name].numpy().view(dtype) if dtype != np.float32 else self.e[name].numpy()
+        scale = max(1.0, float(np.abs(ref).max()))
+        np.testing.assert_allclose(got, ref, rtol=rtol, atol=atol * scale, err_msg=name)
+
+
+class SpecOnly(Both):
+    """The same interface with the executable spec on both sides (no device): what the case tables of
+    tests/gan_kernel_cases.py run through on a machine without a GPU."""
+
+    def __init__(self):
+        self.hip = self.emu = EmuBackend()
+        self.h = self.e = {}
+
+    def arr(self, name, a):
+        self.e[name] = self.emu.upload(np.ascontiguousarray(a))
+        return name
+
+    def run(self, kernel, *args):
+        conv = [Ref(self.e[a[0]], a[1]) if isinstance(a, tuple) and len(a) == 2 and isinstance(a[0], str)
+                else Ref(self.e[a]) if isinstance(a, str) and a in self.e else a for a in args]
+        self.emu.call(kernel, *conv)
+
+
+SENT = np.float32(-12345.5)  # the fixed bit pattern of every float a kernel must not touch (tests/test_gpu_step_tail.py)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+class Arena:
+    """An [n x width] operand at column `col` of a row-major [n x ld] buffer, inside a sentinel-filled allocation with
+    16 * ld floats of guard before and after: a launch that addresses the operand wrongly lands in memory the test owns
+    and shows as a broken sentinel.  `buf` is the allocation to upload, `off` the element offset of the operand's first
+    float (the Ref offset), `window(flat)` the [n x width] view of a downloaded allocation, `check(flat)` asserts that
+    every float outside the window still holds the sentinel bits."""
+
+    def __init__(self, n, width, ld, col, data=None):
+        assert 0 <= col and col + width <= ld
+        self.n, self.width, self.ld, self.col = int(n), int(width), int(ld), int(col)
+        self.guard = 16 * self.ld
+        self.off = self.guard + self.col
+        self.buf = np.full(2 * self.guard + self.n * self.ld, SENT, np.float32)
+        if data is not None:
+            self.window(self.buf)[...] = np.asarray(data, np.float32).reshape(self.n, self.width)
+
+    def window(self, flat):
+        flat = np.asarray(flat).reshape(-1)
+        assert flat.size == self.buf.size
+        return flat[self.guard:self.guard + self.n * self.ld].reshape(self.n, self.ld)[:, self.col:self.col + self.width]
+
+    def check(self, flat, name="operand"):
+        outside = np.ones(self.buf.size, bool)
+        self.window(outside)[...] = False
+        got = bits(np.asarray(flat).reshape(-1))
+        bad = np.flatnonzero(outside & (got != bits(SENT)))
+        assert bad.size == 0, (f"{name}: {bad.size} floats outside the [{self.n} x {self.width}] window at column {self.col} "
+                               f"of ld {self.ld} were written; first at element {int(bad[0]) - self.guard} of the buffer")
+
+
+def arena(n, width, ld, col, data=None):
+    """(Ref offset, ld, checker) of a window; the Arena itself as a fourth element."""
+    a = Arena(n, width, ld, col, data)
+    return a.off, a.ld, a.check, a
+
+
+def assert_close(name, got, ref, rtol, atol):
+    """Both.check's criterion on two host arrays (a window of an arena, say): atol scales with max(1, max|ref|)."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    scale = max(1.0, float(np.abs(ref).max())) if ref.size else 1.0
+    np.testing.assert_allclose(got, ref, rtol=rtol, atol=atol * scale, err_msg=name)
+
+
+def assert_same_bits(name, a, b):
+    a, b = bits(a), bits(b)
+    assert a.shape == b.shape, name
+    bad = np.flatnonzero(a.reshape(-1) != b.reshape(-1))
+    assert bad.size == 0, f"{name}: {bad.size} of {a.size} floats differ in their bits; first at flat index {int(bad[0])}"

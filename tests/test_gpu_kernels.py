@@ -9,6 +9,7 @@ from hypelcnn_amd.backend import GROUP_DTYPE, SEG_DTYPE, TILE_DTYPE, Ref
 from hypelcnn_amd.plan import GemmTables, TowerPlan
 from tests import emu_backend
 from tests.emu_backend import EmuBackend
+from tests.parity_util import Both
 
 pytestmark = pytest.mark.gpu
 
@@ -17,41 +18,6 @@ pytestmark = pytest.mark.gpu
 def hip():
     from hypelcnn_amd.backend import HipBackend
     return HipBackend()
-
-
-class Both:
-    """Mirror host arrays onto both backends; run the same launch; compare named outputs."""
-
-    def __init__(self, hip):
-        self.hip, self.emu = hip, EmuBackend()
-        self.h, self.e = {}, {}
-
-    def arr(self, name, a):
-        a = np.ascontiguousarray(a)
-        self.e[name] = self.emu.upload(a)
-        self.h[name] = self.hip.upload(a)
-        return name
-
-    def run(self, kernel, *args):
-        def conv(store):
-            out = []
-            for a in args:
-                if isinstance(a, tuple) and len(a) == 2 and isinstance(a[0], str):
-                    out.append(Ref(store[a[0]], a[1]))
-                elif isinstance(a, str) and a in store:
-                    out.append(Ref(store[a]))
-                else:
-                    out.append(a)
-            return out
-        self.emu.call(kernel, *conv(self.e))
-        self.hip.call(kernel, *conv(self.h))
-        self.hip.synchronize()
-
-    def check(self, name, rtol=1e-4, atol=1e-5, dtype=np.float32):
-        got = self.h[name].cpu().numpy().view(dtype) if dtype != np.float32 else self.h[name].cpu().numpy()
-        ref = self.e[name].numpy().view(dtype) if dtype != np.float32 else self.e[name].numpy()
-        scale = max(1.0, float(np.abs(ref).max()))
-        np.testing.assert_allclose(got, ref, rtol=rtol, atol=atol * scale, err_msg=name)
 
 
 def _tables(b, groups):  # (b: unused, kept for the call sites)
@@ -968,7 +934,7 @@ def test_gather_pairs_bit_exact(hip, bands, n, with_ratio):
 
 def test_gan_generator_valu_kernels_in_a_subprocess():
     """The generator runs on the matrix cores (gan_mfma.hip) from 16 bands on; gan.hip's wave-per-sample and register-tiled
-    kernels remain the path for B < 16 / B > 384 and under HYPEL_GAN_MFMA=0 (the library reads the switch once per
+    kernels remain the path for B < 16 / B > 368 and under HYPEL_GAN_MFMA=0 (the library reads the switch once per
     process): the same parity cases once more on them."""
     import os
     import subprocess
