@@ -60,6 +60,9 @@ SUMMARY_MAX_LIMITS = 2048  # include/hypel.h HYPEL_SUMMARY_MAX_LIMITS
 FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = 16384, 255, 32, 64
 # include/hypel.h hypel_forest_node_t: a leaf has left = -1 - (its row of the leaf table)
 FOREST_NODE_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<f4"), ("left", "<i4"), ("right", "<i4")])
+# include/hypel.h hypel_tiff_seg_t (byte offsets and lengths), HYPEL_TIFF_*: codecs of hypel_tiff_unpack
+TIFF_SEG_DTYPE = np.dtype([("src_off", "<i8"), ("src_len", "<i8"), ("dst_off", "<i8"), ("dst_len", "<i8")])
+TIFF_LZW, TIFF_PACKBITS = 5, 32773
 COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
                              ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 
@@ -200,6 +203,8 @@ SIGNATURES = {
     "forest_predict_rows": [_P, _I64, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I64, _P],
     "forest_predict_scene": [_P, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P,
                              _I64],
+    "tiff_unpack": [_P, _I64, _P, _I32, _I32, _P, _I64, _P],
+    "tiff_assemble": [_P, _I64, _P, _I32, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

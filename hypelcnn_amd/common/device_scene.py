@@ -10,6 +10,7 @@ import torch
 
 from hypelcnn_amd.backend import OUT_DTYPES, SCENE_RANK_WS_WORDS, Ref
 from hypelcnn_amd.common.common_nn_ops import BasicDataSet, get_data_point_func, get_data_point_func_hsi
+from hypelcnn_amd.common.tiff_io import DeviceRaster
 
 EXTREMA_SLICES = 1024  # partial results of a reduction launch (workspace rows)
 SUM_SLICES = 2048
@@ -65,9 +66,22 @@ def percentile_from_ranks(a, b, t, dtype):
 
 class _Source:
     """A raster in device memory, as the kernels address it: flat byte tensor, element offset, (h, w, bands) and
-    element strides.  A view whose root array is contiguous is uploaded as that root and read in place."""
+    element strides.  A view whose root array is contiguous is uploaded as that root and read in place; a
+    tiff_io.DeviceRaster is where it is already and is read through its strides, without a copy."""
 
     def __init__(self, backend, array):
+        if isinstance(array, DeviceRaster):
+            if array.ndim != 3 or array.dtype not in OUT_DTYPES or 0 in array.shape:
+                raise ValueError("scene rasters are [h, w, bands] of float32, uint16, int16 or uint8")
+            if array.bytes.device.type != torch.device(backend.device).type:
+                raise ValueError("the raster lives on another device than the backend")
+            self.dtype = array.dtype
+            self.code = OUT_DTYPES[array.dtype]
+            self.h, self.w, self.bands = array.shape
+            self.strides = tuple(0 if n == 1 else s for n, s in zip(array.shape, array.strides))
+            self.bytes = array.bytes
+            self.ref = Ref(array.bytes, array.byte_offset)
+            return
         a = numpy.asarray(array)
         if a.ndim != 3 or a.dtype not in OUT_DTYPES:
             raise ValueError("scene rasters are [h, w, bands] of float32, uint16, int16 or uint8")

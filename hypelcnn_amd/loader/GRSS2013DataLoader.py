@@ -1,13 +1,16 @@
 """GRSS2013 (2013 IEEE GRSS Data Fusion Contest, Houston; reference loader/GRSS2013DataLoader.py): a 144-band CASI
 raster plus one LiDAR height band on the same grid, 15 classes, training and validation samples in two label rasters,
-a shadow map for the shadow augmenters.  The rasters must be uncompressed, chunky, single-strip TIFFs
-(common/tiff_io.py).  With a compute backend the scene is prepared on the device (common/device_scene.py)."""
+a shadow map for the shadow augmenters.  The rasters are classic TIFFs in any layout common/tiff_io.py reads (strips
+or tiles, chunky or planar, either byte order, uncompressed / PackBits / LZW / Deflate, Predictor 1-3; BigTIFF, JPEG
+and the other codecs are refused by name).  With a compute backend the two scene rasters are decoded and the scene is
+prepared on the device (tiff_io.read_raster, common/device_scene.py); the label rasters are read on the host."""
 from functools import partial
 
 import numpy
 
 from hypelcnn_amd.common.common_nn_ops import load_shadow_map_common, read_targets_from_image, \
     shuffle_test_data_using_ratio
+from hypelcnn_amd.common import device_scene
 from hypelcnn_amd.common.device_scene import make_basic_data_set
 from hypelcnn_amd.loader.DataLoader import DataLoader, SampleSet
 
@@ -57,10 +60,11 @@ class GRSS2013DataLoader(DataLoader):
         return self.base_dir + "/2013_DFTC/"
 
     def load_data(self, neighborhood, normalize):
-        from hypelcnn_amd.common.tiff_io import imread
-        casi = imread(self.get_model_base_dir() + "2013_IEEE_GRSS_DF_Contest_CASI.tif")
-        lidar = imread(self.get_model_base_dir() + "2013_IEEE_GRSS_DF_Contest_LiDAR.tif")[:, :, numpy.newaxis]
-        data_set = make_basic_data_set(self.backend, shadow_creator_dict=None, casi=casi, lidar=lidar,
+        from hypelcnn_amd.common.tiff_io import read_raster
+        backend = device_scene.resolve_scene_backend(self.backend)
+        casi = read_raster(self.get_model_base_dir() + "2013_IEEE_GRSS_DF_Contest_CASI.tif", backend)
+        lidar = read_raster(self.get_model_base_dir() + "2013_IEEE_GRSS_DF_Contest_LiDAR.tif", backend)[:, :, numpy.newaxis]
+        data_set = make_basic_data_set(backend, shadow_creator_dict=None, casi=casi, lidar=lidar,
                                        neighborhood=neighborhood, normalize=normalize)
         _, shadow_ratio = self.load_shadow_map(neighborhood, data_set)
         data_set.shadow_creator_dict = shadow_creators(self.get_model_base_dir(), GAN_CHECKPOINTS, shadow_ratio,

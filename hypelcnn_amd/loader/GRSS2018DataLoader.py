@@ -33,20 +33,25 @@ class GRSS2018DataSet(BasicDataSet):
 
 
 class GRSS2018DataLoader(DataLoader):
-    """File-backed loader (needs the contest rasters as uncompressed TIFFs readable by common/tiff_io.py; the
-    contest files themselves are not available in the build environment -- SyntheticDataLoader's "grss2018hr" preset
-    produces the same two-resolution geometry)."""
+    """File-backed loader (the contest rasters in any layout common/tiff_io.py reads: strips or tiles, chunky or
+    planar, either byte order, uncompressed / PackBits / LZW / Deflate).  With a compute backend the two scene rasters
+    are decoded on the device (tiff_io.read_raster) and downloaded: the two-resolution GRSS2018DataSet is prepared on
+    the host.  The contest files themselves are not available in the build environment -- SyntheticDataLoader's
+    "grss2018hr" preset produces the same two-resolution geometry."""
 
     def __init__(self, base_dir):
         self.base_dir = base_dir
+        self.backend = None  # raster decoding: this backend, else a visible HIP device, else the host
 
     def get_model_base_dir(self):
         return self.base_dir + "/2018/"
 
     def load_data(self, neighborhood, normalize):
-        from hypelcnn_amd.common.tiff_io import imread
-        casi = imread(self.get_model_base_dir() + "20170218_UH_CASI_S4_NAD83.tiff")[:, :, 0:-2]
-        lidar = imread(self.get_model_base_dir() + "UH17c_GEF051.tif")[:, :, numpy.newaxis]
+        from hypelcnn_amd.common import device_scene
+        from hypelcnn_amd.common.tiff_io import read_raster
+        backend = device_scene.resolve_scene_backend(self.backend)
+        casi = numpy.asarray(read_raster(self.get_model_base_dir() + "20170218_UH_CASI_S4_NAD83.tiff", backend))[:, :, 0:-2]
+        lidar = numpy.asarray(read_raster(self.get_model_base_dir() + "UH17c_GEF051.tif", backend))[:, :, numpy.newaxis]
         lidar[numpy.where(lidar > 300)] = 0  # eliminate unacceptable values (:54)
         return GRSS2018DataSet(shadow_creator_dict=None, casi=casi, lidar=lidar, neighborhood=neighborhood,
                                normalize=normalize)

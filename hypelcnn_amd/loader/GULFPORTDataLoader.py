@@ -1,10 +1,12 @@
 """GULFPORT (MUUFL Gulfport; reference loader/GULFPORTDataLoader.py): a 64-band hyperspectral raster plus one LiDAR
 band, ground truth with classes 1..11 that become labels 0..10.  No shadow map: `load_shadow_map` returns None, as the
-reference's does.  Rasters: uncompressed, chunky, single-strip TIFFs (common/tiff_io.py)."""
+reference's does.  Rasters: classic TIFFs in any layout common/tiff_io.py reads; with a compute backend the two scene
+rasters are decoded on the device (tiff_io.read_raster), the ground truth on the host."""
 import numpy
 
 from hypelcnn_amd.common.common_nn_ops import read_targets_from_image, shuffle_test_data_using_ratio, \
     shuffle_training_data_using_ratio, shuffle_training_data_using_size
+from hypelcnn_amd.common import device_scene
 from hypelcnn_amd.common.device_scene import make_basic_data_set
 from hypelcnn_amd.loader.DataLoader import DataLoader, SampleSet
 
@@ -40,10 +42,11 @@ class GULFPORTDataLoader(DataLoader):
                                        neighborhood, normalize)
 
     def _load_data_utility(self, hsi_file, lidar_file, neighborhood, normalize, casi_min=None, casi_max=None):
-        from hypelcnn_amd.common.tiff_io import imread
-        casi = imread(self.get_model_base_dir() + hsi_file)
-        lidar = imread(self.get_model_base_dir() + lidar_file)[:, :, numpy.newaxis]
-        return make_basic_data_set(self.backend, shadow_creator_dict=None, casi=casi, lidar=lidar,
+        from hypelcnn_amd.common.tiff_io import read_raster
+        backend = device_scene.resolve_scene_backend(self.backend)
+        casi = read_raster(self.get_model_base_dir() + hsi_file, backend)
+        lidar = read_raster(self.get_model_base_dir() + lidar_file, backend)[:, :, numpy.newaxis]
+        return make_basic_data_set(backend, shadow_creator_dict=None, casi=casi, lidar=lidar,
                                    neighborhood=neighborhood, normalize=normalize, casi_min=casi_min,
                                    casi_max=casi_max)
 

@@ -724,6 +724,42 @@ int hypel_scene_prepare_f32(const void* src, int32_t dtype, int64_t h, int64_t w
 int hypel_scene_masked_sums(const float* scene, const uint8_t* map, int64_t hp, int64_t wp, int32_t bands, double* sums,
                             int64_t* counts, double* ws, int32_t ws_slices, hypel_stream_t stream);
 
+/* ---- TIFF layouts (common/tiff_io.py; csrc/tiff.hip) ---------------------------------------------------------------
+ * From "the file's bytes are in HBM" to the raster [h][w][spp] the scene preparation reads.  A segment is a strip or
+ * a tile; segment s of the table is plane s / (segs_across * segs_down) (chunky files have one plane), row of
+ * segments (s / segs_across) % segs_down, column s % segs_across.  Offsets and lengths are bytes; the table lives in
+ * device memory, so the caller checks it before upload (src ranges inside src, dst ranges inside dst and disjoint);
+ * both launches still bound every read by src_len / src_bytes and every write by dst_len / dst_bytes.
+ *
+ * hypel_tiff_unpack: decodes segment s from src[src_off .. + src_len) to dst[dst_off .. + dst_len), one wavefront per
+ *   segment, and writes status[s].  codec 5: TIFF LZW -- codes MSB-first, Clear 256, EOI 257, first free code 258,
+ *   9 bits growing when the next free code reaches 511 / 1023 / 2047; decoding stops at EOI or once dst_len bytes
+ *   exist.  codec 32773: PackBits -- header n in 0..127 copies n + 1 literals, -127..-1 repeats the next byte 1 - n
+ *   times, -128 is a no-op; a run is clipped at dst_len.  A segment whose status is not HYPEL_TIFF_OK stops where the
+ *   fault was met; nothing outside its dst range is written in any case.
+ * hypel_tiff_assemble: out [h][w][spp] of `item`-byte samples in native order, chunky, from segments of
+ *   seg_rows x seg_cols pixels (a strip: seg_cols = w) read at src + src_off (from_decoded 0: the file as it is) or
+ *   src + dst_off (from_decoded 1: the buffer hypel_tiff_unpack or the host's inflate filled); planes 1 (chunky
+ *   segments of spp samples per pixel) or spp (one sample per pixel, plane p feeds sample p).  Per segment row, over
+ *   the full segment width: predictor 2 accumulates samples spp (chunky) or 1 (planar) apart, modulo the sample
+ *   width, after the byte swap; predictor 3 (item 4) accumulates the row's bytes with that stride and re-interleaves
+ *   its four byte planes, most significant first (swap is ignored: the planes have no byte order).  Right and bottom
+ *   edge tiles and the short last strip are clipped.  A segment row that reaches past src_len / dst_len or src_bytes
+ *   is left out. */
+typedef struct {
+    int64_t src_off, src_len; /* the segment in the file */
+    int64_t dst_off, dst_len; /* its decoded bytes */
+} hypel_tiff_seg_t;
+enum { HYPEL_TIFF_LZW = 5, HYPEL_TIFF_PACKBITS = 32773 };
+enum { HYPEL_TIFF_OK = 0, HYPEL_TIFF_BAD_CODE = 1, HYPEL_TIFF_BAD_FIRST = 2, HYPEL_TIFF_TRUNCATED = 3,
+       HYPEL_TIFF_BAD_RANGE = 4 };
+int hypel_tiff_unpack(const uint8_t* src, int64_t src_bytes, const hypel_tiff_seg_t* segs, int32_t n_segs,
+                      int32_t codec, uint8_t* dst, int64_t dst_bytes, int32_t* status, hypel_stream_t stream);
+int hypel_tiff_assemble(const uint8_t* src, int64_t src_bytes, const hypel_tiff_seg_t* segs, int32_t n_segs,
+                        int32_t from_decoded, int64_t h, int64_t w, int32_t spp, int32_t item, int32_t seg_rows,
+                        int32_t seg_cols, int32_t segs_across, int32_t planes, int32_t predictor, int32_t swap,
+                        void* out, hypel_stream_t stream);
+
 /* ---- shadow / lit pixel pairing (gan/gan_sampling_methods.py; csrc/pairs.hip) ---------------------------------------
  * What the samplers do to the shadow map, where the scene lives: the map is a uint8 [h][w] raster in HBM, the results
  * are the int32 [n][2] = (x, y) point lists hypel_gather_patches_f32 cuts the pairs from.  No atomics: two calls
