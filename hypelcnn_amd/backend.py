@@ -41,8 +41,9 @@ TILE_DTYPE = np.dtype([("group", "<i4"), ("m0", "<i4"), ("rows", "<i4"), ("seg_b
                        ("k0", "<i4"), ("c_off", "<i8"), ("a_off0", "<i8"), ("b_off0", "<i8"),
                        ("flags", "<i4"), ("n", "<i4")])
 TILE_PLAIN = 1  # include/hypel.h HYPEL_TILE_PLAIN: K-slice partial (no bias / accumulate / shortcut gather)
-# include/hypel.h HYPEL_DTYPE_*: output dtypes of hypel_denorm_scatter
+# include/hypel.h HYPEL_DTYPE_*: output dtypes of hypel_denorm_scatter, input dtypes of hypel_hsi_to_srgb
 OUT_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2, np.dtype(np.uint8): 3}
+RGB_U8, RGB_F32 = 0, 1  # include/hypel.h HYPEL_RGB_*: output modes of hypel_hsi_to_srgb
 # include/hypel.h hypel_svm_pair_t, HYPEL_SVM_*
 SVM_PAIR_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<i4"), ("out_off", "<i8")])
 # include/hypel.h hypel_svm_job_t: a pair + the element offset of its plane of K + its C (hypel_svm_smo_grid)
@@ -140,6 +141,7 @@ SIGNATURES = {
     "gather_pairs_f32": [_P, _P, _P, _I64, _I32, _P, _P, _P, _F, _P, _P],
     "argmax_scatter": [_P, _I64, _I64, _I32, _P, _P, _I64],
     "denorm_scatter": [_P, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _I64],
+    "hsi_to_srgb": [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _I32, _P],
     "lrn_fwd": [_P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64],
     "lrn_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64, _I32],
     "gan_generator_fwd": [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64],

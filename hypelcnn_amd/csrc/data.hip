@@ -9,8 +9,11 @@
 //                        into the uint8 label raster at the target's (x, y)
 //   * denorm_scatter   : the GAN scene conversion's ((g * casi_max) + casi_min).astype(dtype)
 //                        (gan/gan_infer_image_for_shadow.py:84-85), per pixel row, into the output raster
-// All three are pure HBM streaming: one read and one write of every patch element, channel-contiguous so that
-// consecutive lanes touch consecutive addresses (C >= 49 floats per pixel in every configuration).
+//   * hsi_to_srgb      : the sRGB rendering of that raster (common/hsi_rgb_converter.py, CIE 1931 2 degree observer,
+//                        illuminant E; gan/gan_infer_image_for_shadow.py:97-104)
+// The gathers, the augmentation and the scatters are pure HBM streaming: one read and one write of every patch element,
+// channel-contiguous so that consecutive lanes touch consecutive addresses (C >= 49 floats per pixel in every
+// configuration).  hsi_to_srgb reads a span of each pixel's bands and writes three samples per pixel.
 #include "common.h"
 
 #define ST ((hipStream_t)stream)
@@ -233,6 +236,181 @@ int launch_denorm_scatter(const float* src, int64_t ld_src, const int64_t* rows,
     return 0;
 }
 
+// sRGB rendering of a raster.  A group of G lanes owns HSI_PIXELS = 4 neighbouring pixels at a time: the lanes load each
+// pixel's span of bands contiguously (V neighbouring bands per lane, all the pixels' loads in flight together) and weigh
+// them into partial X, Y, Z per pixel.  The reduction over the group transposes as it halves: at distance 8 a lane hands
+// two of its four pixels to its partner and takes the partner's share of the other two, at distance 4 one of the two,
+// so that after the distances 2 and 1 the four lanes 4 u .. 4 u + 3 hold the sums of pixel u (15 exchanges instead of
+// the 12 per distance of a plain butterfly, which groups wider than 16 lanes still need above distance 8).  Lane
+// 4 u + c then finishes colour channel c of pixel u and stores it.  table[b] = {offset, wx, wy, wz} of band band0 + b
+// (weights already divided by the band's scale and by sum(ybar)); the first V entries of a lane stay in registers over
+// the pixel loop, which covers the first pass over the span.
+// The sums and the matrix are float64: linear sRGB is a difference of the three sums, float32 sums leave a dark channel
+// of a bright pixel about 2e-6 off, and that moves trunc(255 * rgb) across an integer now and then (a 189-sample raster
+// of the tests allows no such byte).  The curve itself is float32; for the byte output it only has to land within half a
+// level, because levels[k], the smallest linear value whose float64 rendering reaches k, decides between k and k - 1.
+constexpr int HSI_PIXELS = 4;
+
+// V neighbouring bands of one pixel as they lie in memory (converted where they are weighed, so that the loads of a
+// round cost few registers while they are in flight)
+template <typename T, int V>
+struct HsiBands { using type = typename Vec4Of<T>::type; };
+template <typename T>
+struct HsiBands<T, 1> { using type = T; };
+
+template <typename T, int V>
+__device__ __forceinline__ typename HsiBands<T, V>::type hsi_load(const T* p) {
+    return *reinterpret_cast<const typename HsiBands<T, V>::type*>(p);
+}
+
+struct HsiXyz {
+    double x, y, z;
+};
+
+__device__ __forceinline__ void hsi_weigh(double v, const double4 t, HsiXyz& a) {
+    const double d = v - t.x;
+    a.x = fma(d, t.y, a.x);
+    a.y = fma(d, t.z, a.y);
+    a.z = fma(d, t.w, a.z);
+}
+
+// one halving step of the reduction: the lane keeps `keep`, hands `give` to the lane at distance m and adds what that
+// lane hands over in turn
+template <int G>
+__device__ __forceinline__ HsiXyz hsi_exchange(const HsiXyz keep, const HsiXyz give, int m) {
+    return {keep.x + __shfl_xor(give.x, m, G), keep.y + __shfl_xor(give.y, m, G), keep.z + __shfl_xor(give.z, m, G)};
+}
+
+template <int V, typename B>
+__device__ __forceinline__ void hsi_weigh_bands(const B v, const double4 (&t)[V], HsiXyz& a) {
+    if constexpr (V == 4) {
+        hsi_weigh((double)v.x, t[0], a);
+        hsi_weigh((double)v.y, t[1], a);
+        hsi_weigh((double)v.z, t[2], a);
+        hsi_weigh((double)v.w, t[3], a);
+    } else {
+        hsi_weigh((double)v, t[0], a);
+    }
+}
+
+// skimage's xyz2rgb on one channel's linear value, the sRGB transfer curve and the clip to [0, 1], in float32 on the
+// hardware's log2 / exp2 (lin above the knee is a normal number): within 1e-6 of the curve
+__device__ __forceinline__ float hsi_srgb_curve(float lin) {
+    const float s = lin > 0.0031308f ? 1.055f * __builtin_amdgcn_exp2f((1.0f / 2.4f) * __builtin_amdgcn_logf(lin)) - 0.055f
+                                     : 12.92f * lin;
+    return fminf(fmaxf(s, 0.0f), 1.0f);
+}
+
+template <typename T, int G, int V>
+__global__ void __launch_bounds__(256) hsi_to_srgb_kernel(const T* __restrict__ raster, int64_t ld_in, int64_t n, int span,
+                                                          const double4* __restrict__ table,
+                                                          const double* __restrict__ levels, void* __restrict__ out) {
+    constexpr int U = HSI_PIXELS;
+    static_assert(U == 4 && G >= 16 && G <= 64, "the reduction leaves pixel u in the lanes 4 u .. 4 u + 3");
+    const int lane = threadIdx.x % G;
+    const int nvec = span / V;  // whole V-band items of the span; the span % V bands left go one per lane
+    const int rem = span - nvec * V;
+    const double4 zero = make_double4(0.0, 0.0, 0.0, 0.0);  // a lane without a band weighs nothing
+    double4 t0[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) t0[e] = lane < nvec ? table[lane * V + e] : zero;
+    const double4 tr = lane < rem ? table[nvec * V + lane] : zero;
+    const int64_t step = (int64_t)gridDim.x * (256 / G) * U;
+    for (int64_t p0 = ((int64_t)blockIdx.x * (256 / G) + threadIdx.x / G) * U; p0 < n; p0 += step) {
+        const T* row = raster + p0 * ld_in;
+        const int live = n - p0 < U ? (int)(n - p0) : U;  // pixels of this round that exist
+        using Bands = typename HsiBands<T, V>::type;
+        HsiXyz a[U];
+        Bands v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            a[u] = {0.0, 0.0, 0.0};
+            v[u] = Bands{};
+            if (lane < nvec && u < live) v[u] = hsi_load<T, V>(row + u * ld_in + lane * V);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) hsi_weigh_bands<V>(v[u], t0, a[u]);
+        for (int j = lane + G; j < nvec; j += G) {
+            double4 t[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) t[e] = table[j * V + e];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < live) v[u] = hsi_load<T, V>(row + u * ld_in + j * V);
+#pragma unroll
+            for (int u = 0; u < U; ++u) hsi_weigh_bands<V>(v[u], t, a[u]);
+        }
+        if (lane < rem) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < live) hsi_weigh((double)row[u * ld_in + nvec * V + lane], tr, a[u]);
+        }
+#pragma unroll
+        for (int m = G / 2; m >= 16; m >>= 1) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) a[u] = hsi_exchange<G>(a[u], a[u], m);
+        }
+        const bool up8 = (lane & 8) != 0, up4 = (lane & 4) != 0;
+        const HsiXyz b0 = hsi_exchange<G>(up8 ? a[2] : a[0], up8 ? a[0] : a[2], 8);  // pixel 2 h
+        const HsiXyz b1 = hsi_exchange<G>(up8 ? a[3] : a[1], up8 ? a[1] : a[3], 8);  // pixel 2 h + 1, h = bit 3
+        HsiXyz s = hsi_exchange<G>(up4 ? b1 : b0, up4 ? b0 : b1, 4);               // pixel 2 h + bit 2
+        s = hsi_exchange<G>(s, s, 2);
+        s = hsi_exchange<G>(s, s, 1);
+        const int u = lane >> 2, c = lane & 3;
+        if (u < live && c < 3) {
+            const double px = s.x, py = s.y, pz = s.z;
+            // row c of the inverse of skimage's xyz_from_rgb [[0.412453, 0.357580, 0.180423], [0.212671, 0.715160,
+            // 0.072169], [0.019334, 0.119193, 0.950227]]
+            const double mx = c == 0 ? 3.240481343200526 : (c == 1 ? -0.9692549499965682 : 0.05564663913517716);
+            const double my = c == 0 ? -1.5371515162713185 : (c == 1 ? 1.8759900014898907 : -0.20404133836651123);
+            const double mz = c == 0 ? -0.4985363261688878 : (c == 1 ? 0.04155592655829284 : 1.0573110696453443);
+            const double lin = mx * px + my * py + mz * pz;
+            const bool finite = lin - lin == 0.0;  // only non-finite input makes it otherwise: rendered as 0
+            const float rgb = finite ? hsi_srgb_curve((float)lin) : 0.0f;
+            const int64_t o = (p0 + u) * 3 + c;
+            if (levels == nullptr) {
+                static_cast<float*>(out)[o] = rgb;
+            } else {
+                const int k = (int)rintf(255.0f * rgb);  // rgb in [0, 1]; levels[0] = -inf
+                static_cast<uint8_t*>(out)[o] = (uint8_t)((finite && lin >= levels[k]) ? k : (k > 0 ? k - 1 : 0));
+            }
+        }
+    }
+}
+
+template <typename T, int G, int V>
+void launch_hsi_to_srgb_gv(const T* raster, int64_t ld_in, int64_t n, int span, const double* table, const double* levels,
+                           void* out, hipStream_t st) {
+    const dim3 grid(hypel_grid_1d(n, 256 / G * HSI_PIXELS, 256 * 32)), block(256);
+    hipLaunchKernelGGL((hsi_to_srgb_kernel<T, G, V>), grid, block, 0, st, raster, ld_in, n, span,
+                       reinterpret_cast<const double4*>(table), levels, out);
+}
+
+template <typename T, int V>
+void launch_hsi_to_srgb_v(const T* raster, int64_t ld_in, int64_t n, int span, const double* table, const double* levels,
+                          void* out, hipStream_t st) {
+    // lanes per group: enough to cover the span in four passes.  Measured on 349 x 1905 pixels, one, two and four
+    // passes: 120 / 91 / 92 us at a span of 68 bands, 320 / 320 / 250 us at 360; no difference at 52 bands and below
+    const int items = ((span + V - 1) / V + 3) / 4;
+    if (items <= 16)
+        launch_hsi_to_srgb_gv<T, 16, V>(raster, ld_in, n, span, table, levels, out, st);
+    else if (items <= 32)
+        launch_hsi_to_srgb_gv<T, 32, V>(raster, ld_in, n, span, table, levels, out, st);
+    else
+        launch_hsi_to_srgb_gv<T, 64, V>(raster, ld_in, n, span, table, levels, out, st);
+}
+
+// four bands per lane when every pixel's span starts on a four-element boundary, one band per lane otherwise
+template <typename T>
+void launch_hsi_to_srgb(const void* raster, int64_t ld_in, int64_t n, int band0, int span, const double* table,
+                        const double* levels, void* out, hipStream_t st) {
+    const T* r = static_cast<const T*>(raster) + band0;
+    if (ld_in % 4 == 0 && (uintptr_t)r % (4 * sizeof(T)) == 0)
+        launch_hsi_to_srgb_v<T, 4>(r, ld_in, n, span, table, levels, out, st);
+    else
+        launch_hsi_to_srgb_v<T, 1>(r, ld_in, n, span, table, levels, out, st);
+}
+
 }  // namespace
 
 extern "C" int hypel_gather_pairs_f32(const float* normal, const float* shadow, const int64_t* idx, int64_t n, int32_t bands,
@@ -309,5 +487,35 @@ extern "C" int hypel_denorm_scatter(const float* src, int64_t ld_src, const int6
         default: hypel_set_error("hypel_denorm_scatter: unsupported out_dtype %d", (int)out_dtype); return -1;
     }
     HYPEL_CHECK_LAUNCH("hypel_denorm_scatter");
+    return 0;
+}
+
+extern "C" int hypel_hsi_to_srgb(const void* raster, int32_t in_dtype, int64_t ld_in, int64_t n_pixels, int32_t bands,
+                                 int32_t band0, int32_t span, const double* table, const double* levels,
+                                 int32_t out_mode, void* out, hypel_stream_t stream) {
+    HYPEL_REQUIRE(raster && table && out && n_pixels > 0 && bands > 0 && ld_in >= bands, "hypel_hsi_to_srgb");
+    HYPEL_REQUIRE(band0 >= 0 && span > 0 && span <= bands - band0, "hypel_hsi_to_srgb");
+    HYPEL_REQUIRE(((uintptr_t)table & 31) == 0, "hypel_hsi_to_srgb");
+    HYPEL_REQUIRE((out_mode == HYPEL_RGB_U8 && levels && ((uintptr_t)levels & 7) == 0) ||
+                      (out_mode == HYPEL_RGB_F32 && ((uintptr_t)out & 3) == 0),
+                  "hypel_hsi_to_srgb");
+    if (out_mode == HYPEL_RGB_F32) levels = nullptr;
+    switch (in_dtype) {
+        case HYPEL_DTYPE_F32:
+            HYPEL_REQUIRE(((uintptr_t)raster & 3) == 0, "hypel_hsi_to_srgb");
+            launch_hsi_to_srgb<float>(raster, ld_in, n_pixels, band0, span, table, levels, out, ST);
+            break;
+        case HYPEL_DTYPE_U16:
+            HYPEL_REQUIRE(((uintptr_t)raster & 1) == 0, "hypel_hsi_to_srgb");
+            launch_hsi_to_srgb<uint16_t>(raster, ld_in, n_pixels, band0, span, table, levels, out, ST);
+            break;
+        case HYPEL_DTYPE_I16:
+            HYPEL_REQUIRE(((uintptr_t)raster & 1) == 0, "hypel_hsi_to_srgb");
+            launch_hsi_to_srgb<int16_t>(raster, ld_in, n_pixels, band0, span, table, levels, out, ST);
+            break;
+        case HYPEL_DTYPE_U8: launch_hsi_to_srgb<uint8_t>(raster, ld_in, n_pixels, band0, span, table, levels, out, ST); break;
+        default: hypel_set_error("hypel_hsi_to_srgb: unsupported in_dtype %d", (int)in_dtype); return -1;
+    }
+    HYPEL_CHECK_LAUNCH("hypel_hsi_to_srgb");
     return 0;
 }

@@ -7,8 +7,12 @@ flags.
 The reference calls sess.run once per pixel.  Here the normalised scene [H*W, bands] is uploaded once and written
 back as pass-through by one hypel_denorm_scatter over every pixel; the selected pixels then go through the generator
 in fixed-size chunks (hypel_gather_patches_f32 with p = 1 into the phase input, one generator forward, a
-hypel_denorm_scatter of the chunk into its raster rows), and the raster is copied back once.  The reference's second,
-RGB rendering of the scene needs the CIE 1931 tables and is not written."""
+hypel_denorm_scatter of the chunk into its raster rows), and the raster is copied back once.
+
+With --rgb true the reference's second output is written too: the sRGB rendering of the converted scene (CIE 1931
+2 degree observer, common/hsi_rgb_converter.py), one hypel_hsi_to_srgb launch over the raster before it leaves the
+device, saved as shadow_image_rgb_{mode}_{step}_{'' | '_all'}.tif.  The flag defaults to false, which leaves the
+output directory as it was before the rendering existed."""
 import argparse
 import os
 import time
@@ -20,6 +24,7 @@ from hypelcnn_amd.backend import OUT_DTYPES, Ref
 from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, \
     type_ensure_strtobool
 from hypelcnn_amd.common.common_nn_ops import get_loader_from_name
+from hypelcnn_amd.common.hsi_rgb_converter import render_raster_rgb
 from hypelcnn_amd.common.tiff_io import imwrite
 from hypelcnn_amd.gan.gan_utilities import GeneratorAugmenter, load_gan_variables
 from hypelcnn_amd.gan.wrapper_registry import get_infer_wrapper_dict
@@ -35,6 +40,8 @@ def add_parse_cmds_for_app(parser):
                         help="makes the scene shadowed(shadow), non shadowed(deshadow), or empty(none)")
     parser.add_argument("--convert_all", nargs="?", type=type_ensure_strtobool, default=False,
                         help="Whether to convert filtered pixels(shadowed or not) or all.")
+    parser.add_argument("--rgb", nargs="?", type=type_ensure_strtobool, default=False,
+                        help="Whether to write the sRGB rendering of the converted scene next to it.")
 
 
 def parse_mode(make_them_shadow):
@@ -90,11 +97,15 @@ class GeneratorChunks:
         return ct.value(self.aug.out, copy=False)
 
 
-def convert_scene(data_set, shadow_map, mode, convert_all, apply_generator, backend, chunk=DEFAULT_CHUNK, timings=None):
+def convert_scene(data_set, shadow_map, mode, convert_all, apply_generator, backend, chunk=DEFAULT_CHUNK, timings=None,
+                  rgb_band_measurements=None):
     """The converted scene [H, W, bands] in the scene's original dtype (reference :66-85).
 
     apply_generator: `input(n)` / `__call__(n)` as GeneratorChunks (tests plug a scripted generator in here).  The
-    pass-through pixels are the normalised input put through the same de-normalisation, as in the reference."""
+    pass-through pixels are the normalised input put through the same de-normalisation, as in the reference.
+
+    rgb_band_measurements: the loader's band wavelengths; when given, the finished raster is also rendered to sRGB
+    while it is still on the device (reference :97-100) and (scene, uint8 [H, W, 3]) is returned."""
     h, w = data_set.get_scene_shape()
     bands = data_set.get_casi_band_count()
     if data_set.neighborhood != 0:
@@ -135,12 +146,16 @@ def convert_scene(data_set, shadow_map, mode, convert_all, apply_generator, back
         backend.synchronize()
         t["generator_s"] += t2 - t1
         t["denorm_s"] += time.perf_counter() - t2
+    if rgb_band_measurements is not None:
+        t3 = time.perf_counter()
+        rgb = render_raster_rgb(backend, raster, dtype, h, w, bands, rgb_band_measurements, offset, scale)
+        t["rgb_s"] = time.perf_counter() - t3
     t3 = time.perf_counter()
     image = raster.cpu().numpy().view(dtype).reshape(h, w, bands)
     t["copy_back_s"] = time.perf_counter() - t3
     t["pixels"] = int(h * w)
     t["converted"] = int(n_sel)
-    return image
+    return image if rgb_band_measurements is None else (image, rgb)
 
 
 def checkpoint_step(base_log_path):
@@ -151,6 +166,11 @@ def checkpoint_step(base_log_path):
 
 def output_name(mode, base_log_path, convert_all):
     return f"shadow_image_{mode}_{checkpoint_step(base_log_path)}{'' if not convert_all else '_all'}.tif"
+
+
+def rgb_output_name(mode, base_log_path, convert_all):
+    """The reference's name, stray underscore included (:101-102)."""
+    return f"shadow_image_rgb_{mode}_{checkpoint_step(base_log_path)}_{'' if not convert_all else '_all'}.tif"
 
 
 def build_parser():
@@ -182,12 +202,20 @@ def main(argv=None, backend=None, chunk=DEFAULT_CHUNK, generator=None):
             variables = load_gan_variables(flags.base_log_path)
             generator.load({k: variables[k] for k in wrapper.create_generator_restorer()(list(variables))})
     start = time.time()
-    image = convert_scene(data_set, shadow_map, mode, flags.convert_all, generator, backend, chunk=chunk)
+    image = convert_scene(data_set, shadow_map, mode, flags.convert_all, generator, backend, chunk=chunk,
+                          rgb_band_measurements=loader.get_band_measurements() if flags.rgb else None)
+    if flags.rgb:
+        image, rgb = image
     os.makedirs(flags.output_path, exist_ok=True)
     path = os.path.join(flags.output_path, output_name(mode, flags.base_log_path, flags.convert_all))
     print(f"Saving output to {path}")
     imwrite(path, image)
-    print("RGB rendering skipped: the HSI -> RGB conversion (CIE 1931 tables) is not part of this package")
+    if flags.rgb:
+        rgb_path = os.path.join(flags.output_path, rgb_output_name(mode, flags.base_log_path, flags.convert_all))
+        print(f"Saving output RGB to {rgb_path}")
+        imwrite(rgb_path, rgb)
+    else:
+        print("RGB rendering skipped: pass --rgb true for the sRGB rendering of the converted scene")
     print(f"Done conversion({time.time() - start:.3f} sec)")
     return image, path
 

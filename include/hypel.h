@@ -423,6 +423,23 @@ enum { HYPEL_DTYPE_F32 = 0, HYPEL_DTYPE_U16 = 1, HYPEL_DTYPE_I16 = 2, HYPEL_DTYP
 int hypel_denorm_scatter(const float* src, int64_t ld_src, const int64_t* rows, int64_t n, int32_t bands,
                          const float* scale, const float* offset, int32_t out_dtype, void* out, int64_t ld_out,
                          hypel_stream_t stream);
+/* The sRGB rendering of a raster (common/hsi_rgb_converter.py get_rgb_from_hsi with the CIE 1931 2 degree observer and
+ * illuminant E, as gan/gan_infer_image_for_shadow.py:97-104 applies it to the converted scene): raster [n_pixels][ld_in]
+ * of in_dtype (HYPEL_DTYPE_*), of which the bands band0 .. band0 + span - 1 <= bands - 1 are read.  table [span][4]
+ * float64, 32-byte aligned: {offset, wx, wy, wz} per band of the span, so that
+ *   XYZ = sum_b (raster[p][band0 + b] - offset[b]) * (wx, wy, wz)[b]
+ * is the reference's XYZ / 100 -- the caller folds the 31 selected bands (duplicates summed, unselected bands zero),
+ * the colour matching functions, 1 / sum(ybar) and 1 / casi_max into the weights.  Then skimage's xyz2rgb: the inverse
+ * of [[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]],
+ * 1.055 * lin^(1/2.4) - 0.055 above 0.0031308 and 12.92 * lin below, clipped to [0, 1].  The sums and the matrix are
+ * float64, the curve is float32 (within 1e-6).  out [n_pixels][3]: float32 rgb (HYPEL_RGB_F32, levels unused), or uint8
+ * trunc(255 * rgb) (HYPEL_RGB_U8): levels [256] float64 with levels[0] = -inf and levels[k] the smallest linear value
+ * whose float64 curve times 255 reaches k, so that the byte is the largest k with levels[k] <= lin, exactly.  Inputs
+ * are finite: a pixel with a non-finite sample anywhere in its span renders as 0. */
+enum { HYPEL_RGB_U8 = 0, HYPEL_RGB_F32 = 1 };
+int hypel_hsi_to_srgb(const void* raster, int32_t in_dtype, int64_t ld_in, int64_t n_pixels, int32_t bands,
+                      int32_t band0, int32_t span, const double* table, const double* levels, int32_t out_mode,
+                      void* out, hypel_stream_t stream);
 
 /* ---- LRN (tf.nn.local_response_normalization, CONCNNModel.py:37,41) -------------------------------------- */
 int hypel_lrn_fwd(const float* x, int64_t ldx, int64_t rows, int32_t c, int32_t radius, float bias, float alpha,
