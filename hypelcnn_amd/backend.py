@@ -53,6 +53,8 @@ SVM_RBF, SVM_POLY = 0, 1
 SVM_CONVERGED, SVM_NOT_CONVERGED = 0, 1
 SVM_MAX_ITER_LIMIT = 1000000
 SCENE_RANK_WS_WORDS = 772  # include/hypel.h HYPEL_SCENE_RANK_WS_WORDS: uint32 of workspace per band
+# include/hypel.h HYPEL_COLUMN_RANK_*: uint32 of workspace per band and ranks per call of hypel_column_rank_select_f32
+COLUMN_RANK_WS_WORDS, COLUMN_RANK_MAX_RANKS, COLUMN_RANK_MAX_BANDS = 2320, 8, 65536
 COMPACT_TILE = 4096  # include/hypel.h HYPEL_COMPACT_TILE: pixels per int32 of hypel_mask_compact_points_i32's workspace
 SUMMARY_SLICE = 32768  # include/hypel.h HYPEL_SUMMARY_SLICE: elements per slice of hypel_tensor_summary_f32
 SUMMARY_MAX_LIMITS = 2048  # include/hypel.h HYPEL_SUMMARY_MAX_LIMITS
@@ -207,6 +209,8 @@ SIGNATURES = {
                              _I64],
     "tiff_unpack": [_P, _I64, _P, _I32, _I32, _P, _I64, _P],
     "tiff_assemble": [_P, _I64, _P, _I32, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "band_ratio_f32": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I64, _P, _P],
+    "column_rank_select_f32": [_P, _I64, _I64, _I32, _P, _I64, _P, _I32, _P, _P],
     "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
 }
 NO_STREAM = {"version", "last_error", "device_info"}

@@ -6,13 +6,15 @@ flags.
 
 Restores the generator(s), runs the wrapper's inference hook once at iteration 0 and returns its divergences.  The
 hook writes best_ratio_<suffix>.json (and a summaries.jsonl line) into the directory the reference's summary writer
-uses: --base_log_path itself, without the .npz suffix."""
+uses: --base_log_path itself, without the .npz suffix; with --band_ratio_stats true also the band-ratio figure and its
+numbers, band_ratio_<suffix>_0.pdf / .json."""
 import argparse
 import os
 
 import numpy
 
-from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_loaders, add_parse_cmds_for_loggers
+from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, \
+    type_ensure_strtobool
 from hypelcnn_amd.common.common_nn_ops import get_loader_from_name
 from hypelcnn_amd.gan.gan_utilities import load_gan_variables
 from hypelcnn_amd.gan.wrapper_registry import get_infer_wrapper_dict
@@ -23,6 +25,8 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--number_of_samples", nargs="?", type=int, default=6000, help="Number of samples.")
     parser.add_argument("--gan_type", nargs="?", type=str, default="cycle_gan",
                         help="Gan type to train, possible values; cycle_gan, gan_x2y and gan_y2x")
+    parser.add_argument("--band_ratio_stats", nargs="?", type=type_ensure_strtobool, default=False,
+                        help="Write band_ratio_<suffix>_<iteration>.json / .pdf (the band-ratio figure) to the log dir.")
 
 
 def build_parser():
@@ -54,6 +58,7 @@ def main(argv=None, backend=None):
                                          neighborhood=flags.neighborhood, shadow_map=shadow_map,
                                          shadow_ratio=shadow_ratio, validation_iteration_count=0,
                                          validation_sample_count=flags.number_of_samples, backend=backend)
+    hook.band_ratio_stats = bool(flags.band_ratio_stats)
     sess = C.restore_generators(hook.ctx, wrapper.create_generator_restorer(), load_gan_variables(flags.base_log_path))
     hook.after_create_session(sess, None)
     hook.after_run(0)

@@ -5,7 +5,9 @@
 
 One loop iteration = one `session.run(global_step_inc_op)` of the reference with its sequential RunTrainOpsHooks:
 every phase (generator, discriminator[, feature discriminator]) is a pre-planned list of HIP launches replayed as
-a HIP graph; the paired samples stay resident in HBM."""
+a HIP graph; the paired samples stay resident in HBM.  --band_ratio_stats true also writes the band-ratio figure and
+its numbers for the closing statistic, band_ratio_<suffix>_<step>.pdf / .json, into the log directory
+(common/band_ratio.py)."""
 import argparse
 import json
 import os
@@ -42,6 +44,7 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--discriminator_reg_scale", nargs="?", type=float, default=0.00001)
     parser.add_argument("--gen_disc_reg_scale", nargs="?", type=float, default=0.0001)
     parser.add_argument("--pairing_method", nargs="?", type=str, default="random")
+    parser.add_argument("--band_ratio_stats", nargs="?", type=b, default=False)  # band-ratio figure + numbers, log dir
     parser.add_argument("--master", nargs="?", type=str, default="")      # TF1 parameter-server flags: accepted,
     parser.add_argument("--ps_tasks", nargs="?", type=int, default=0)     # ignored (vestigial)
     parser.add_argument("--task", nargs="?", type=int, default=0)
@@ -205,8 +208,16 @@ def run_session(params, base_log_path, backend=None):
     gen.set_input("y" if "in:y" in b and "in:x" not in b else "x", src)
     gen.forward()
     ratio = shadow_ratio if shadow_ratio is not None else numpy.ones(bands, numpy.float32)
-    div_mean, div_upper, _, _ = create_stats(gen.value(the_gan_loss.generate_outputs[0], copy=False), src,
-                                             torch.as_tensor(ratio, dtype=torch.float32).to(src.device))
+    generated = gen.value(the_gan_loss.generate_outputs[0], copy=False)
+    ratio = torch.as_tensor(ratio, dtype=torch.float32).to(src.device)
+    div_mean, div_upper, _, _ = create_stats(generated, src, ratio)
+    if getattr(flags, "band_ratio_stats", False):
+        from hypelcnn_amd.classify.monitored_session_runner import is_chief
+        from hypelcnn_amd.common.band_ratio import band_ratio_stats, write_band_ratio
+        if is_chief():
+            write_band_ratio(log_dir, "band_ratio_" + ("deshadowed" if src is not xs else "shadowed"), sess.global_step,
+                             loader.get_band_measurements(), band_ratio_stats(sess.backend, generated, src, ratio),
+                             "p50", "p10", "p90")
     return [div_upper, div_mean]
 
 

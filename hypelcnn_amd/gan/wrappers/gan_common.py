@@ -300,6 +300,15 @@ class PeerValidationHook:
     def __init__(self, *validation_base_hooks):
         self._validation_base_hooks = validation_base_hooks
 
+    @property
+    def band_ratio_stats(self):
+        return all(hook.band_ratio_stats for hook in self._validation_base_hooks)
+
+    @band_ratio_stats.setter
+    def band_ratio_stats(self, on):
+        for hook in self._validation_base_hooks:
+            hook.band_ratio_stats = on
+
     def after_create_session(self, session=None, coord=None):
         for hook in self._validation_base_hooks:
             hook.after_create_session(session, coord)
@@ -325,9 +334,15 @@ class PeerValidationHook:
 
 class ValidationHook(BaseValidationHook):
     """Runs the generator `infer_model` (a symbol of the tower of `ctx`, fed through the placeholder `input_tensor`) on
-    `sample_count` fixed pixels of one side of the shadow map and tracks create_stats' divergences.  The band-ratio
-    plot of the reference is not drawn; best_ratio_<suffix>.json and a line of log_dir/summaries.jsonl record the
-    result."""
+    `sample_count` fixed pixels of one side of the shadow map and tracks create_stats' divergences;
+    best_ratio_<suffix>.json and a line of log_dir/summaries.jsonl record the result.  With `band_ratio_stats` set
+    (--band_ratio_stats true; off by default, when no file is added), every validation iteration also writes the
+    reference's band-ratio figure (print_stats :210-219) as band_ratio_<suffix>_<iteration>.pdf -- the per-band median
+    of generated / input * ratio with the 10th to 90th percentile band -- and its numbers as
+    band_ratio_<suffix>_<iteration>.json (common/band_ratio.py: the percentiles are selected on the device from the
+    generated tensor where it is)."""
+
+    band_ratio_stats = False
 
     def __init__(self, iteration_freq, sample_count, log_dir, loader, data_set, neighborhood, shadow_map, shadow_ratio,
                  input_tensor, infer_model, name_suffix, fetch_shadows, ctx, seed=1234):
@@ -370,6 +385,11 @@ class ValidationHook(BaseValidationHook):
             f.write(json.dumps({"step": int(current_iteration), f"divergence_{self._name_suffix}": div_mean}) + "\n")
         print(f"Validation metrics for {self._name_suffix} #{current_iteration}")
         print_overall_info(self.last_stats[2], self.last_stats[3])
+        if self.band_ratio_stats:
+            from hypelcnn_amd.common.band_ratio import band_ratio_stats, write_band_ratio
+            self.last_band_ratio = write_band_ratio(
+                self._log_dir, f"band_ratio_{self._name_suffix}", current_iteration, self._bands,
+                band_ratio_stats(sess.backend, generated, x, ratio), "p50", "p10", "p90")
         print(f"Divergence for {self._name_suffix}; mean:{div_mean}, upper:{div_upper}")
         print(f"Best {self._name_suffix} options:{self.best_mean_div_holder}")
 

@@ -741,6 +741,29 @@ int hypel_scene_prepare_f32(const void* src, int32_t dtype, int64_t h, int64_t w
 int hypel_scene_masked_sums(const float* scene, const uint8_t* map, int64_t hp, int64_t wp, int32_t bands, double* sums,
                             int64_t* counts, double* ws, int32_t ws_slices, hypel_stream_t stream);
 
+/* ---- band-ratio statistics (gan_common.py print_stats / create_stats; csrc/band_ratio.hip) -----------------------
+ * hypel_band_ratio_f32: ratio[i*ld_ratio + b] = num[i*ld_num + b] / den[i*ld_den + b] * scale[b] for n rows of `bands`
+ *   float32 (row strides in elements, each >= bands; scale optional: null = no multiplication).  The division is IEEE,
+ *   correctly rounded, then the multiplication, rounded on its own: NumPy's float32 num / den * scale bit for bit.
+ *   row_ok[i] (uint8) = 1 where every band of row i of the ratio is finite; *kept (device int64, cleared by the call) =
+ *   the number of such rows.  Mask and count are integer work: two calls give identical bits.  1 <= n < 2^31.
+ * hypel_column_rank_select_f32: out[r*bands + b] = the value at 0-based ascending rank ranks[r] of column b of
+ *   x [n][bands] (float32, row stride ld) over the rows with row_ok[i] != 0 (null: all rows), exactly.  `kept` is the
+ *   number of those rows (n when row_ok is null); `ranks` is a HOST array of n_ranks values in [0, kept), in any order,
+ *   repeats allowed, 1 <= n_ranks <= HYPEL_COLUMN_RANK_MAX_RANKS -- all checked before anything is launched.  Rows
+ *   masked out are never read and may hold NaN or inf; kept rows are finite.  Order is by value: -0.0 and +0.0 are
+ *   equal and either may be returned.  ws: bands * HYPEL_COLUMN_RANK_WS_WORDS uint32, 16-byte aligned, cleared by the
+ *   call.  Integer counts only: two calls give identical bits.  1 <= n < 2^31, bands <= HYPEL_COLUMN_RANK_MAX_BANDS. */
+#define HYPEL_COLUMN_RANK_MAX_RANKS 8
+#define HYPEL_COLUMN_RANK_MAX_BANDS 65536 /* columns of one hypel_column_rank_select_f32 call (a wider matrix: call per window) */
+#define HYPEL_COLUMN_RANK_WS_WORDS 2320 /* 256 (level 1) + 8 * 256 (levels 2..4 per rank) + 8 * 2 (prefix, rank) */
+int hypel_band_ratio_f32(const float* num, int64_t ld_num, const float* den, int64_t ld_den, int64_t n, int32_t bands,
+                         const float* scale, float* ratio, int64_t ld_ratio, uint8_t* row_ok, int64_t* kept,
+                         hypel_stream_t stream);
+int hypel_column_rank_select_f32(const float* x, int64_t ld, int64_t n, int32_t bands, const uint8_t* row_ok,
+                                 int64_t kept, const int64_t* ranks, int32_t n_ranks, float* out, uint32_t* ws,
+                                 hypel_stream_t stream);
+
 /* ---- TIFF layouts (common/tiff_io.py; csrc/tiff.hip) ---------------------------------------------------------------
  * From "the file's bytes are in HBM" to the raster [h][w][spp] the scene preparation reads.  A segment is a strip or
  * a tile; segment s of the table is plane s / (segs_across * segs_down) (chunky files have one plane), row of
