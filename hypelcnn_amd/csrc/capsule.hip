@@ -355,10 +355,10 @@ __global__ __launch_bounds__(256) void caps_mask_bwd_kernel(const float* __restr
 }
 
 bool caps_shape_ok(int64_t N, int I, int J, int D) {
-    return N > 0 && N <= 65535 && I > 0 && J > 0 && D > 0 && D <= HYPEL_CAPS_MAX_D && (int64_t)J * D <= HYPEL_CAPS_MAX_JD;
+    return N > 0 && N <= HYPEL_CAPS_MAX_N && I > 0 && J > 0 && D > 0 && D <= HYPEL_CAPS_MAX_D && (int64_t)J * D <= HYPEL_CAPS_MAX_JD;
 }
 
-constexpr size_t kMaxDynLds = 64 * 1024;
+constexpr size_t kMaxDynLds = HYPEL_CAPS_MAX_LDS;  // graph.py::capsule_fits restates the two LDS formulas below
 
 }  // namespace
 

@@ -620,6 +620,30 @@ def local_response_normalization(inputs, depth_radius=5, bias=1.0, alpha=1.0, be
 
 CAPSULE_MAX_WIDTH = 32  # hypel.h HYPEL_CAPS_MAX_D: capsule width the routing kernels keep in registers
 CAPSULE_MAX_COLS = 512  # ... HYPEL_CAPS_MAX_JD: classes x width
+CAPSULE_MAX_BATCH = 65535  # ... the sample index is the grid's y dimension in the routing sums
+CAPSULE_LDS_BYTES = 64 * 1024  # ... dynamic LDS a block of the two u_hat products may ask for
+CAPSULE_TILE = 16  # ... samples per staged tile of the two u_hat products
+
+
+def capsule_lds_bytes(classes, width, iterations):
+    """(forward, backward) dynamic LDS of hypel_caps_uhat_fwd / hypel_caps_uhat_bwd (csrc/capsule.hip) in bytes: the
+    forward stages W_i, bias_i and a tile of x; the backward W_i and a tile of du_hat at an odd row stride, a tile of x
+    and the 2R-1 coefficient rows of its capsule."""
+    jd = classes * width
+    jdp = jd | 1
+    fwd = (width + 1) * jd + CAPSULE_TILE * width
+    bwd = width * jdp + CAPSULE_TILE * jdp + CAPSULE_TILE * width + (2 * iterations - 1) * classes
+    return 4 * fwd, 4 * bwd
+
+
+def capsule_fits(classes, width, iterations, training):
+    """The argument rules of the hypel_caps_* entry points restated (include/hypel.h "capsule classifier"), so that a
+    shape they would refuse at the first launch is refused when the graph is built.  An evaluation tower launches the
+    forward product only."""
+    if not (1 <= width <= CAPSULE_MAX_WIDTH and classes >= 1 and classes * width <= CAPSULE_MAX_COLS and iterations >= 1):
+        return False
+    fwd, bwd = capsule_lds_bytes(classes, width, iterations)
+    return fwd <= CAPSULE_LDS_BYTES and (not training or bwd <= CAPSULE_LDS_BYTES)
 
 
 def capsule_routing(primary, capsule_count, classes, width, iterations, scope_prefix="DigitCaps_layer_w_"):
@@ -634,6 +658,12 @@ def capsule_routing(primary, capsule_count, classes, width, iterations, scope_pr
         raise NotImplementedError(f"capsule_routing: width {width} / {classes * width} prediction columns exceed what the "
                                   f"routing kernels hold per thread ({CAPSULE_MAX_WIDTH} / {CAPSULE_MAX_COLS})")
     tower = primary.tower
+    if not capsule_fits(classes, width, iterations, tower.is_training):
+        fwd, bwd = capsule_lds_bytes(classes, width, iterations)
+        raise NotImplementedError(f"capsule_routing: {classes} classes of width {width} with {iterations} routing iterations "
+                                  f"need {fwd} (forward) / {bwd} (backward) bytes of LDS per block in the u_hat products, "
+                                  f"above their {CAPSULE_LDS_BYTES}-byte limit"
+                                  + ("" if tower.is_training else " (an evaluation tower needs the forward product only)"))
     st = tower.store
     n_caps = primary.npix * capsule_count
     jd = classes * width

@@ -1911,6 +1911,10 @@ class TowerPlan:
             raise NotImplementedError("capsule routing is single-device only: its agreement is summed over the batch, so "
                                       "data parallel (WORLD_SIZE > 1) would need an all-reduce inside every routing iteration")
         nb, src = self.nb, node.src
+        if nb > G.CAPSULE_MAX_BATCH:
+            raise NotImplementedError(f"capsule routing: a batch of {nb} exceeds the {G.CAPSULE_MAX_BATCH} samples one launch of "
+                                      "the routing kernels covers (the sample index is a grid dimension): use a smaller "
+                                      "batch size")
         J, D, R, I = node.classes, node.width, node.iterations, node.capsules
         M = src.c // D
         jd = J * D

@@ -618,9 +618,19 @@ int hypel_nce_loss(const float* g, int64_t ldg, const float* r, int64_t ldr, int
  *   uhat_bwd   duhat[n][i][col] = sum_t coefs[t][i][col / d] * vecs[t][n][col] (n_terms pairs, never stored);
  *              dw_i = x_i^T duhat_i, dbias_i = sum_n duhat_i (both or neither), dx[n][i][:] = duhat[n][i][:] . W_i^T
  *              at dpix[i / m] + n * lddx + (i % m) * d (null dx = skipped); acc_w / acc_x: add to what is there
- *   mask_fwd   out[n][e] = sum_j labels[n][j] * v[n][j * d + e];  mask_bwd: gv[n][j * d + e] (+)= labels[n][j] * gout[n][e] */
+ *   mask_fwd   out[n][e] = sum_j labels[n][j] * v[n][j * d + e];  mask_bwd: gv[n][j * d + e] (+)= labels[n][j] * gout[n][e]
+ * Limits (a call outside them returns -1 before anything is launched): 1 <= n <= HYPEL_CAPS_MAX_N (the sample index is
+ * a grid dimension), d <= HYPEL_CAPS_MAX_D, jd <= HYPEL_CAPS_MAX_JD, i % m == 0, jd % d == 0, and the dynamic LDS of the
+ * two u_hat products <= HYPEL_CAPS_MAX_LDS bytes:
+ *   uhat_fwd   4 * ((d + 1) * jd + 16 * d)
+ *   uhat_bwd   4 * (d * jdp + 16 * jdp + 16 * d + n_terms * j),  jdp = jd | 1,  n_terms = 2 R - 1 for R routing iterations
+ * At d = 16 the backward admits j <= 31 (and that only for R <= 4; j = 32 never), at d = 32 j <= 10; the forward alone
+ * admits j = 32 at d = 16 and j <= 15 at d = 32.  hypelcnn_amd/graph.py::capsule_fits restates the rule and refuses such
+ * a model when it is built. */
 #define HYPEL_CAPS_MAX_D 32
 #define HYPEL_CAPS_MAX_JD 512
+#define HYPEL_CAPS_MAX_N 65535
+#define HYPEL_CAPS_MAX_LDS 65536
 int hypel_caps_uhat_fwd(const float* x, const int64_t* pix, int64_t ldx, int32_t m, const float* w, const float* bias,
                         int64_t n, int32_t i, int32_t d, int32_t jd, float* uhat, hypel_stream_t stream);
 int hypel_caps_route_fwd(const float* uhat, const float* coef, int64_t n, int32_t i, int32_t j, int32_t d, float* s,

@@ -141,6 +141,25 @@ def test_refusals_name_their_reason(monkeypatch):
     assert G.conv2d(x, 8, [1, 1], scope="c1", padding="VALID").hw == (5, 5)
     with pytest.raises(NotImplementedError, match="routing kernels"):
         G.capsule_routing(G.conv2d(x, 2 * 64, [1, 1], scope="wide"), 2, 3, 64, 3)
+
+    def route(training, classes, width, iterations=3):
+        t = G.Tower(G.VariableStore("t"), training)
+        return G.capsule_routing(G.conv2d(t.placeholder("x", (1, 1), 4), width, [1, 1], scope="c"), 1, classes, width, iterations)
+
+    # the LDS of the two u_hat products (include/hypel.h "Limits"): corner shapes that pass the width / column limits
+    for classes, width in ((32, 16), (11, 32), (15, 32), (16, 32)):
+        with pytest.raises(NotImplementedError, match=r"bytes of LDS per block.*65536-byte limit"):
+            route(True, classes, width)
+    with pytest.raises(NotImplementedError, match="67328"):
+        route(True, 32, 16)
+    with pytest.raises(NotImplementedError, match="LDS"):
+        route(True, 31, 16, iterations=5)  # the backward's 2R-1 coefficient rows count too
+    with pytest.raises(NotImplementedError, match="evaluation tower needs the forward product only"):
+        route(False, 16, 32)
+    for training, classes, width in ((True, 31, 16), (True, 10, 32), (True, 20, 16), (False, 32, 16), (False, 11, 32),
+                                     (False, 15, 32)):
+        assert route(training, classes, width)[1].c == classes * width
+    assert route(True, 31, 16, iterations=4)[0].c == 31
     monkeypatch.setenv("WORLD_SIZE", "2")
     alg = dict(iter_routing=1, conv_layer_kernel_size=1, primary_caps_kernel_size=1, feature_count=4, primary_capsule_count=2,
                digit_capsule_output_space=4, lrelu_alpha=0.1, enable_decoding=False)
@@ -151,6 +170,50 @@ def test_refusals_name_their_reason(monkeypatch):
     from hypelcnn_amd import tf_facade
     with pytest.raises(NotImplementedError, match="facade"):
         tf_facade.reference_model("CAPModel", "/nonexistent")
+
+
+def test_planner_refuses_a_batch_beyond_the_routing_grid():
+    alg = dict(iter_routing=2, conv_layer_kernel_size=1, primary_caps_kernel_size=1, feature_count=2, primary_capsule_count=1,
+               digit_capsule_output_space=2, optimizer="AdamOptimizer", learning_rate=1e-4, learning_rate_decay_factor=0.96,
+               learning_rate_decay_step=350, lrelu_alpha=0.1, enable_decoding=False)
+    built = PU.build("CAPModel", 1, 2, 2, alg, EmuBackend())
+    built.ctx.session()
+    assert G.CAPSULE_MAX_BATCH == 65535
+    with pytest.raises(NotImplementedError, match="batch of 65536 exceeds the 65535"):
+        built.train_step.compiled(65536)
+    with pytest.raises(NotImplementedError, match="batch of 65536 exceeds the 65535"):
+        PU.run_eval(built, np.zeros((65536, 1, 1, 2), np.float32))
+    built.train_step.compiled(65535)
+
+
+def test_capsule_fits_never_admits_what_the_kernels_refuse():
+    """(J, D, R) over the whole admitted domain against the formulas as include/hypel.h documents them: what the Python
+    rule admits fits the 64 KB, and what it refuses inside the width / column limits does not (the rule is the kernels',
+    not a narrower one)."""
+    cap = 64 * 1024
+    admitted = refused = 0
+    for d in range(1, 33):
+        for j in range(1, 512 // d + 1):
+            jd = j * d
+            fwd = 4 * ((d + 1) * jd + 16 * d)
+            for r in range(1, 9):
+                jdp, terms = jd | 1, 2 * r - 1
+                bwd = 4 * (d * jdp + 16 * jdp + 16 * d + terms * j)
+                assert G.capsule_lds_bytes(j, d, r) == (fwd, bwd)
+                assert G.capsule_fits(j, d, r, False) == (fwd <= cap)
+                assert G.capsule_fits(j, d, r, True) == (fwd <= cap and bwd <= cap)
+                admitted += G.capsule_fits(j, d, r, True)
+                refused += not G.capsule_fits(j, d, r, True)
+    assert admitted > 10000 and refused > 100
+    assert not G.capsule_fits(1, 33, 1, False) and not G.capsule_fits(513, 1, 1, False) and not G.capsule_fits(2, 2, 0, False)
+    import re
+    header = open(os.path.join(os.path.dirname(GOLDEN), "..", "include", "hypel.h")).read()
+    limits = {k: int(v) for k, v in re.findall(r"#define\s+HYPEL_CAPS_MAX_(\w+)\s+(\d+)", header)}
+    assert limits == dict(D=G.CAPSULE_MAX_WIDTH, JD=G.CAPSULE_MAX_COLS, N=G.CAPSULE_MAX_BATCH, LDS=G.CAPSULE_LDS_BYTES)
+    # the corners the header names
+    assert G.capsule_fits(31, 16, 4, True) and not G.capsule_fits(31, 16, 5, True) and not G.capsule_fits(32, 16, 1, True)
+    assert G.capsule_fits(10, 32, 3, True) and not G.capsule_fits(11, 32, 1, True)
+    assert G.capsule_fits(32, 16, 3, False) and G.capsule_fits(15, 32, 3, False) and not G.capsule_fits(16, 32, 3, False)
 
 
 def test_planner_refuses_a_data_parallel_session(fixture):
