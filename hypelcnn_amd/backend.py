@@ -16,58 +16,49 @@ import subprocess
 import numpy as np
 import torch
 
+from . import abi
+from .abi import HypelError  # noqa: F401 (raised here, imported from here by the rest of the package)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HYPEL_LIB_PATH: an alternative build of the same ABI (A/B experiments on one GPU box)
 LIB_PATH = os.environ.get("HYPEL_LIB_PATH") or os.path.join(_HERE, "csrc", "libhypel_hip.so")
 
-ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4
-GEMM_BM = 128
-ABI_VERSION = 8  # include/hypel.h HYPEL_ABI_VERSION: a library built from other headers is refused at load time
+ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID, ACT_TANH = (abi.const("HYPEL_ACT_" + k)
+                                                         for k in ("NONE", "LRELU", "RELU", "SIGMOID", "TANH"))
+GEMM_BM = abi.const("HYPEL_GEMM_BM")
+ABI_VERSION = abi.const("HYPEL_ABI_VERSION")  # a library built from other headers is refused at load time
 
-SEG_DTYPE = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("k", "<i4"), ("reserved", "<i4")])
-GROUP_DTYPE = np.dtype([("c_off", "<i8"), ("seg_begin", "<i4"), ("seg_count", "<i4"), ("rows", "<i4"),
-                        ("reserved", "<i4")])
-LOSS_TERM_DTYPE = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("da_off", "<i8"), ("db_off", "<i8"), ("lda", "<i8"),
-                            ("ldb", "<i8"), ("ldda", "<i8"), ("lddb", "<i8"), ("rows", "<i8"), ("mode", "<i4"), ("c", "<i4"),
-                            ("acc_da", "<i4"), ("acc_db", "<i4"), ("target", "<f4"), ("gcoef", "<f4"), ("pscale", "<f4"),
-                            ("slot", "<i4")])
-LOSS_NONE = -(1 << 63)
-MTILE_DTYPE = np.dtype([("c_off", "<i8"), ("a_off0", "<i8"), ("b_off0", "<i8"), ("m0", "<i4"), ("rows", "<i4"),
-                        ("n0", "<i4"), ("n", "<i4"), ("seg_begin", "<i4"), ("seg_count", "<i4"), ("k0", "<i4"),
-                        ("flags", "<i4"), ("lda", "<i4"), ("ldb", "<i4"), ("ldc", "<i4"), ("reserved", "<i4")])
-REDUCE_ENTRY_DTYPE = np.dtype([("partial_off", "<i8"), ("out_off", "<i8"), ("stride", "<i8"), ("count", "<i8"),
-                               ("n_splits", "<i4"), ("flags", "<i4")])
-TILE_DTYPE = np.dtype([("group", "<i4"), ("m0", "<i4"), ("rows", "<i4"), ("seg_begin", "<i4"), ("seg_count", "<i4"),
-                       ("k0", "<i4"), ("c_off", "<i8"), ("a_off0", "<i8"), ("b_off0", "<i8"),
-                       ("flags", "<i4"), ("n", "<i4")])
-TILE_PLAIN = 1  # include/hypel.h HYPEL_TILE_PLAIN: K-slice partial (no bias / accumulate / shortcut gather)
-# include/hypel.h HYPEL_DTYPE_*: output dtypes of hypel_denorm_scatter, input dtypes of hypel_hsi_to_srgb
-OUT_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2, np.dtype(np.uint8): 3}
-RGB_U8, RGB_F32 = 0, 1  # include/hypel.h HYPEL_RGB_*: output modes of hypel_hsi_to_srgb
-# include/hypel.h hypel_svm_pair_t, HYPEL_SVM_*
-SVM_PAIR_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<i4"), ("out_off", "<i8")])
-# include/hypel.h hypel_svm_job_t: a pair + the element offset of its plane of K + its C (hypel_svm_smo_grid)
-SVM_JOB_DTYPE = np.dtype([("a0", "<i4"), ("na", "<i4"), ("b0", "<i4"), ("nb", "<i4"), ("out_off", "<i8"),
-                          ("k_off", "<i8"), ("c", "<f8")])
-SVM_RBF, SVM_POLY = 0, 1
-SVM_CONVERGED, SVM_NOT_CONVERGED = 0, 1
-SVM_MAX_ITER_LIMIT = 1000000
-SCENE_RANK_WS_WORDS = 772  # include/hypel.h HYPEL_SCENE_RANK_WS_WORDS: uint32 of workspace per band
-# include/hypel.h HYPEL_COLUMN_RANK_*: uint32 of workspace per band and ranks per call of hypel_column_rank_select_f32
-COLUMN_RANK_WS_WORDS, COLUMN_RANK_MAX_RANKS, COLUMN_RANK_MAX_BANDS = 2320, 8, 65536
-COMPACT_TILE = 4096  # include/hypel.h HYPEL_COMPACT_TILE: pixels per int32 of hypel_mask_compact_points_i32's workspace
-SUMMARY_SLICE = 32768  # include/hypel.h HYPEL_SUMMARY_SLICE: elements per slice of hypel_tensor_summary_f32
-SUMMARY_MAX_LIMITS = 2048  # include/hypel.h HYPEL_SUMMARY_MAX_LIMITS
-# include/hypel.h HYPEL_FOREST_*: rows sorted per column for the bin edges, edges per column, classes of the LDS
-# histogram, depth cap of the level loop
-FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = 16384, 255, 32, 64
-# include/hypel.h hypel_forest_node_t: a leaf has left = -1 - (its row of the leaf table)
-FOREST_NODE_DTYPE = np.dtype([("feature", "<i4"), ("threshold", "<f4"), ("left", "<i4"), ("right", "<i4")])
-# include/hypel.h hypel_tiff_seg_t (byte offsets and lengths), HYPEL_TIFF_*: codecs of hypel_tiff_unpack
-TIFF_SEG_DTYPE = np.dtype([("src_off", "<i8"), ("src_len", "<i8"), ("dst_off", "<i8"), ("dst_len", "<i8")])
-TIFF_LZW, TIFF_PACKBITS = 5, 32773
-COPY_BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("src_ld", "<i4"),
-                             ("dst_ld", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
+SEG_DTYPE = abi.struct("hypel_seg_t")
+GROUP_DTYPE = abi.struct("hypel_group_t")
+TILE_DTYPE = abi.struct("hypel_tile_t")
+MTILE_DTYPE = abi.struct("hypel_mtile_t")
+REDUCE_ENTRY_DTYPE = abi.struct("hypel_reduce_entry_t")
+COPY_BLOCK_DTYPE = abi.struct("hypel_copy_block_t")
+LOSS_TERM_DTYPE = abi.struct("hypel_loss_term_t")
+LOSS_NONE = abi.const("HYPEL_LOSS_NONE")
+TILE_PLAIN = abi.const("HYPEL_TILE_PLAIN")  # K-slice partial (no bias / accumulate / shortcut gather)
+# output dtypes of hypel_denorm_scatter, input dtypes of hypel_hsi_to_srgb
+OUT_DTYPES = {np.dtype(t): abi.const("HYPEL_DTYPE_" + k)
+              for t, k in ((np.float32, "F32"), (np.uint16, "U16"), (np.int16, "I16"), (np.uint8, "U8"))}
+RGB_U8, RGB_F32 = abi.const("HYPEL_RGB_U8"), abi.const("HYPEL_RGB_F32")  # output modes of hypel_hsi_to_srgb
+SVM_PAIR_DTYPE = abi.struct("hypel_svm_pair_t")
+SVM_JOB_DTYPE = abi.struct("hypel_svm_job_t")  # a pair + the element offset of its plane of K + its C (hypel_svm_smo_grid)
+SVM_RBF, SVM_POLY = abi.const("HYPEL_SVM_RBF"), abi.const("HYPEL_SVM_POLY")
+SVM_CONVERGED, SVM_NOT_CONVERGED = abi.const("HYPEL_SVM_CONVERGED"), abi.const("HYPEL_SVM_NOT_CONVERGED")
+SVM_MAX_ITER_LIMIT = abi.const("HYPEL_SVM_MAX_ITER_LIMIT")
+SCENE_RANK_WS_WORDS = abi.const("HYPEL_SCENE_RANK_WS_WORDS")  # uint32 of workspace per band
+# uint32 of workspace per band and ranks per call of hypel_column_rank_select_f32
+COLUMN_RANK_WS_WORDS, COLUMN_RANK_MAX_RANKS, COLUMN_RANK_MAX_BANDS = (
+    abi.const("HYPEL_COLUMN_RANK_" + k) for k in ("WS_WORDS", "MAX_RANKS", "MAX_BANDS"))
+COMPACT_TILE = abi.const("HYPEL_COMPACT_TILE")  # pixels per int32 of hypel_mask_compact_points_i32's workspace
+SUMMARY_SLICE = abi.const("HYPEL_SUMMARY_SLICE")  # elements per slice of hypel_tensor_summary_f32
+SUMMARY_MAX_LIMITS = abi.const("HYPEL_SUMMARY_MAX_LIMITS")
+# rows sorted per column for the bin edges, edges per column, classes of the LDS histogram, depth cap of the level loop
+FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = (
+    abi.const("HYPEL_FOREST_" + k) for k in ("EDGE_ROWS", "MAX_EDGES", "MAX_CLASSES", "MAX_DEPTH"))
+FOREST_NODE_DTYPE = abi.struct("hypel_forest_node_t")  # a leaf has left = -1 - (its row of the leaf table)
+TIFF_SEG_DTYPE = abi.struct("hypel_tiff_seg_t")  # byte offsets and lengths
+TIFF_LZW, TIFF_PACKBITS = abi.const("HYPEL_TIFF_LZW"), abi.const("HYPEL_TIFF_PACKBITS")  # codecs of hypel_tiff_unpack
 
 
 class Ref:
@@ -92,132 +83,12 @@ def build_library(verbose=False):
     return LIB_PATH
 
 
-_P, _I64, _I32, _F, _U64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
-_F64 = ctypes.c_double
+_P = ctypes.c_void_p
 
-# name -> argument ctypes (stream appended automatically); mirrors include/hypel.h one to one
-SIGNATURES = {
-    "nhwc_to_pnc": [_P, _P, _I64, _I32, _I32, _I64],
-    "pnc_to_nhwc": [_P, _I64, _P, _I64, _I32, _I32],
-    "fill_f32": [_P, _I64, _F],
-    "seg_gemm_f32": [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _I32, _P, _I32],
-    "seg_gemm_stats_f32": [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P],
-    "seg_gemm_res_f32": [_P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _I64, _P],
-    "reduce_splits_f32": [_P, _I64, _I32, _P, _I64, _I32, _P, _I32, _I64],
-    "reduce_splits_pair_f32": [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I32, _I32],
-    "seg_gemm_multi_f32": [_P, _I32, _I32, _I32, _P, _P, _I32],
-    "copy_blocks_f32": [_P, _P, _I32, _I64],
-    "reduce_splits_wave_multi_f32": [_P, _P, _I32, _I64],
-    "reduce_splits_multi_f32": [_P, _P, _I32],
-    "reduce_splits_multi_sized_f32": [_P, _P, _I32, _I64],
-    "col_stats_partial": [_P, _I64, _I64, _I32, _I32, _P],
-    "bn_act_small_fwd": [_P, _I64, _I64, _I32, _F, _P, _I32, _F, _P, _I64, _P, _P, _P, _P, _F, _P, _I64],
-    "bn_act_small_bwd": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _P, _I64, _P, _I64, _P, _I32],
-    "bn_finalize": [_P, _I32, _I32, _I64, _I32, _F, _P, _P, _P, _P, _F],
-    "bn_merge_partials": [_P, _I32, _I32, _I64, _I32, _P],
-    "bn_finalize_ranks": [_P, _I32, _I32, _F, _P, _P, _P, _P, _F],
-    "rstd_from_var": [_P, _I32, _F, _P],
-    "bn_act_fwd": [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64],
-    "bn_act_bwd_reduce": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _P, _I64, _I32, _P],
-    "act_bias_bwd_reduce": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _P, _I64, _I32, _P, _P, _I64],
-    "bwd_reduce_finalize": [_P, _I32, _I32, _P, _P, _I32],
-    "bn_act_bwd_apply": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _P, _I64, _P, _P, _I64],
-    "bn_act_bwd_apply_global": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _P, _I64, _P, _I64, _P, _I64],
-    "chanmap_bwd": [_P, _I64, _I64, _I32, _P, _I64, _I32, _P, _I32],
-    "softmax_xent": [_P, _I64, _I64, _I32, _P, _I64, _P, _P, _I64, _F],
-    "mse": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I64, _F, _P],
-    "sum_f32": [_P, _I64, _F, _P, _P],
-    "adam_tf1": [_P, _P, _P, _P, _I64, _F, _F, _F, _F],
-    "momentum_tf1": [_P, _P, _P, _I64, _F, _F],
-    "adam_tf1_guarded": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P],
-    "momentum_tf1_guarded": [_P, _P, _P, _I64, _F, _F, _P],
-    "loss_guard_f32": [_P, _P, _P],
-    "mse_partial_f32": [_P, _I64, _P, _I64, _I64, _I32, _P, _I64, _F, _P],
-    "loss_finalize_f32": [_P, _I32, _P, _F64, _P, _P, _P, _P],
-    "dropout_mask": [_P, _I64, _F, _U64, _P],
-    "step_inc": [_P],
-    "argmax_confusion": [_P, _I64, _I64, _I32, _P, _P, _P],
-    "gather_patches_f32": [_P, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P],
-    "gather_patches_2x_f32": [_P, _P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _I32, _P],
-    "augment_patches_f32": [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
-    "gather_pairs_f32": [_P, _P, _P, _I64, _I32, _P, _P, _P, _F, _P, _P],
-    "argmax_scatter": [_P, _I64, _I64, _I32, _P, _P, _I64],
-    "denorm_scatter": [_P, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _I64],
-    "hsi_to_srgb": [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _I32, _P],
-    "lrn_fwd": [_P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64],
-    "lrn_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _F, _P, _I64, _I32],
-    "gan_generator_fwd": [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64],
-    "gan_generator_bwd": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _P, _P],
-    "dense_stack_fwd": [_P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _I64],
-    "dense_stack_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _I64, _I32,
-                        _P, _P],
-    "gan_generator_fwd_keep": [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P],
-    "gan_generator_bwd_kept": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _I32, _P, _P, _P],
-    "gan_generator_fwd_tap": [_P, _I64, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P],
-    "gan_generator_bwd_tap": [_P, _I64, _P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _I32, _P, _P, _P],
-    "copy_pair_f32": [_P, _P, _I64, _P, _P, _I64],
-    "gan_generator_fwd_apps": [_P, _I64, _I64, _I32, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P],
-    "gan_generator_bwd_apps": [_P, _I64, _P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _I32,
-                               _P, _P, _P],
-    "dense_stack_fwd_apps": [_P, _I64, _I64, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P,
-                             _I64],
-    "dense_stack_bwd_apps": [_P, _I64, _P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32,
-                             _I32, _F, _P, _P, _P, _I64, _I32, _P, _P],
-    "gan_loss": [_I32, _P, _I64, _P, _I64, _I64, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
-    "l2_reg": [_P, _I64, _F, _P, _I32, _P, _P],
-    "loss_finalize_slots": [_P, _I32, _P, _I32],
-    "loss_terms_slots": [_P, _P, _I32, _P],
-    "l2norm_fwd": [_P, _I64, _I64, _I32, _P, _I64, _P],
-    "l2norm_parts_fwd": [_P, _I64, _I64, _I32, _I32, _P, _I64, _P],
-    "l2norm_parts_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _I64, _I32],
-    "l2norm_segs_fwd": [_P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P],
-    "l2norm_segs_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _I64, _I32],
-    "l2norm_bwd": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I64, _I32],
-    "caps_uhat_fwd": [_P, _P, _I64, _I32, _P, _P, _I64, _I32, _I32, _I32, _P],
-    "caps_route_fwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
-    "caps_agree_fwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
-    "caps_head_bwd": [_P, _P, _P, _I64, _I32, _I32, _P],
-    "caps_agree_bwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
-    "caps_route_bwd": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
-    "caps_uhat_bwd": [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _I64, _I32],
-    "caps_mask_fwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _I64],
-    "caps_mask_bwd": [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32],
-    "svm_center_norms_f32": [_P, _I64, _I64, _I32, _P, _P],
-    "svm_kernel_apply_f32": [_P, _I64, _I64, _I32, _I32, _F64, _F64, _I32, _P, _P],
-    "svm_smo_ovo": [_P, _I64, _P, _I32, _I32, _F64, _F64, _I32, _P, _P, _P, _P, _P, _P],
-    "svm_vote": [_P, _I64, _I64, _I32, _P, _P, _P, _I64],
-    "svm_kernel_planes_f32": [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _I64],
-    "svm_smo_grid": [_P, _I64, _P, _P, _I32, _I32, _F64, _I32, _P, _P, _P, _P, _P, _P],
-    "svm_scatter_coef_f32": [_P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P, _I64, _P],
-    "svm_vote_score": [_P, _I64, _I64, _I32, _I32, _I32, _P, _P],
-    "scene_extrema": [_P, _I32, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I32],
-    "scene_rank_select_u16": [_P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P],
-    "scene_prepare_f32": [_P, _I32, _I64, _I64, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P],
-    "scene_masked_sums": [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I32],
-    "mask_dilate_l1_u8": [_P, _I64, _I64, _I32, _P, _P],
-    "pair_masks_u8": [_P, _P, _P, _I64, _P, _P],
-    "mask_compact_points_i32": [_P, _I64, _I64, _P, _I64, _P, _P],
-    "points_expand_i32": [_P, _I64, _I32, _I64, _P],
-    "tensor_summary_f32": [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _I32],
-    "forest_bin_edges_f32": [_P, _I64, _I64, _I32, _P, _I32, _P, _P],
-    "forest_bin_u8": [_P, _I64, _I64, _I32, _P, _P, _P, _I64],
-    "forest_split_hist": [_P, _I64, _P, _P, _I64, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P],
-    "forest_split_apply": [_P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32,
-                           _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "forest_predict_rows": [_P, _I64, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _I64, _P],
-    "forest_predict_scene": [_P, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _P,
-                             _I64],
-    "tiff_unpack": [_P, _I64, _P, _I32, _I32, _P, _I64, _P],
-    "tiff_assemble": [_P, _I64, _P, _I32, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
-    "band_ratio_f32": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I64, _P, _P],
-    "column_rank_select_f32": [_P, _I64, _I64, _I32, _P, _I64, _P, _I32, _P, _P],
-    "nce_loss": [_P, _I64, _P, _I64, _I64, _I32, _I32, _F, _F, _P, _I32, _P, _I64, _I32, _P, _I64, _I32, _P],
-}
-NO_STREAM = {"version", "last_error", "device_info"}
-
-
-class HypelError(RuntimeError):
-    pass
+# launch entry points (last parameter `hypel_stream_t stream`; the hypel_graph_* calls control a capture and are no
+# launches): short name -> argument ctypes without the stream
+SIGNATURES = {name[len("hypel_"):]: [t for _, t in params[:-1]] for name, (_, params) in abi.FUNCTIONS.items()
+              if params and params[-1][0] == "stream" and not name.startswith("hypel_graph_")}
 
 
 def load_library(path=LIB_PATH):
@@ -225,37 +96,25 @@ def load_library(path=LIB_PATH):
         raise HypelError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          f"(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    lib.hypel_last_error.restype = ctypes.c_char_p
-    lib.hypel_version.restype = ctypes.c_int
-    for name, sig in SIGNATURES.items():
-        fn = getattr(lib, "hypel_" + name, None)
+    for name, (restype, params) in abi.FUNCTIONS.items():
+        fn = getattr(lib, name, None)
         if fn is None:
             continue  # optional entry points (checked by tests/test_abi.py against the header)
-        fn.argtypes = list(sig) + [_P]
-        fn.restype = ctypes.c_int
-    lib.hypel_graph_begin_capture.argtypes = [_P]
-    lib.hypel_graph_end_capture.argtypes = [_P, ctypes.POINTER(_P)]
-    lib.hypel_graph_launch.argtypes = [_P, _P]
-    lib.hypel_graph_destroy.argtypes = [_P]
-    lib.hypel_device_info.argtypes = [ctypes.POINTER(_I32), ctypes.POINTER(_I32)]
-    lib.hypel_gan_generator_blocks.argtypes = [_I64]
-    lib.hypel_gan_generator_blocks.restype = ctypes.c_int
-    lib.hypel_dense_stack_blocks.argtypes = [_I64]
-    lib.hypel_dense_stack_blocks.restype = ctypes.c_int
-    lib.hypel_gan_generator_blocks_apps.argtypes = [_I64, _I32]
-    lib.hypel_gan_generator_blocks_apps.restype = ctypes.c_int
-    lib.hypel_dense_stack_blocks_apps.argtypes = [_I64, _I32]
-    lib.hypel_dense_stack_blocks_apps.restype = ctypes.c_int
-    lib.hypel_dense_stack_supported.argtypes = [_I32] * 6
-    lib.hypel_dense_stack_supported.restype = ctypes.c_int
-    lib.hypel_gan_generator_tap_supported.argtypes = [_I32]
-    lib.hypel_gan_generator_tap_supported.restype = ctypes.c_int
-    lib.hypel_gan_generator_keep_floats.argtypes = [_I64, _I32, _I32]
-    lib.hypel_gan_generator_keep_floats.restype = ctypes.c_int64
+        fn.argtypes = [t for _, t in params]
+        fn.restype = restype
     return lib
 
 
-COLLECTIVES = ("_allreduce", "_allgather")
+# host-side pseudo-launches of a plan (bind_collective) and their parameter names
+COLLECTIVES = {"_allreduce": ("ref", "count"), "_allgather": ("src", "count", "dst")}
+
+
+def arg_index(name, param):
+    """Position of the header's parameter `param` in the argument tuple of a `name` launch."""
+    names = COLLECTIVES.get(name) or [p for p, _ in abi.FUNCTIONS["hypel_" + name][1]]
+    if param not in names:
+        raise HypelError(f"hypel_{name} has no parameter {param!r}: its parameters are ({', '.join(names)})")
+    return names.index(param)
 
 
 def bind_collective(name, args):

@@ -15,10 +15,11 @@ their numpy emulation of the same entry points."""
 import numpy as np
 import torch
 
+from hypelcnn_amd import abi
 from hypelcnn_amd.backend import (Ref, SVM_MAX_ITER_LIMIT, SVM_NOT_CONVERGED, SVM_PAIR_DTYPE, SVM_POLY, SVM_RBF)
 from hypelcnn_amd.gemm_tables import GemmTables
 
-GEMM_SPLIT6 = 0x8000  # include/hypel.h HYPEL_GEMM_SPLIT6
+GEMM_SPLIT6 = abi.const("HYPEL_GEMM_SPLIT6")
 # Iteration cap of a pair (include/hypel.h: the solver loop is bounded).  libsvm's own max(10^7, 100 l) is too long for
 # a shared device.  On the fixture problems of tests/golden/reference_classic_ml.json the emulation of this solver needs
 # at most 1 120 iterations for a pair at tol = 1e-6 (recorded there per case as "emu_n_iter_max"; scikit-learn: 1 093);

@@ -17,7 +17,6 @@ to load a written file back.  The implementation follows the published format (t
 tensor_bundle.proto) and is tested by round trip, by hand-assembled known-answer bytes for every primitive (varints,
 protobuf fields, block trailer, masked CRC-32C with the RFC 3720 vectors) and by corruption detection.
 """
-import ctypes
 import os
 import struct
 
@@ -40,8 +39,6 @@ def crc32c(data, crc=0):
     if _lib is None:
         from hypelcnn_amd import backend
         _lib = backend.load_library()
-        _lib.hypel_crc32c.restype = ctypes.c_uint32
-        _lib.hypel_crc32c.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64]
     data = bytes(data)
     return int(_lib.hypel_crc32c(crc, data, len(data)))
 

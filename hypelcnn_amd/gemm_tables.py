@@ -3,9 +3,10 @@ the `Launch` record the planner emits and `GemmTables`, the builder of a launch'
 records) arrays incl. the XCD-aware tile order, segment pairing and the algorithmic-byte count of a launch."""
 import numpy as np
 
-from .backend import GEMM_BM, GROUP_DTYPE, SEG_DTYPE, TILE_DTYPE
+from . import abi
+from .backend import GEMM_BM, GROUP_DTYPE, SEG_DTYPE, TILE_DTYPE, arg_index
 
-SEG_PAIR_FLAG = 0x40000000  # include/hypel.h: HYPEL_SEG_PAIR_FLAG
+SEG_PAIR_FLAG = abi.const("HYPEL_SEG_PAIR_FLAG")
 
 
 class Launch:
@@ -19,6 +20,11 @@ class Launch:
         self.tag = tag
         self.kparts = 1  # channel parts the reduction dimension of a level forward was cut into (diagnostic)
         self.meta = {}  # diagnostics (e.g. the products a merged filter-gradient launch contains)
+
+    def set(self, param, value):
+        """Replace the argument that include/hypel.h calls `param` in this launch's prototype."""
+        i = arg_index(self.name, param)
+        self.args = tuple(self.args[:i]) + (value,) + tuple(self.args[i + 1:])
 
 
 class GemmTables:

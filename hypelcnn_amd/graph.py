@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 
+from . import abi
+
 ACT_CODES = {None: 0, "lrelu": 1, "relu": 2, "sigmoid": 3, "tanh": 4}
 
 
@@ -618,11 +620,11 @@ def local_response_normalization(inputs, depth_radius=5, bias=1.0, alpha=1.0, be
     return node.out
 
 
-CAPSULE_MAX_WIDTH = 32  # hypel.h HYPEL_CAPS_MAX_D: capsule width the routing kernels keep in registers
-CAPSULE_MAX_COLS = 512  # ... HYPEL_CAPS_MAX_JD: classes x width
-CAPSULE_MAX_BATCH = 65535  # ... the sample index is the grid's y dimension in the routing sums
-CAPSULE_LDS_BYTES = 64 * 1024  # ... dynamic LDS a block of the two u_hat products may ask for
-CAPSULE_TILE = 16  # ... samples per staged tile of the two u_hat products
+CAPSULE_MAX_WIDTH = abi.const("HYPEL_CAPS_MAX_D")  # capsule width the routing kernels keep in registers
+CAPSULE_MAX_COLS = abi.const("HYPEL_CAPS_MAX_JD")  # classes x width
+CAPSULE_MAX_BATCH = abi.const("HYPEL_CAPS_MAX_N")  # the sample index is the grid's y dimension in the routing sums
+CAPSULE_LDS_BYTES = abi.const("HYPEL_CAPS_MAX_LDS")  # dynamic LDS a block of the two u_hat products may ask for
+CAPSULE_TILE = 16  # samples per staged tile of the two u_hat products (csrc/capsule.hip)
 
 
 def capsule_lds_bytes(classes, width, iterations):

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from . import graph as G
+from . import abi, graph as G
 from .backend import COPY_BLOCK_DTYPE, GEMM_BM, MTILE_DTYPE, REDUCE_ENTRY_DTYPE, SEG_DTYPE, Ref
 from .gemm_tables import SEG_PAIR_FLAG, GemmTables, Launch  # noqa: F401 (re-exported: tests and tools build tables through plan)
 
@@ -78,7 +78,7 @@ class Storage:
         return self.npix * self.nb
 
 
-MSE_PARTIALS = 1024  # include/hypel.h HYPEL_MSE_PARTIALS
+MSE_PARTIALS = abi.const("HYPEL_MSE_PARTIALS")
 DP_SYNC_WORK = 0.5  # share of the filter-gradient work before the sync point
 # Gradient buckets of the data-parallel exchange: two by default (one sync point: >= 60 % of the bytes leave under the
 # second half of the backward pass).  More buckets are available for large models -- one sync point per DP_BUCKET_BYTES
@@ -91,15 +91,15 @@ DP_BUCKET_BYTES = int(float(os.environ.get("HYPEL_DP_BUCKET_MB", "256")) * (1 <<
 DP_MAX_BUCKETS = 8
 HINT_OVERRIDE = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("HYPEL_HINT_OVERRIDE", "").split(",") if kv)}
 RESIDENT_BLOCKS_64 = 6 * 256  # 128x64 (and multi-segment 128x32) blocks the device holds at once
-GEMM_SINGLE_SEG = 0x800  # include/hypel.h HYPEL_GEMM_SINGLE_SEG
-GEMM_PAIRED_SEGS = 0x400    # ... HYPEL_GEMM_PAIRED_SEGS (bit of `accumulate`)
+GEMM_SINGLE_SEG = abi.const("HYPEL_GEMM_SINGLE_SEG")
+GEMM_PAIRED_SEGS = abi.const("HYPEL_GEMM_PAIRED_SEGS")  # (bit of `accumulate`)
 GEMM_BK = 32  # reduction columns per k-tile of the kernel
 # fp32 products on the bf16 matrix cores with three-way split operands and six partial products (include/hypel.h
 # HYPEL_GEMM_SPLIT6): "0" = never, "6" = wherever the launch is eligible and large enough (widths by column count),
 # "6:W" = the same with the tile width forced to hint W (1 = 128x32, 2 = 128x64, 3 = 128x128; per-launch A/B).
 # HYPEL_SPLIT_OVERRIDE="fwd:conv_dec_0=3,dgrad:conv_dec_0=0": per launch tag, 0 = fp32 MFMA kernel.
-GEMM_SPLIT6 = 0x8000        # include/hypel.h HYPEL_GEMM_SPLIT6 (bit of `accumulate`)
-GEMM_MULTI_SPLIT6 = 0x100   # ... HYPEL_GEMM_MULTI_SPLIT6 (bit of hypel_seg_gemm_multi_f32's tile_width)
+GEMM_SPLIT6 = abi.const("HYPEL_GEMM_SPLIT6")  # (bit of `accumulate`)
+GEMM_MULTI_SPLIT6 = abi.const("HYPEL_GEMM_MULTI_SPLIT6")  # (bit of hypel_seg_gemm_multi_f32's tile_width)
 _gs = os.environ.get("HYPEL_GEMM_SPLIT", "6").split(":")
 GEMM_SPLIT = int(_gs[0] or 0)
 GEMM_SPLIT_WIDTH = int(_gs[1]) if len(_gs) > 1 else 0
@@ -128,8 +128,8 @@ KSLICE_FRAC_MIN = 0.7    # smallest threshold (fraction of the launch's heaviest
 #                          partial traffic; the simulation, which knows nothing of two blocks sharing a CU, prefers 0.25
 KSLICE_REDUCE_COST_K = 55  # the reduce launch behind a sliced launch (~6 us), in reduction columns of a 128 x 128 block
 KSLICE_SLOTS = {1: 768, 2: 512, 3: 512}  # resident blocks of the split kernels by tile-width hint (3 / 2 / 2 per CU)
-GEMM_MFMA16X4 = 0x2000  # include/hypel.h HYPEL_GEMM_MFMA16X4: 128x64 blocks on the 16x16x4 MFMA (merged level, <= 16 filters)
-GEMM_VAR_N = 0x4000     # ... HYPEL_GEMM_VAR_N: tile records carry their group's column count
+GEMM_MFMA16X4 = abi.const("HYPEL_GEMM_MFMA16X4")  # 128x64 blocks on the 16x16x4 MFMA (merged level, <= 16 filters)
+GEMM_VAR_N = abi.const("HYPEL_GEMM_VAR_N")  # tile records carry their group's column count
 # Merged multi-kernel levels (include/hypel.h): the nested branches of a level share one packed weight image
 # W_pack[offset][Cin][C]; per output pixel and ring of input offsets ONE product on the column range of the branches
 # that contain the ring.  HYPEL_MERGE_LEVELS: comma list of the passes that use it -- "fwd", "dgrad", "wgrad"; default all
@@ -567,10 +567,10 @@ class TowerPlan:
             pos = len(lst)
             self._emit_gemm(lst, stab, n, a_ref, lda, ta, b_ref, ldb, tb, c_ref, ldc, None, 0, tag + "/splitk",
                             allow_split=False)
-            self._scratch(lst[pos], 6, "scratch_wgrad", S * count)
+            self._scratch(lst[pos], "c", "scratch_wgrad", S * count)
             l2 = Launch("reduce_splits_f32", (None, count, S, c_ref + c_min, count, int(accumulate), bias_ref, int(n), 0),
                         nbytes=4 * count * (S + 1), tag="splitk-reduce")
-            self._scratch(l2, 0, "scratch_wgrad", S * count)
+            self._scratch(l2, "partial", "scratch_wgrad", S * count)
             lst.append(l2)
             return
         pair = bool(pair and not ta and tb and n > 16 and stats is None)
@@ -615,7 +615,7 @@ class TowerPlan:
             args = args + (None,)
         l = Launch(name, args, flops=2 * macs, nbytes=tables.compulsory_bytes(n, lda, ta, ldb, tb), tag=tag)
         if stats is not None:
-            self._scratch(l, len(args) - 1, "scratch_partial", stats)
+            self._scratch(l, "stats_partial", "scratch_partial", stats)
         lst.append(l)
         if reduce_after is not None:
             l.meta["kslices"] = reduce_after.meta["kslices"]
@@ -790,14 +790,13 @@ class TowerPlan:
         launches' scratch arguments."""
         for name, size in self.scratch_sizes.items():
             self._alloc(name, size)
-        for launch, pos, name in self._pending_scratch:
-            args = list(launch.args)
-            args[pos] = self._ref(name)
-            launch.args = tuple(args)
+        for launch, param, name in self._pending_scratch:
+            launch.set(param, self._ref(name))
 
-    def _scratch(self, launch, pos, name, size=0):
+    def _scratch(self, launch, param, name, size=0):
+        """The launch's argument `param` (the header's parameter name) is the shared scratch region `name`."""
         self.scratch_sizes[name] = max(self.scratch_sizes.get(name, 1), int(size))
-        self._pending_scratch.append((launch, pos, name))
+        self._pending_scratch.append((launch, param, name))
 
     # ------------------------------------------------------------------ LinearNode forward
     def _vec_params(self, node):
@@ -1133,7 +1132,7 @@ class TowerPlan:
                 n_chunks = (rows + chunk - 1) // chunk
                 l1 = Launch("col_stats_partial", (self._ref(ybuf), c, rows, c, chunk, None),
                             nbytes=4 * rows * c, tag="bn-stats")
-                self._scratch(l1, 5, "scratch_partial", n_chunks * 2 * c)
+                self._scratch(l1, "partial", "scratch_partial", n_chunks * 2 * c)
                 self.fwd.append(l1)
                 self._emit_bn_finalize(idx, node, aux, n_chunks, chunk, rows, c)
                 aux["mean"] = self._ref(f"mean:{idx}")
@@ -1177,18 +1176,18 @@ class TowerPlan:
         tail = (float(node.bn_eps), mean_ref, rstd_ref, self._s(aux["mm"]), self._s(aux["mv"]), self._bn_decay(node))
         if not self.sync_bn:
             l2 = Launch("bn_finalize", (None, n_chunks, chunk, rows, c) + tail, tag="bn-finalize")
-            self._scratch(l2, 0, "scratch_partial", n_chunks * 2 * c)
+            self._scratch(l2, "partial", "scratch_partial", n_chunks * 2 * c)
             self.fwd.append(l2)
             return
         rec = 2 * c + 1
         l2 = Launch("bn_merge_partials", (None, n_chunks, chunk, rows, c, None), tag="bn-sync-merge")
-        self._scratch(l2, 0, "scratch_partial", n_chunks * 2 * c)
-        self._scratch(l2, 5, "sbn_local", rec)
+        self._scratch(l2, "partial", "scratch_partial", n_chunks * 2 * c)
+        self._scratch(l2, "out", "sbn_local", rec)
         l3 = Launch("_allgather", (None, rec, None), tag="bn-sync-gather")
-        self._scratch(l3, 0, "sbn_local", rec)
-        self._scratch(l3, 2, "sbn_all", self.world * rec)
+        self._scratch(l3, "src", "sbn_local", rec)
+        self._scratch(l3, "dst", "sbn_all", self.world * rec)
         l4 = Launch("bn_finalize_ranks", (None, self.world, c) + tail, tag="bn-finalize")
-        self._scratch(l4, 0, "sbn_all", self.world * rec)
+        self._scratch(l4, "gathered", "sbn_all", self.world * rec)
         self.fwd += [l2, l3, l4]
 
     @staticmethod
@@ -1458,11 +1457,11 @@ class TowerPlan:
                         self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, w_ref, w_ld or cout, 1,
                                         self._ref(gst.buf), gst.ld, None, 0,
                                         f"dgrad:{items[0][0].scope}/split{mtag}")
-                        self._scratch(self.bwd[pos], 6, "scratch_dgrad", S * copy)
+                        self._scratch(self.bwd[pos], "c", "scratch_dgrad", S * copy)
                         l2 = Launch("reduce_splits_f32", (None, copy, S, self._ref(gst.buf), h * w * nb * src.c,
                                                           acc, None, src.c, gst.ld),
                                     nbytes=4 * h * w * nb * src.c * (S + 1), tag="dgrad-split-reduce")
-                        self._scratch(l2, 0, "scratch_dgrad", S * copy)
+                        self._scratch(l2, "partial", "scratch_dgrad", S * copy)
                         self.bwd.append(l2)
                         acc = 1
                         continue
@@ -1542,7 +1541,7 @@ class TowerPlan:
                             nbytes=12 * rows * c, tag="post-bwd-reduce+apply")
                 if dparam is None:
                     # the phase does not train this layer: only dY is wanted, the chunk sums have no reader
-                    self._scratch(l1, 11, "scratch_partial", n_chunks * 2 * c)
+                    self._scratch(l1, "partial", "scratch_partial", n_chunks * 2 * c)
                     self.bwd.append(l1)
                     return
                 if self._defer_bias_sums:
@@ -1552,25 +1551,23 @@ class TowerPlan:
                     self._bias_sum_bufs += 1
                     name = f"bias_sums:{k}"
                     self._alloc(name, n_chunks * 2 * c)
-                    args = list(l1.args)
-                    args[11] = self._ref(name)
-                    l1.args = tuple(args)
+                    l1.set("partial", self._ref(name))
                     self.bwd.append(l1)
                     self._bias_sum_entries.append((self._ref(name), dparam, 2 * c, c, n_chunks, pacc))
                     return
-                self._scratch(l1, 11, "scratch_partial", n_chunks * 2 * c)
+                self._scratch(l1, "partial", "scratch_partial", n_chunks * 2 * c)
                 l2 = Launch("bwd_reduce_finalize", (None, n_chunks, c, None, dparam, pacc), tag="post-bwd-finalize")
-                self._scratch(l2, 0, "scratch_partial", n_chunks * 2 * c)
-                self._scratch(l2, 3, "sums", 2 * c)
+                self._scratch(l2, "partial", "scratch_partial", n_chunks * 2 * c)
+                self._scratch(l2, "sums", "sums", 2 * c)
                 self.bwd += [l1, l2]
                 return
             else:
                 l1 = Launch("bn_act_bwd_reduce", (dz, c, y_ref, c, rows, c, mean, rstd, beta, code, alpha, mask, c,
                                                   chunk, None), nbytes=8 * rows * c, tag="post-bwd-reduce")
-                self._scratch(l1, 14, "scratch_partial", n_chunks * 2 * c)
+                self._scratch(l1, "partial", "scratch_partial", n_chunks * 2 * c)
                 l2 = Launch("bwd_reduce_finalize", (None, n_chunks, c, None, dparam, pacc), tag="post-bwd-finalize")
-                self._scratch(l2, 0, "scratch_partial", n_chunks * 2 * c)
-                self._scratch(l2, 3, "sums", 2 * c)
+                self._scratch(l2, "partial", "scratch_partial", n_chunks * 2 * c)
+                self._scratch(l2, "sums", "sums", 2 * c)
                 self.bwd += [l1, l2]
             sums = "pending"
         sync = self.sync_bn and has_bn and node.training and sums is not None
@@ -1578,7 +1575,7 @@ class TowerPlan:
             # sum(dyh), sum(dyh * xhat) over the GLOBAL batch (the parameter gradient above stays the local sum: it
             # travels in the flat gradient all-reduce)
             lc = Launch("_allreduce", (None, 2 * c), tag="bn-sync-reduce")
-            self._scratch(lc, 0, "sums", 2 * c)
+            self._scratch(lc, "ref", "sums", 2 * c)
             self.bwd.append(lc)
         if dy is not None and (has_bn or code != 0 or mask is not None):
             if sync:
@@ -1590,7 +1587,7 @@ class TowerPlan:
                 l3 = Launch("bn_act_bwd_apply", (dz, c, y_ref, c, rows, c, mean, rstd, beta, code, alpha, mask, c, None,
                                                  dy, c), nbytes=12 * rows * c, tag="post-bwd-apply")
             if sums is not None:
-                self._scratch(l3, 13, "sums", 2 * c)
+                self._scratch(l3, "sums", "sums", 2 * c)
             self.bwd.append(l3)
 
     def _wgrad_splits(self, base_blocks, n_pairs):
@@ -1654,10 +1651,10 @@ class TowerPlan:
         self._emit_gemm(self.bwd, tb, n, a_ref, lda, 1, b_ref, ldb, 0, Ref(self.sess.grads), n, None, 0, tag,
                         allow_split=False)
         l = self.bwd[launch_pos]
-        self._scratch(l, 6, "scratch_wgrad", S * slab)
+        self._scratch(l, "c", "scratch_wgrad", S * slab)
         l2 = Launch("reduce_splits_f32", (None, slab, S, Ref(self.sess.grads, w0_offset), slab, acc, None, 0, 0),
                     nbytes=4 * slab * (S + 1), tag="wgrad-reduce")
-        self._scratch(l2, 0, "scratch_wgrad", S * slab)
+        self._scratch(l2, "partial", "scratch_wgrad", S * slab)
         self.bwd.append(l2)
 
     def _flush_wgrads(self):

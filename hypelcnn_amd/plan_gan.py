@@ -48,7 +48,7 @@ class PhasePlan(TowerPlan):
         self._term_batch = []  # deferred loss terms of the next loss_terms_slots launch
         self._term_list = None  # the launch list that batch goes to
         self._n_loss_slots = 0  # loss slots handed out so far
-        self._slot_launches = []  # (launch, argument index) that take the slot buffer (_finish_loss_slots)
+        self._slot_launches = []  # (launch, parameter name) that take the slot buffer (_finish_loss_slots)
         self._loss_written = False  # a term has written the op's loss value: later ones accumulate
         super().__init__(tower, nb, session, loss=None, external_masks=True, seed=seed)
 
@@ -495,14 +495,14 @@ class PhasePlan(TowerPlan):
                                        nbytes=8 * len(ents) * nb0 * c, tag="batch-scatter"))
 
     # ---- per-block gradient slabs of the fused kernels: reduced once per train op ----
-    def _defer_slab_reduce(self, launch, nodes, pos_w, pos_b, blocks, w_geom, b_geom, pos_strides=None):
-        """The backward kernel `launch` leaves `blocks` filter / bias gradient slabs (arguments pos_w / pos_b; geometry
+    def _defer_slab_reduce(self, launch, nodes, blocks, w_geom, b_geom):
+        """The backward kernel `launch` leaves `blocks` filter / bias gradient slabs (arguments `pw` / `pb`; geometry
         (stride, count) per slab) for each of its variable sets -- `nodes`: one application node per set, two for the
         *_apps form.  Instead of one reduction launch per application, every application of one weight set appends its
         slabs to that set's region and ONE hypel_reduce_splits_wave_multi_f32 at the end of the backward pass sums each
         region (one entry per weight set and kind: two entries never write the same gradient).  An *_apps launch reaches
-        its second set's first slab by a stride from the first set's (arguments pos_strides), known once the regions are
-        laid out."""
+        its second set's first slab by a stride from the first set's (arguments `pw_stride` / `pb_stride`), known once
+        the regions are laid out."""
         where = []
         for nd in nodes:
             acc = self._param_acc(nd.weights[0])
@@ -512,7 +512,7 @@ class PhasePlan(TowerPlan):
                                                                      acc=acc, blocks=0))
             where.append((st, st["blocks"]))
             st["blocks"] += blocks
-        self._slab_launches.append((launch, pos_w, pos_b, pos_strides, where))
+        self._slab_launches.append((launch, where))
 
     def _flush_slab_reduces(self):
         sets, self._slab_sets = self._slab_sets, {}
@@ -547,14 +547,13 @@ class PhasePlan(TowerPlan):
                 self._alloc(st[kind + "_buf"], st["blocks"] * stride)
                 ents.append((rel(self._ref(st[kind + "_buf"])), rel(self._g(var)), stride, count, st["blocks"], st["acc"]))
                 total += count
-        for launch, pos_w, pos_b, pos_strides, where in launches:
+        for launch, where in launches:
             first = [(self._ref(st["w_buf"], b0 * st["w"][0]), self._ref(st["b_buf"], b0 * st["b"][0])) for st, b0 in where]
-            args = list(launch.args)
-            args[pos_w], args[pos_b] = first[0]
-            if pos_strides is not None:  # the second variable set's first slabs, as element distances from the first set's
-                args[pos_strides[0]] = (first[1][0].ptr() - first[0][0].ptr()) // 4
-                args[pos_strides[1]] = (first[1][1].ptr() - first[0][1].ptr()) // 4
-            launch.args = tuple(args)
+            launch.set("pw", first[0][0])
+            launch.set("pb", first[0][1])
+            if len(first) > 1:  # the second variable set's first slabs, as element distances from the first set's
+                launch.set("pw_stride", (first[1][0].ptr() - first[0][0].ptr()) // 4)
+                launch.set("pb_stride", (first[1][1].ptr() - first[0][1].ptr()) // 4)
         for rnd in [ents] + later:
             e_t = self.be.upload(np.array(rnd, REDUCE_ENTRY_DTYPE))
             self.tables.append(e_t)
@@ -580,18 +579,16 @@ class PhasePlan(TowerPlan):
         z_st = self.storage[id(node.out)]
         return (self._ref(s_st.buf, s_st.ch_off), s_st.ld), (self._ref("g:" + z_st.buf), z_st.ld), self._grad_ref(node.src)
 
-    def _stack_slabs(self, launch, node, pos_w, blocks, w_geom, b_geom, scratch):
-        """Where the backward launch of a fused stack leaves its per-block filter / bias gradient slabs (arguments pos_w,
-        pos_w + 1): the regions that the train op's slab reduction sums, or shared scratch when the phase does not train
+    def _stack_slabs(self, launch, node, blocks, w_geom, b_geom, scratch):
+        """Where the backward launch of a fused stack leaves its per-block filter / bias gradient slabs (arguments `pw`,
+        `pb`): the regions that the train op's slab reduction sums, or shared scratch when the phase does not train
         these weights."""
-        apps = getattr(node, "app_nodes", None)
+        apps = getattr(node, "app_nodes", None) or [node]
         if self._trains(node.weights):
-            n_apps = len(apps) if apps is not None else 1
-            self._defer_slab_reduce(launch, apps or [node], pos_w, pos_w + 1, blocks // n_apps, w_geom, b_geom,
-                                    (8, 9) if apps is not None else None)  # (hypel.h: slab strides of both *_bwd_apps)
+            self._defer_slab_reduce(launch, apps, blocks // len(apps), w_geom, b_geom)
         else:
-            self._scratch(launch, pos_w, f"scratch_{scratch}_w", blocks * w_geom[0])
-            self._scratch(launch, pos_w + 1, f"scratch_{scratch}_b", blocks * b_geom[0])
+            self._scratch(launch, "pw", f"scratch_{scratch}_w", blocks * w_geom[0])
+            self._scratch(launch, "pb", f"scratch_{scratch}_b", blocks * b_geom[0])
 
     # ---- fused generator ----
     def _gen_refs(self, node):
@@ -638,17 +635,15 @@ class PhasePlan(TowerPlan):
             self._alloc(f"gkeep:{idx}", keep_n)
             kref = self._ref(f"gkeep:{idx}")
             f = self._gen_fwd[idx]
-            if f.name in ("gan_generator_fwd_tap", "gan_generator_fwd_apps"):
-                f.args = tuple(f.args[:-1]) + (kref,)
-            else:
-                f.name, f.args = "gan_generator_fwd_keep", tuple(f.args) + (kref,)
+            if f.name == "gan_generator_fwd":  # (its activation-keeping form has the parameter the other two always have)
+                f.name, f.args = "gan_generator_fwd_keep", tuple(f.args) + (None,)
+            f.set("keep", kref)
             f.bytes += 4 * keep_n
         if apps is not None:
             w1, b1, _ = self._gen_refs(apps[1])
             l1 = Launch("gan_generator_bwd_apps", (*x, *dy, self.nb // n_apps, n_apps, self._rel(w0, w1), self._rel(b0, b1), 0,
                                                    0, src.c, self._p(w0), self._p(b0), int(node.only_encoder), *dx, None, None,
                                                    kref), nbytes=12 * self.nb * src.c + 4 * keep_n, tag="gen-bwd-apps")
-            pos_w = 17
         elif tap is not None and self.grad_written.get(id(tap), False):
             # one backward pass for the full application and the encoder-only one read from it: the gradient that reached
             # the encoder output joins dn_4
@@ -656,16 +651,13 @@ class PhasePlan(TowerPlan):
             l1 = Launch("gan_generator_bwd_tap", (*x, *dy, self._ref("g:" + t_st.buf, t_st.ch_off), t_st.ld, self.nb, src.c,
                                                   self._p(w0), self._p(b0), *dx, None, None, kref),
                         nbytes=16 * self.nb * src.c + 4 * keep_n, tag="gen-bwd+enc")
-            pos_w = 13
         else:
-            l1 = Launch("gan_generator_bwd", (*x, *dy, self.nb, src.c, self._p(w0), self._p(b0), int(node.only_encoder),
-                                              *dx, None, None), nbytes=12 * self.nb * src.c, tag="gen-bwd")
-            if kref is not None:
-                l1.name, l1.args = "gan_generator_bwd_kept", tuple(l1.args) + (kref,)
-                l1.bytes += 4 * keep_n
-            pos_w = 12
+            kept = kref is not None
+            l1 = Launch("gan_generator_bwd_kept" if kept else "gan_generator_bwd",
+                        (*x, *dy, self.nb, src.c, self._p(w0), self._p(b0), int(node.only_encoder), *dx, None, None)
+                        + ((kref,) if kept else ()), nbytes=12 * self.nb * src.c + 4 * keep_n, tag="gen-bwd")
         self.bwd.append(l1)
-        self._stack_slabs(l1, node, pos_w, blocks, (wtotal, wtotal), (8, 7), "gen")
+        self._stack_slabs(l1, node, blocks, (wtotal, wtotal), (8, 7), "gen")
 
     # ---- fused fully-connected stack (narrow discriminators) ----
     def _densestack_args(self, node):
@@ -712,7 +704,7 @@ class PhasePlan(TowerPlan):
                                             None, None), tag="dense-stack-bwd")
         l1.flops, l1.bytes = 6 * self.nb * wtotal, 4 * self.nb * (2 * src.c + out.c)
         self.bwd.append(l1)
-        self._stack_slabs(l1, node, len(l1.args) - 2, blocks, (wtotal, wtotal), (btotal, btotal), "ds")
+        self._stack_slabs(l1, node, blocks, (wtotal, wtotal), (btotal, btotal), "ds")
 
     # ---- feature stack (global l2 normalise per slice, stacked) ----
     def _fwd_featstack(self, idx, node):
@@ -798,7 +790,7 @@ class PhasePlan(TowerPlan):
             l = Launch("nce_loss", (a_ref, a_st.ld, self._ref(b_st.buf, b_st.ch_off), b_st.ld, nb, int(term.parts),
                                     int(term.embed), float(term.tau), float(term.weight), self._ref("loss"), acc_loss,
                                     da, ldda, acc_a, db, lddb, acc_b, None), tag="loss-nce")
-            self._scratch(l, 17, "scratch_nce", nb + 1024)
+            self._scratch(l, "ws", "scratch_nce", nb + 1024)
             self.fwd.append(l)
             return
         mode = {"mean_sq": 0, "mean_abs": 1, "mean": 2}[term.kind]
@@ -857,12 +849,12 @@ class PhasePlan(TowerPlan):
         e_t = self.be.upload(arr)
         self.tables.append(e_t)
         l = Launch("loss_terms_slots", (Ref(self.sess.params), Ref(e_t), len(batch), None), tag=f"loss-terms/{len(batch)}")
-        self._loss_slot(l, 3)
+        self._loss_slot(l, "slots")
         self._term_list.append(l)
 
-    def _loss_slot(self, launch, pos):
+    def _loss_slot(self, launch, param):
         """Give a deferred loss term the next 1024-float slot of the op's slot buffer (allocated in _finish_loss_slots)."""
-        self._slot_launches.append((launch, pos))
+        self._slot_launches.append((launch, param))
 
     def _finish_loss_slots(self):
         self._flush_loss_terms()
@@ -871,10 +863,8 @@ class PhasePlan(TowerPlan):
         if not pend or not n_slots:
             return
         self._alloc("loss_slots", 1024 * n_slots)
-        for launch, pos in pend:
-            args = list(launch.args)
-            args[pos] = self._ref("loss_slots")
-            launch.args = tuple(args)
+        for launch, param in pend:
+            launch.set(param, self._ref("loss_slots"))
         self.bwd.append(Launch("loss_finalize_slots", (self._ref("loss_slots"), n_slots, self._ref("loss"),
                                                        1 if self._loss_written else 0),
                                tag="loss-finalize"))

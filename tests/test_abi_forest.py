@@ -1,5 +1,5 @@
-"""CPU: the random-forest entry points are declared in include/hypel.h, exported by the library, bound in
-backend.SIGNATURES with the stream as the last header parameter, and refuse null pointers, zero or negative sizes,
+"""CPU: the random-forest entry points are declared in include/hypel.h, exported by the library (their binding:
+tests/test_abi.py, which checks every prototype of the header), and refuse null pointers, zero or negative sizes,
 n_classes above the LDS cap and max_features > F with a message before anything is launched.  The ABI version is still
 8: new symbols only."""
 import ctypes
@@ -19,13 +19,6 @@ def test_version_8_new_symbols_and_constants(lib):  # noqa: F811
     decl = _declared()
     for name in NEW:
         assert name in decl and hasattr(lib, name)
-        assert decl[name] == len(backend.SIGNATURES[name[len("hypel_"):]]) + 1
-        proto = re.search(name + r"\s*\(([^;]*?)\)\s*;", src, flags=re.S).group(1)
-        assert proto.split(",")[-1].split() == ["hypel_stream_t", "stream"]
-        # pointer parameters are bound as pointers, sizes as the header's integer width
-        kinds = [backend._P if "*" in a else {"int64_t": backend._I64, "int32_t": backend._I32}[a.split()[0]]
-                 for a in proto.split(",")[:-1]]
-        assert kinds == backend.SIGNATURES[name[len("hypel_"):]], name
     define = lambda k: int(re.search(r"#define\s+HYPEL_FOREST_" + k + r"\s+(\d+)", src).group(1))  # noqa: E731
     assert backend.FOREST_NODE_DTYPE.itemsize == 16 and backend.FOREST_NODE_DTYPE.fields["left"][1] == 8
     assert (define("EDGE_ROWS"), define("MAX_EDGES"), define("MAX_CLASSES"), define("MAX_DEPTH")) == \

@@ -1,5 +1,5 @@
-"""CPU: ABI 8 -- the grid-search entry points are declared, exported and bound, and hypel_svm_job_t's numpy dtype has
-the header's layout (a hypel_svm_pair_t, then k_off and c)."""
+"""CPU: ABI 8 -- the grid-search entry points are declared and exported (their binding: tests/test_abi.py), and
+hypel_svm_job_t's numpy dtype has the header's layout (a hypel_svm_pair_t, then k_off and c)."""
 import re
 
 from tests.test_abi import HEADER, _declared, lib  # noqa: F401 -- `lib` is the module fixture of tests/test_abi.py
@@ -14,7 +14,6 @@ def test_version_8_and_new_symbols(lib):  # noqa: F811
     decl = _declared()
     for name in NEW:
         assert name in decl and hasattr(lib, name)
-        assert decl[name] == len(backend.SIGNATURES[name[len("hypel_"):]]) + 1
 
 
 def test_job_record_layout():
