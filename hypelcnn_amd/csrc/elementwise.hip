@@ -11,7 +11,6 @@
 namespace {
 
 constexpr int STAT_TX = 64;  // threads along channels
-constexpr int STAT_TY = 4;   // row lanes
 
 // Elementwise kernels map a 256-thread block onto [TY rows x TX column-vectors] (TX = power of two >= the
 // number of column vectors, capped at 256), so (row, col) needs no division, consecutive lanes touch
@@ -31,6 +30,11 @@ static inline EwShape ew_shape(int64_t rows, int cvec) {
     return EwShape{l, (int)g};
 }
 static inline bool aligned16(const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; }
+// a (nullable) row operand that can be read as float4: 16-byte aligned base, leading dimension a multiple of 4
+static inline bool rows_v4(const void* p, int64_t ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); }
+// The float4 (`v4`) or the scalar instantiation of a kernel template whose first argument is the vector width; further
+// template arguments follow the name.  Every launcher decides `v4` from its own operands and launches the result once.
+#define HYPEL_VEC_KERNEL(v4, K, ...) ((v4) ? K<4, ##__VA_ARGS__> : K<1, ##__VA_ARGS__>)
 
 template <int VEC>
 struct Vec;
@@ -56,6 +60,19 @@ struct Vec<4> {
         v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
     }
 };
+
+// body(k) for the VEC elements of a vector, in the reductions' row loops.  VEC == 1 calls the body directly: even a
+// one-trip loop inside a row loop under `#pragma unroll 4` changes how hipcc unrolls the row loop, and with it which of
+// the sums it contracts into fma (the scalar chunk statistics then round differently than with the body written out).
+template <int VEC, class F>
+__device__ __forceinline__ void vec_each(F body) {
+    if constexpr (VEC == 1) {
+        body(0);
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) body(k);
+    }
+}
 
 template <int VEC, class F>
 __device__ __forceinline__ void ew_loop(int64_t rows, int c, int tx_log2, F body) {
@@ -259,7 +276,8 @@ __global__ void reduce_splits_kernel(const float* __restrict__ partial, int64_t 
 }
 
 // Several reductions in one launch: blockIdx.y = entry, blockIdx.x strides over the entry's elements (float4 when
-// the entry's count / stride / addresses allow it).  Same summation order as reduce_splits_kernel.
+// the entry's count / stride / addresses allow it).  Here the old value comes FIRST, then the slabs in k order (the
+// flat kernels add the bias, the slabs in k order and the old value last).
 __global__ void reduce_splits_multi_kernel(const float* __restrict__ base,
                                            const hypel_reduce_entry_t* __restrict__ entries) {
     const hypel_reduce_entry_t e = entries[blockIdx.y];
@@ -292,13 +310,6 @@ __global__ void reduce_splits_multi_kernel(const float* __restrict__ base,
 }
 
 // ------------------------------------------------------------------------------------- BN statistics
-// grid = (n_chunks, ceil(c/64)); block = 64 x 4.  Shifted sums (shift = first row of the chunk) keep the
-// fp32 accumulation well conditioned; the chunk's (mean, M2) pair is then exact enough to Chan-merge in fp64.
-
-// float4 variant: block = 16 column quads x 16 row lanes.  Four times the bytes in flight per block: narrow layers
-// (c <= 128) launch only ~256-512 blocks, and at 8 KB in flight per CU the scalar kernel is latency bound.
-constexpr int STAT_V4_TY = 16;
-
 // Combine the chunk partials: mean = sum n_k mean_k / N, M2 = sum (M2_k + n_k (mean_k - mean)^2), both as fp64
 // sums with a FIXED association (16 strided lanes per channel, then an xor tree) -> deterministic, and ~20x
 // shorter than a serial Chan chain over ~200 chunks.  block = 16 channels x 16 lanes.
@@ -431,82 +442,59 @@ __global__ void bn_finalize_ranks_kernel(const float* __restrict__ gathered, int
     }
 }
 
+// Chunk statistics and the backward column sums share one block shape: grid = (n_chunks, ceil(c / 64)), a block covers
+// 64 columns of one chunk of rows with STAT_TX / VEC column lanes x 256 / (STAT_TX / VEC) row lanes -- 64 x 4 scalar,
+// 16 quads x 16 as float4.  The float4 form has four times the bytes in flight per block: narrow layers (c <= 128)
+// launch only ~256-512 blocks, and at 8 KB in flight per CU the scalar form is latency bound.  A thread takes its rows
+// in steps of TY; thread t < 64 then adds the TY lane sums of column t from LDS in lane order (tests/bn_ref.py bounds
+// the error of exactly this order, for 4 and for 16 lanes).
+//
+// Statistics: shifted sums (shift = first row of the chunk) keep the fp32 accumulation well conditioned; the chunk's
+// (mean, M2) pair is then exact enough to Chan-merge in fp64.
+template <int VEC>
 __global__ __launch_bounds__(256) void col_stats_partial_kernel(const float* __restrict__ x, int64_t ld, int64_t rows,
                                                                  int c, int chunk_rows, float* __restrict__ partial) {
-    __shared__ float sh[2][STAT_TY][STAT_TX];
-    const int tx = threadIdx.x & (STAT_TX - 1), ty = threadIdx.x / STAT_TX;
-    const int col = blockIdx.y * STAT_TX + tx;
+    constexpr int TX = STAT_TX / VEC, TY = 256 / TX;
+    __shared__ float sh[2][TY][STAT_TX];
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    const int col = blockIdx.y * STAT_TX + tx * VEC;
     const int64_t r0 = (int64_t)blockIdx.x * chunk_rows;
     const int64_t r1 = min(rows, r0 + (int64_t)chunk_rows);
-    float s = 0.0f, ss = 0.0f, shift = 0.0f;
-    if (col < c) {
-        shift = x[r0 * ld + col];
+    Vec<VEC> s = {}, ss = {}, shift = {};
+    if (col < c) {  // c % VEC == 0: a vector is entirely inside or outside
+        shift.load(x + r0 * ld + col);
 #pragma unroll 4
-        for (int64_t r = r0 + ty; r < r1; r += STAT_TY) {
-            const float d = x[r * ld + col] - shift;
-            s += d;
-            ss += d * d;
+        for (int64_t r = r0 + ty; r < r1; r += TY) {
+            Vec<VEC> v;
+            v.load(x + r * ld + col);
+            vec_each<VEC>([&](int k) {
+                const float d = v.v[k] - shift.v[k];
+                s.v[k] += d;
+                ss.v[k] += d * d;
+            });
         }
     }
-    sh[0][ty][tx] = s;
-    sh[1][ty][tx] = ss;
+    s.store(&sh[0][ty][tx * VEC]);
+    ss.store(&sh[1][ty][tx * VEC]);
     __syncthreads();
-    if (ty == 0 && col < c) {
+    const int cc = blockIdx.y * STAT_TX + threadIdx.x;
+    if (threadIdx.x < STAT_TX && cc < c) {
         float ts = 0.0f, tss = 0.0f;
 #pragma unroll
-        for (int k = 0; k < STAT_TY; ++k) {
-            ts += sh[0][k][tx];
-            tss += sh[1][k][tx];
+        for (int k = 0; k < TY; ++k) {
+            ts += sh[0][k][threadIdx.x];
+            tss += sh[1][k][threadIdx.x];
         }
         const float cnt = (float)(r1 - r0);
         const float mean_d = ts / cnt;
         float m2 = tss - ts * mean_d;
         if (m2 < 0.0f) m2 = 0.0f;
+        float shift_cc;  // the scalar form holds its column's shift; a quad lane reads the one of column cc again
+        if constexpr (VEC == 1) shift_cc = shift.v[0];
+        else shift_cc = x[r0 * ld + cc];
         float* po = partial + (int64_t)blockIdx.x * 2 * c;
-        po[col] = shift + mean_d;
-        po[c + col] = m2;
-    }
-}
-
-__global__ __launch_bounds__(256) void col_stats_partial_v4_kernel(const float* __restrict__ x, int64_t ld,
-                                                                    int64_t rows, int c, int chunk_rows,
-                                                                    float* __restrict__ partial) {
-    __shared__ float sh[2][STAT_V4_TY][STAT_TX];
-    const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int col = blockIdx.y * STAT_TX + tq * 4;
-    const int64_t r0 = (int64_t)blockIdx.x * chunk_rows;
-    const int64_t r1 = min(rows, r0 + (int64_t)chunk_rows);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), ss = s, shift = s;
-    if (col < c) {  // c % 4 == 0: a quad is entirely inside or outside
-        shift = *reinterpret_cast<const float4*>(x + r0 * ld + col);
-#pragma unroll 4
-        for (int64_t r = r0 + ty; r < r1; r += STAT_V4_TY) {
-            const float4 v = *reinterpret_cast<const float4*>(x + r * ld + col);
-            const float dx = v.x - shift.x, dy = v.y - shift.y, dz = v.z - shift.z, dw = v.w - shift.w;
-            s.x += dx; s.y += dy; s.z += dz; s.w += dw;
-            ss.x += dx * dx; ss.y += dy * dy; ss.z += dz * dz; ss.w += dw * dw;
-        }
-    }
-    *reinterpret_cast<float4*>(&sh[0][ty][tq * 4]) = s;
-    *reinterpret_cast<float4*>(&sh[1][ty][tq * 4]) = ss;
-    __syncthreads();
-    if (threadIdx.x < STAT_TX) {
-        const int tx = threadIdx.x, cc = blockIdx.y * STAT_TX + tx;
-        if (cc < c) {
-            float ts = 0.0f, tss = 0.0f;
-#pragma unroll
-            for (int k = 0; k < STAT_V4_TY; ++k) {
-                ts += sh[0][k][tx];
-                tss += sh[1][k][tx];
-            }
-            const float cnt = (float)(r1 - r0);
-            const float mean_d = ts / cnt;
-            float m2 = tss - ts * mean_d;
-            if (m2 < 0.0f) m2 = 0.0f;
-            float* po = partial + (int64_t)blockIdx.x * 2 * c;
-            po[cc] = x[r0 * ld + cc] + mean_d;
-            po[c + cc] = m2;
-        }
+        po[cc] = shift_cc + mean_d;
+        po[c + cc] = m2;
     }
 }
 
@@ -566,27 +554,6 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(
     });
 }
 
-__device__ __forceinline__ void bwd_elem(const float* dz, int64_t lddz, const float* __restrict__ y,
-                                         int64_t ldy, int64_t row, int col, const float* __restrict__ mean,
-                                         const float* __restrict__ rstd, const float* __restrict__ beta, int act,
-                                         float alpha, const float* __restrict__ mask, int64_t ldm, float& dyh,
-                                         float& xhat) {
-    float v = y[row * ldy + col];
-    float pre = v;
-    if (mean) {
-        xhat = hypel_bn_xhat(v, mean[col], rstd[col]);
-        pre = hypel_bn_pre(xhat, beta[col]);
-    } else {
-        xhat = v;
-    }
-    float g = dz[row * lddz + col];
-    if (mask) g *= mask[row * ldm + col];
-    dyh = g * hypel_act_grad(pre, act, alpha);
-}
-
-
-// float4 x 16 row lanes (see col_stats_partial_v4_kernel)
-
 __device__ __forceinline__ void bwd_finalize_body(int blk16, const float* __restrict__ partial, int n_chunks, int c,
                                                   float* __restrict__ sums, float* __restrict__ dparam,
                                                   int accumulate, double* sh) {
@@ -627,112 +594,79 @@ __global__ __launch_bounds__(256) void bwd_reduce_finalize_kernel(const float* _
     bwd_finalize_body(blockIdx.x, partial, n_chunks, c, sums, dparam, accumulate, sh);
 }
 
+// Column sums of dyh = dZ * act'(pre) (* mask) and of dyh * xhat per chunk of rows, in the block shape of
+// col_stats_partial_kernel.
 // DY (layers WITHOUT batch norm only): the pass also writes dY = dZ * act'(y) (* mask) -- there the input gradient does
 // not depend on the column sums, so the reduction pass of the bias gradient delivers dY as well and the separate
 // hypel_bn_act_bwd_apply launch (one more read of dZ and Y) goes away (hypel_act_bias_bwd_reduce).
 // dy may alias dz (in-place post-op backward, include/hypel.h): neither pointer is __restrict__
-template <bool DY>
+template <int VEC, bool DY>
 __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(
     const float* dz, int64_t lddz, const float* __restrict__ y, int64_t ldy, int64_t rows, int c,
     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ beta, int act,
     float alpha, const float* __restrict__ mask, int64_t ldm, int chunk_rows, float* __restrict__ partial,
     float* dy, int64_t lddy) {
-    __shared__ float sh[2][STAT_TY][STAT_TX];
-    const int tx = threadIdx.x & (STAT_TX - 1), ty = threadIdx.x / STAT_TX;
-    const int col = blockIdx.y * STAT_TX + tx;
+    constexpr int TX = STAT_TX / VEC, TY = 256 / TX;
+    __shared__ float sh[2][TY][STAT_TX];
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    const int col = blockIdx.y * STAT_TX + tx * VEC;
     const int64_t r0 = (int64_t)blockIdx.x * chunk_rows;
     const int64_t r1 = min(rows, r0 + (int64_t)chunk_rows);
-    float s0 = 0.0f, s1 = 0.0f;
+    // The sums are plain arrays and the mask defaults to 1 in registers on purpose.  Which of these sums hipcc contracts
+    // into fma depends on such details (Vec accumulators: the float4 form rounds differently), and the float4 form
+    // without dy sits at exactly 128 VGPRs, the last count with 4 waves per SIMD (mask registers left unset: 129).
+    // After a change here compare tools/kernel_resources.py and the output bits with the build before.
+    float s0[VEC] = {}, s1[VEC] = {};
     if (col < c) {
+        Vec<VEC> mu = {}, rs = {}, be = {};
+        if (mean) {
+            mu.load_param(mean + col); rs.load_param(rstd + col); be.load_param(beta + col);
+        }
 #pragma unroll 4
-        for (int64_t r = r0 + ty; r < r1; r += STAT_TY) {
-            float dyh, xhat;
-            bwd_elem(dz, lddz, y, ldy, r, col, mean, rstd, beta, act, alpha, mask, ldm, dyh, xhat);
-            if constexpr (DY) dy[r * lddy + col] = dyh;
-            s0 += dyh;
-            s1 += dyh * xhat;
+        for (int64_t r = r0 + ty; r < r1; r += TY) {
+            Vec<VEC> yv, g, mk;
+            yv.load(y + r * ldy + col);
+            g.load(dz + r * lddz + col);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) mk.v[k] = 1.0f;
+            if (mask) mk.load(mask + r * ldm + col);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                float xhat = yv.v[k], pre = yv.v[k];
+                if (mean) {
+                    xhat = hypel_bn_xhat(yv.v[k], mu.v[k], rs.v[k]);
+                    pre = hypel_bn_pre(xhat, be.v[k]);
+                }
+                float gk = g.v[k];
+                if (mask) gk *= mk.v[k];
+                const float dyh = gk * hypel_act_grad(pre, act, alpha);
+                if constexpr (DY) g.v[k] = dyh;
+                s0[k] += dyh;
+                s1[k] += dyh * xhat;
+            }
+            if constexpr (DY) g.store(dy + r * lddy + col);
         }
     }
-    sh[0][ty][tx] = s0;
-    sh[1][ty][tx] = s1;
+    Vec<VEC> v0, v1;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        v0.v[k] = s0[k];
+        v1.v[k] = s1[k];
+    }
+    v0.store(&sh[0][ty][tx * VEC]);
+    v1.store(&sh[1][ty][tx * VEC]);
     __syncthreads();
-    if (ty == 0 && col < c) {
+    const int cc = blockIdx.y * STAT_TX + threadIdx.x;
+    if (threadIdx.x < STAT_TX && cc < c) {
         float t0 = 0.0f, t1 = 0.0f;
 #pragma unroll
-        for (int k = 0; k < STAT_TY; ++k) {
-            t0 += sh[0][k][tx];
-            t1 += sh[1][k][tx];
+        for (int k = 0; k < TY; ++k) {
+            t0 += sh[0][k][threadIdx.x];
+            t1 += sh[1][k][threadIdx.x];
         }
         float* po = partial + (int64_t)blockIdx.x * 2 * c;
-        po[col] = t0;
-        po[c + col] = t1;
-    }
-}
-
-template <bool DY>
-__global__ __launch_bounds__(256) void bn_act_bwd_reduce_v4_kernel(
-    const float* dz, int64_t lddz, const float* __restrict__ y, int64_t ldy, int64_t rows, int c,
-    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ beta, int act,
-    float alpha, const float* __restrict__ mask, int64_t ldm, int chunk_rows, float* __restrict__ partial,
-    float* dy, int64_t lddy) {
-    __shared__ float sh[2][STAT_V4_TY][STAT_TX];
-    const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int col = blockIdx.y * STAT_TX + tq * 4;
-    const int64_t r0 = (int64_t)blockIdx.x * chunk_rows;
-    const int64_t r1 = min(rows, r0 + (int64_t)chunk_rows);
-    float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
-    if (col < c) {
-        float mu[4] = {0.f, 0.f, 0.f, 0.f}, rs[4] = {1.f, 1.f, 1.f, 1.f}, be[4] = {0.f, 0.f, 0.f, 0.f};
-        if (mean) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                mu[q] = mean[col + q];
-                rs[q] = rstd[col + q];
-                be[q] = beta[col + q];
-            }
-        }
-#pragma unroll 4
-        for (int64_t r = r0 + ty; r < r1; r += STAT_V4_TY) {
-            const float4 yv4 = *reinterpret_cast<const float4*>(y + r * ldy + col);
-            const float4 gv4 = *reinterpret_cast<const float4*>(dz + r * lddz + col);
-            float4 mv4 = make_float4(1.f, 1.f, 1.f, 1.f);
-            if (mask) mv4 = *reinterpret_cast<const float4*>(mask + r * ldm + col);
-            const float yv[4] = {yv4.x, yv4.y, yv4.z, yv4.w}, gv[4] = {gv4.x, gv4.y, gv4.z, gv4.w};
-            const float mv[4] = {mv4.x, mv4.y, mv4.z, mv4.w};
-            [[maybe_unused]] float dv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float xhat = yv[q], pre = yv[q];
-                if (mean) {
-                    xhat = hypel_bn_xhat(yv[q], mu[q], rs[q]);
-                    pre = hypel_bn_pre(xhat, be[q]);
-                }
-                float g = gv[q];
-                if (mask) g *= mv[q];
-                const float dyh = g * hypel_act_grad(pre, act, alpha);
-                if constexpr (DY) dv[q] = dyh;
-                s0[q] += dyh;
-                s1[q] += dyh * xhat;
-            }
-            if constexpr (DY) *reinterpret_cast<float4*>(dy + r * lddy + col) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-        }
-    }
-    *reinterpret_cast<float4*>(&sh[0][ty][tq * 4]) = make_float4(s0[0], s0[1], s0[2], s0[3]);
-    *reinterpret_cast<float4*>(&sh[1][ty][tq * 4]) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-    __syncthreads();
-    if (threadIdx.x < STAT_TX) {
-        const int tx = threadIdx.x, cc = blockIdx.y * STAT_TX + tx;
-        if (cc < c) {
-            float t0 = 0.0f, t1 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < STAT_V4_TY; ++k) {
-                t0 += sh[0][k][tx];
-                t1 += sh[1][k][tx];
-            }
-            float* po = partial + (int64_t)blockIdx.x * 2 * c;
-            po[cc] = t0;
-            po[c + cc] = t1;
-        }
+        po[cc] = t0;
+        po[c + cc] = t1;
     }
 }
 
@@ -1326,11 +1260,6 @@ extern "C" int hypel_fill_f32(float* dst, int64_t count, float value, hypel_stre
     return 0;
 }
 
-static int red_max_blocks() {
-    constexpr int v = 8192;
-    return v;
-}
-
 extern "C" int hypel_reduce_splits_f32(const float* partial, int64_t stride, int32_t n_splits, float* out,
                                        int64_t count, int32_t accumulate, const float* bias, int32_t n,
                                        int64_t ldc, hypel_stream_t stream) {
@@ -1340,14 +1269,14 @@ extern "C" int hypel_reduce_splits_f32(const float* partial, int64_t stride, int
     if (n_splits >= 32 && count <= 65536)
         hipLaunchKernelGGL(reduce_splits_wave_kernel, dim3(hypel_grid_1d(count * 64, 256)), dim3(256), 0, ST, partial,
                            stride, n_splits, out, count, accumulate, bias, n, ldc);
-    else if ((count % 4 == 0) &&
-             (stride % 4 == 0) && aligned16(partial) && aligned16(out) &&
-             ((ldc <= 0 && (!bias || n % 4 == 0)) || (ldc > 0 && ldc % 4 == 0 && n % 4 == 0)))
-        hipLaunchKernelGGL(reduce_splits_v4_kernel, dim3(hypel_grid_1d(count / 4, 256, red_max_blocks())), dim3(256), 0, ST,
-                           partial, stride, n_splits, out, count / 4, accumulate, bias, n, ldc);
-    else
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(hypel_grid_1d(count, 256, red_max_blocks())), dim3(256), 0, ST,
-                           partial, stride, n_splits, out, count, accumulate, bias, n, ldc);
+    else {
+        // float4: slabs and output rows (of a window: ldc > 0) are whole aligned quads, and so are the bias periods
+        const bool v4 = count % 4 == 0 && rows_v4(partial, stride) && rows_v4(out, ldc > 0 ? ldc : 0) &&
+                        ((ldc <= 0 && !bias) || n % 4 == 0);
+        const int64_t count_v = v4 ? count / 4 : count;
+        hipLaunchKernelGGL(v4 ? reduce_splits_v4_kernel : reduce_splits_kernel, dim3(hypel_grid_1d(count_v, 256, 8192)),
+                           dim3(256), 0, ST, partial, stride, n_splits, out, count_v, accumulate, bias, n, ldc);
+    }
     HYPEL_CHECK_LAUNCH("hypel_reduce_splits_f32");
     return 0;
 }
@@ -1447,14 +1376,9 @@ extern "C" int hypel_reduce_splits_multi_sized_f32(const float* base, const hype
 static int launch_col_stats(const float* x, int64_t ld, int64_t rows, int32_t c, int32_t chunk_rows, float* partial,
                             hypel_stream_t stream) {
     const int n_chunks = (int)((rows + chunk_rows - 1) / chunk_rows);
-    constexpr bool v4_on = true;
-    const bool v4 = v4_on && (c % 4 == 0) && (ld % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    if (v4)
-        hipLaunchKernelGGL(col_stats_partial_v4_kernel, dim3(n_chunks, (c + STAT_TX - 1) / STAT_TX), dim3(256), 0, ST,
-                           x, ld, rows, c, chunk_rows, partial);
-    else
-        hipLaunchKernelGGL(col_stats_partial_kernel, dim3(n_chunks, (c + STAT_TX - 1) / STAT_TX), dim3(256), 0, ST, x,
-                           ld, rows, c, chunk_rows, partial);
+    const bool v4 = c % 4 == 0 && rows_v4(x, ld);
+    hipLaunchKernelGGL(HYPEL_VEC_KERNEL(v4, col_stats_partial_kernel), dim3(n_chunks, (c + STAT_TX - 1) / STAT_TX), dim3(256),
+                       0, ST, x, ld, rows, c, chunk_rows, partial);
     return 0;
 }
 
@@ -1511,17 +1435,12 @@ extern "C" int hypel_bn_act_fwd(const float* y, int64_t ldy, int64_t rows, int32
                                 int64_t ld2, const int32_t* idx2, float* z, int64_t ldz, hypel_stream_t stream) {
     HYPEL_REQUIRE(y && z && rows > 0 && c > 0, "hypel_bn_act_fwd");
     HYPEL_REQUIRE((mean == nullptr) == (rstd == nullptr) && (mean == nullptr) == (beta == nullptr), "hypel_bn_act_fwd");
-    const bool v4 = (c % 4 == 0) && aligned16(y) && aligned16(z) && aligned16(mask) && ldy % 4 == 0 &&
-                    ldz % 4 == 0 && (!mask || ldm % 4 == 0) &&
-                    (!res1 || idx1 || (aligned16(res1) && ld1 % 4 == 0)) &&
-                    (!res2 || idx2 || (aligned16(res2) && ld2 % 4 == 0));
+    // a residual with an index table is gathered element by element whatever its layout
+    const bool v4 = c % 4 == 0 && rows_v4(y, ldy) && rows_v4(z, ldz) && rows_v4(mask, ldm) &&
+                    (idx1 || rows_v4(res1, ld1)) && (idx2 || rows_v4(res2, ld2));
     const EwShape sh = ew_shape(rows, v4 ? c / 4 : c);
-    if (v4)
-        hipLaunchKernelGGL(bn_act_fwd_kernel<4>, dim3(sh.grid), dim3(256), 0, ST, y, ldy, rows, c, mean, rstd, beta,
-                           act, alpha, mask, ldm, res1, ld1, idx1, res2, ld2, idx2, z, ldz, sh.tx_log2);
-    else
-        hipLaunchKernelGGL(bn_act_fwd_kernel<1>, dim3(sh.grid), dim3(256), 0, ST, y, ldy, rows, c, mean, rstd, beta,
-                           act, alpha, mask, ldm, res1, ld1, idx1, res2, ld2, idx2, z, ldz, sh.tx_log2);
+    hipLaunchKernelGGL(HYPEL_VEC_KERNEL(v4, bn_act_fwd_kernel), dim3(sh.grid), dim3(256), 0, ST, y, ldy, rows, c, mean,
+                       rstd, beta, act, alpha, mask, ldm, res1, ld1, idx1, res2, ld2, idx2, z, ldz, sh.tx_log2);
     HYPEL_CHECK_LAUNCH("hypel_bn_act_fwd");
     return 0;
 }
@@ -1531,22 +1450,11 @@ static int launch_bwd_reduce(const float* dz, int64_t lddz, const float* y, int6
                              const float* mask, int64_t ldm, int32_t chunk_rows, float* partial,
                              hypel_stream_t stream, float* dy = nullptr, int64_t lddy = 0) {
     const int n_chunks = (int)((rows + chunk_rows - 1) / chunk_rows);
-    constexpr bool v4_on = true;
-    const bool v4 = v4_on && (c % 4 == 0) && (lddz % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)dz & 15) == 0) &&
-                    (((uintptr_t)y & 15) == 0) && (!mask || ((ldm % 4 == 0) && (((uintptr_t)mask & 15) == 0))) &&
-                    (!dy || ((lddy % 4 == 0) && (((uintptr_t)dy & 15) == 0)));
-    const dim3 grid(n_chunks, (c + STAT_TX - 1) / STAT_TX);
-#define HYPEL_BWD_REDUCE(K, D)                                                                                          \
-    hipLaunchKernelGGL(K<D>, grid, dim3(256), 0, ST, dz, lddz, y, ldy, rows, c, mean, rstd, beta, act, alpha, mask, ldm, \
-                       chunk_rows, partial, dy, lddy)
-    if (v4) {
-        if (dy) HYPEL_BWD_REDUCE(bn_act_bwd_reduce_v4_kernel, true);
-        else HYPEL_BWD_REDUCE(bn_act_bwd_reduce_v4_kernel, false);
-    } else {
-        if (dy) HYPEL_BWD_REDUCE(bn_act_bwd_reduce_kernel, true);
-        else HYPEL_BWD_REDUCE(bn_act_bwd_reduce_kernel, false);
-    }
-#undef HYPEL_BWD_REDUCE
+    const bool v4 = c % 4 == 0 && rows_v4(dz, lddz) && rows_v4(y, ldy) && rows_v4(mask, ldm) && rows_v4(dy, lddy);
+    const auto kernel = dy ? HYPEL_VEC_KERNEL(v4, bn_act_bwd_reduce_kernel, true)
+                           : HYPEL_VEC_KERNEL(v4, bn_act_bwd_reduce_kernel, false);
+    hipLaunchKernelGGL(kernel, dim3(n_chunks, (c + STAT_TX - 1) / STAT_TX), dim3(256), 0, ST, dz, lddz, y, ldy, rows, c,
+                       mean, rstd, beta, act, alpha, mask, ldm, chunk_rows, partial, dy, lddy);
     return 0;
 }
 
@@ -1630,15 +1538,10 @@ static int bn_act_bwd_apply_launch(const float* dz, int64_t lddz, const float* y
                                    int64_t lddy, hypel_stream_t stream, const char* what) {
     HYPEL_REQUIRE(dz && y && dy && rows > 0 && c > 0 && stat_rows >= rows, what);
     HYPEL_REQUIRE(mean == nullptr || sums != nullptr, what);
-    const bool v4 = (c % 4 == 0) && aligned16(y) && aligned16(dz) && aligned16(dy) && aligned16(mask) &&
-                    ldy % 4 == 0 && lddz % 4 == 0 && lddy % 4 == 0 && (!mask || ldm % 4 == 0);
+    const bool v4 = c % 4 == 0 && rows_v4(y, ldy) && rows_v4(dz, lddz) && rows_v4(dy, lddy) && rows_v4(mask, ldm);
     const EwShape sh = ew_shape(rows, v4 ? c / 4 : c);
-    if (v4)
-        hipLaunchKernelGGL(bn_act_bwd_apply_kernel<4>, dim3(sh.grid), dim3(256), 0, ST, dz, lddz, y, ldy, rows, c, mean,
-                           rstd, beta, act, alpha, mask, ldm, sums, dy, lddy, sh.tx_log2, stat_rows);
-    else
-        hipLaunchKernelGGL(bn_act_bwd_apply_kernel<1>, dim3(sh.grid), dim3(256), 0, ST, dz, lddz, y, ldy, rows, c, mean,
-                           rstd, beta, act, alpha, mask, ldm, sums, dy, lddy, sh.tx_log2, stat_rows);
+    hipLaunchKernelGGL(HYPEL_VEC_KERNEL(v4, bn_act_bwd_apply_kernel), dim3(sh.grid), dim3(256), 0, ST, dz, lddz, y, ldy,
+                       rows, c, mean, rstd, beta, act, alpha, mask, ldm, sums, dy, lddy, sh.tx_log2, stat_rows);
     HYPEL_CHECK_LAUNCH(what);
     return 0;
 }
@@ -1664,14 +1567,11 @@ extern "C" int hypel_chanmap_bwd(const float* dz, int64_t lddz, int64_t rows, in
                                  int32_t cin, const int32_t* start, int32_t accumulate, hypel_stream_t stream) {
     HYPEL_REQUIRE(dz && dr && rows > 0 && c > 0 && cin > 0, "hypel_chanmap_bwd");
     HYPEL_REQUIRE(start != nullptr || cin == c, "hypel_chanmap_bwd");
-    const bool v4 = (cin % 4 == 0) && aligned16(dr) && lddr % 4 == 0 && (start || (aligned16(dz) && lddz % 4 == 0));
+    // with a `start` table dz is summed element by element whatever its layout
+    const bool v4 = cin % 4 == 0 && rows_v4(dr, lddr) && (start || rows_v4(dz, lddz));
     const EwShape sh = ew_shape(rows, v4 ? cin / 4 : cin);
-    if (v4)
-        hipLaunchKernelGGL(chanmap_bwd_kernel<4>, dim3(sh.grid), dim3(256), 0, ST, dz, lddz, rows, c, dr, lddr, cin,
-                           start, accumulate, sh.tx_log2);
-    else
-        hipLaunchKernelGGL(chanmap_bwd_kernel<1>, dim3(sh.grid), dim3(256), 0, ST, dz, lddz, rows, c, dr, lddr, cin,
-                           start, accumulate, sh.tx_log2);
+    hipLaunchKernelGGL(HYPEL_VEC_KERNEL(v4, chanmap_bwd_kernel), dim3(sh.grid), dim3(256), 0, ST, dz, lddz, rows, c, dr,
+                       lddr, cin, start, accumulate, sh.tx_log2);
     HYPEL_CHECK_LAUNCH("hypel_chanmap_bwd");
     return 0;
 }
@@ -1687,20 +1587,6 @@ extern "C" int hypel_softmax_xent(const float* logits, int64_t ld, int64_t n, in
 }
 
 static void mse_partial_launch(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t c,
-                               float* da, int64_t ldda, float gscale, float* ws, int grid, hypel_stream_t stream);
-
-extern "C" int hypel_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t c, float* out,
-                         float* da, int64_t ldda, float gscale, float* ws, hypel_stream_t stream) {
-    HYPEL_REQUIRE(a && b && out && ws && rows > 0 && c > 0, "hypel_mse");
-    const int64_t total = rows * c;
-    const int grid = hypel_grid_1d(total, 256, RED_BLOCKS);
-    mse_partial_launch(a, lda, b, ldb, rows, c, da, ldda, gscale, ws, grid, stream);
-    hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, ST, ws, grid, 1.0 / (double)total, out);
-    HYPEL_CHECK_LAUNCH("hypel_mse");
-    return 0;
-}
-
-static void mse_partial_launch(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t c,
                                float* da, int64_t ldda, float gscale, float* ws, int grid, hypel_stream_t stream) {
     const int64_t total = rows * c;
     const float gcoef = gscale * 2.0f / (float)total;
@@ -1711,6 +1597,17 @@ static void mse_partial_launch(const float* a, int64_t lda, const float* b, int6
                            reinterpret_cast<const float4*>(b), total / 4, reinterpret_cast<float4*>(da), gcoef, ws);
     else
         hipLaunchKernelGGL(mse_partial_kernel, dim3(grid), dim3(256), 0, ST, a, lda, b, ldb, rows, c, da, ldda, gcoef, ws);
+}
+
+extern "C" int hypel_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t c, float* out,
+                         float* da, int64_t ldda, float gscale, float* ws, hypel_stream_t stream) {
+    HYPEL_REQUIRE(a && b && out && ws && rows > 0 && c > 0, "hypel_mse");
+    const int64_t total = rows * c;
+    const int grid = hypel_grid_1d(total, 256, RED_BLOCKS);
+    mse_partial_launch(a, lda, b, ldb, rows, c, da, ldda, gscale, ws, grid, stream);
+    hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, ST, ws, grid, 1.0 / (double)total, out);
+    HYPEL_CHECK_LAUNCH("hypel_mse");
+    return 0;
 }
 
 extern "C" int hypel_mse_partial_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t c,

@@ -646,6 +646,66 @@ def test_reduce_splits_pair_bit_identical(hip, splits, c0, c1, acc):
     assert torch.equal(a0, b0) and torch.equal(a1, b1)
 
 
+def _splits_forms_operands(hip, rng, stride, splits, count, n, ldc):
+    """The same partials and the same old output twice in sentinel-filled buffers: at a 16-byte aligned base (the float4
+    form) and one element further (the scalar form).  -> [(partial Ref, out Ref, out tensor)] * 2, the mask of the
+    output buffer's live floats relative to the out Ref, the lead of the out Ref."""
+    from tests.parity_util import SENT
+    lead, tail = 64, 67
+    live = np.zeros(stride, bool)
+    i = np.arange(count)
+    live[(i // n) * ldc + i % n if ldc > 0 else i] = True
+    part = rng.standard_normal(splits * stride).astype(np.float32)
+    old = np.where(live, rng.standard_normal(stride), SENT).astype(np.float32)
+    forms = []
+    for shift in (0, 1):
+        pbuf = np.full(lead + splits * stride + tail, SENT, np.float32)
+        obuf = np.full(lead + stride + tail, SENT, np.float32)
+        pbuf[lead + shift:lead + shift + part.size] = part
+        obuf[lead + shift:lead + shift + stride] = old
+        pt, ot = hip.upload(pbuf), hip.upload(obuf)
+        forms.append((Ref(pt, lead + shift), Ref(ot, lead + shift), ot))
+        assert forms[-1][0].ptr() % 16 == 4 * shift and forms[-1][1].ptr() % 16 == 4 * shift
+    return forms, live, lead
+
+
+def _splits_forms_compare(forms, live, lead):
+    from tests.parity_util import SENT, assert_same_bits, bits
+    got = [ot.cpu().numpy() for _, _, ot in forms]
+    for shift, g in enumerate(got):
+        untouched = np.ones(g.size, bool)
+        untouched[lead + shift:lead + shift + live.size] = ~live
+        assert (bits(g)[untouched] == bits(SENT)).all(), f"form {shift}: a float outside the {int(live.sum())} outputs was written"
+    a, b = (g[lead + shift:lead + shift + live.size][live] for shift, g in enumerate(got))
+    assert (bits(a) != bits(SENT)).all(), "an output was not written"
+    assert_same_bits("float4 form against scalar form", a, b)
+
+
+@pytest.mark.parametrize("stride,splits,count,acc,n,ldc", [(1000, s, 900, acc, n, 0) for s in (5, 31) for acc in (0, 1)
+                                                           for n in (0, 100)] + [(400, 5, 192, 1, 8, 16)])
+def test_reduce_splits_forms_agree_bitwise(hip, stride, splits, count, acc, n, ldc):
+    """The scalar and the float4 form of the slab sum are elementwise the same arithmetic: hypel_reduce_splits_f32 at an
+    aligned base and one element further gives the same bits, with and without a bias (n > 0, ldc == 0), in a window
+    (ldc > 0), and so do two such entries of one hypel_reduce_splits_multi_f32 launch.  31 slabs: the last count below
+    the wave form."""
+    from hypelcnn_amd.backend import REDUCE_ENTRY_DTYPE
+    rng = np.random.default_rng(1000 * splits + 10 * n + acc)
+    forms, live, lead = _splits_forms_operands(hip, rng, stride, splits, count, n, ldc)
+    bias = hip.upload(rng.standard_normal(n).astype(np.float32)) if n and not ldc else None
+    for p, o, _ in forms:
+        hip.call("reduce_splits_f32", p, stride, splits, o, count, acc, None if bias is None else Ref(bias), n, ldc)
+    hip.synchronize()
+    _splits_forms_compare(forms, live, lead)
+    if n == 0:  # the table form knows neither bias nor window
+        forms, live, lead = _splits_forms_operands(hip, rng, stride, splits, count, n, ldc)
+        base = forms[0][0]
+        rel = lambda r: (r.ptr() - base.ptr()) // 4
+        ents = hip.upload(np.array([(rel(p), rel(o), stride, count, splits, acc) for p, o, _ in forms], REDUCE_ENTRY_DTYPE))
+        hip.call("reduce_splits_multi_f32", base, Ref(ents), len(forms))
+        hip.synchronize()
+        _splits_forms_compare(forms, live, lead)
+
+
 def test_losses(hip):
     rng = np.random.default_rng(1)
     n, c = 1000, 15
