@@ -1190,81 +1190,131 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 3)) void seg_gemm
     seg_gemm_body<WM, WN, TM, TN, TA, TB, false, MULTI, false, false, false, true>(HYPEL_GEMM_ARGS);
 }
 
-template <int WM, int WN, int TM, int TN>
-int launch_cfg_pair(const float* a, int64_t lda, const float* b, int64_t ldb, float* c, int64_t ldc, int n,
-                    const hypel_group_t* groups, const hypel_seg_t* segs, const void* tiles, int n_tiles,
-                    const float* bias, int accumulate, const float* res, int64_t ldr, const int32_t* res_start,
-                    hipStream_t st) {
-    constexpr int BN = WN * TN * 32;
-    const int n_nt = (n + BN - 1) / BN;
-    hipLaunchKernelGGL((seg_gemm_kernel<WM, WN, TM, TN, false, true, false, false, true>), dim3(n_tiles * n_nt),
-                       dim3(256), 0, st, a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate,
-                       res, ldr, res_start, (float*)nullptr);
-    return 0;
+// ---- host side: the kernels' arguments, the kernels the library contains, the choice among them, the launch ----
+
+struct GemmArgs {  // HYPEL_GEMM_PARAMS, built once per entry point (n_ntiles is the launcher's to fill)
+    const float* a; int64_t lda; const float* b; int64_t ldb; float* c; int64_t ldc; int n;
+    const hypel_group_t* groups; const hypel_seg_t* segs; const void* tiles; int n_tiles, n_ntiles;
+    const float* bias; int accumulate; const float* res; int64_t ldr; const int32_t* res_start; float* stats;
+};
+
+struct GemmVariant {
+    void (*fn)(HYPEL_GEMM_PARAMS);
+    int bn, threads;  // output columns and threads of a block
+    bool multi;       // blocks of hypel_seg_gemm_multi_f32: one per record, no column tiling
+};
+template <int WM, int WN, int TM, int TN, bool TA, bool TB, bool NARROW = false, bool MULTI = false, bool PAIR = false,
+          bool VARN = false, bool ACT = false>
+constexpr GemmVariant f32() {
+    return {seg_gemm_kernel<WM, WN, TM, TN, TA, TB, NARROW, MULTI, PAIR, VARN, ACT>, NARROW ? 16 * TN : WN * TN * 32, 256,
+            MULTI};
+}
+template <int WM, int WN, int TM, int TN, bool TA, bool TB>
+constexpr GemmVariant s96() { return {seg_gemm_kernel_s96<WM, WN, TM, TN, TA, TB>, WN * TN * 32, 256, false}; }
+template <int WM, int WN, int TM, int TN, bool TA, bool TB, bool MULTI = false>
+constexpr GemmVariant spl() {
+    return {seg_gemm_split_kernel<WM, WN, TM, TN, TA, TB, MULTI>, WN * TN * 32, 64 * WM * WN, MULTI};
 }
 
-template <int WM, int WN, int TM, int TN, bool NARROW = false, bool MULTI = false>
-int launch_cfg(const float* a, int64_t lda, int ta, const float* b, int64_t ldb, int tb, float* c, int64_t ldc,
-               int n, const hypel_group_t* groups, const hypel_seg_t* segs, const void* tiles, int n_tiles,
-               const float* bias, int accumulate, const float* res, int64_t ldr, const int32_t* res_start,
-               hipStream_t st, float* stats = nullptr, bool cap96 = false) {
-    constexpr int BN = NARROW ? 16 * TN : WN * TN * 32;
-    const int n_nt = MULTI ? 1 : (n + BN - 1) / BN;
-    const int grid = n_tiles * n_nt;
-    if constexpr (NARROW && TN > 1) {  // forward products only (dispatch checks trans_a = trans_b = 0)
-        hipLaunchKernelGGL((seg_gemm_kernel<WM, WN, TM, TN, false, false, true, false>), dim3(grid), dim3(256), 0, st, a,
-                           lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate, res, ldr,
-                           res_start, stats);
+// THE KERNELS OF THE LIBRARY: every instantiation is listed here, once (35: 21 + 2 + 12).  Template arguments:
+// f32<WM, WN, TM, TN, TA, TB, NARROW, MULTI, PAIR, VARN, ACT>, s96<WM, WN, TM, TN, TA, TB>, spl<WM, WN, TM, TN, TA, TB, MULTI>.
+// xNN = output columns of a block (128 rows); x16 and kMfma16x4 (128x64, forward only) run on the 16x16x4 MFMA; kPair (data
+// gradients only) and kAct hold x32, x64; kMulti x16, x32, x64; kSplitMulti x32, x64, x128.
+enum { T_NN, T_NT, T_TN };  // index of the rows of three: A B (forward), A B^T (data gradients), A^T B (filter gradients)
+constexpr GemmVariant kF32x16[3] = {f32<4, 1, 1, 1, 0, 0, 1>(), f32<4, 1, 1, 1, 0, 1, 1>(), f32<4, 1, 1, 1, 1, 0, 1>()};
+constexpr GemmVariant kF32x32[3] = {f32<4, 1, 1, 1, 0, 0>(), f32<4, 1, 1, 1, 0, 1>(), f32<4, 1, 1, 1, 1, 0>()};
+constexpr GemmVariant kS96x32[2] = {s96<4, 1, 1, 1, 0, 0>(), s96<4, 1, 1, 1, 0, 1>()};  // 7 blocks per CU; A as stored only
+constexpr GemmVariant kF32x64[3] = {f32<4, 1, 1, 2, 0, 0>(), f32<4, 1, 1, 2, 0, 1>(), f32<4, 1, 1, 2, 1, 0>()};
+constexpr GemmVariant kF32x96[3] = {f32<4, 1, 1, 3, 0, 0>(), f32<4, 1, 1, 3, 0, 1>(), f32<4, 1, 1, 3, 1, 0>()};
+constexpr GemmVariant kMfma16x4 = f32<4, 1, 1, 4, 0, 0, 1>();
+constexpr GemmVariant kPair[2] = {f32<4, 1, 1, 1, 0, 1, 0, 0, 1>(), f32<4, 1, 1, 2, 0, 1, 0, 0, 1>()};
+constexpr GemmVariant kVarN = f32<4, 1, 1, 2, 0, 0, 0, 0, 0, 1>();  // 128x64 blocks, one- and two-tile MFMA phases
+constexpr GemmVariant kAct[2] = {f32<4, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1>(), f32<4, 1, 1, 2, 0, 0, 0, 0, 0, 0, 1>()};
+constexpr GemmVariant kMulti[3] = {f32<4, 1, 1, 1, 1, 0, 1, 1>(), f32<4, 1, 1, 1, 1, 0, 0, 1>(), f32<4, 1, 1, 2, 1, 0, 0, 1>()};
+constexpr GemmVariant kSplit[3][3] = {{spl<4, 1, 1, 1, 0, 0>(), spl<4, 1, 1, 1, 0, 1>(), spl<4, 1, 1, 1, 1, 0>()},   // 128x32
+                                      {spl<4, 2, 1, 1, 0, 0>(), spl<4, 2, 1, 1, 0, 1>(), spl<4, 2, 1, 1, 1, 0>()},   // 128x64
+                                      {spl<2, 4, 2, 1, 0, 0>(), spl<2, 4, 2, 1, 0, 1>(), spl<2, 4, 2, 1, 1, 0>()}};  // 128x128
+constexpr GemmVariant kSplitMulti[3] = {spl<4, 1, 1, 1, 1, 0, 1>(), spl<4, 2, 1, 1, 1, 0, 1>(), spl<2, 4, 2, 1, 1, 0, 1>()};
+
+struct GemmMode {     // the fields of `accumulate` (include/hypel.h)
+    bool accumulate;  // bit 0
+    // bits 8-9: tile-width hint of the caller (1 = 128x32, 2 = 128x64, 3 = 128x96), measured per launch class
+    // (profiles/r1_gemm_tile_choice.txt): data gradients with >= 48 reduction columns per segment and launches with few
+    // blocks run faster on the narrow tile, wide filter gradients on the wide one; without a hint: launches with fewer
+    // than ~one round of 128x64 blocks (level data gradients: 784) balance better as 128x32
+    int hint;
+    bool pairs;     // HYPEL_GEMM_PAIRED_SEGS: segments carry HYPEL_SEG_PAIR_FLAG
+    bool cap96;     // HYPEL_GEMM_SINGLE_SEG: every group has one segment
+    bool mfma16x4;  // HYPEL_GEMM_MFMA16X4: merged level with <= 16 filters per branch
+    bool var_n;     // HYPEL_GEMM_VAR_N: groups differ in their column count
+    bool split6;    // HYPEL_GEMM_SPLIT6: three-way split operands on the bf16 matrix cores
+    int act_idx;    // bits 16-18, HYPEL_GEMM_ACT_*: leaky-ReLU of (product + bias)
+};
+GemmMode decode_mode(int32_t w) {
+    return {(w & 1) != 0, (w >> 8) & 3, (w & HYPEL_GEMM_PAIRED_SEGS) != 0, (w & HYPEL_GEMM_SINGLE_SEG) != 0,
+            (w & HYPEL_GEMM_MFMA16X4) != 0, (w & HYPEL_GEMM_VAR_N) != 0, (w & HYPEL_GEMM_SPLIT6) != 0, (w >> 16) & 7};
+}
+
+// The kernel of a single launch (trans_a && trans_b is refused before): 0 and *out, or -1 and the error set.
+int select_variant(int trans_a, int trans_b, int n, int n_tiles, const GemmMode& mode, bool stats, bool res,
+                   const GemmVariant** out) {
+    auto [accumulate, hint, pairs, cap96, mfma16x4, var_n, split6, act_idx] = mode;
+    const int t = trans_a ? T_TN : (trans_b ? T_NT : T_NN);
+    if (split6) {
+        HYPEL_REQUIRE(!pairs && !mfma16x4 && !act_idx && n > 16,
+                      "hypel_seg_gemm_f32: HYPEL_GEMM_SPLIT6 needs a plain product with n > 16");
+        // hint: 1 = 128x32, 2 = 128x64, 3 = 128x128 blocks; 0 = by n
+        const int w = hint == 1 || n <= 32 ? 32 : (hint == 2 || n <= 64 ? 64 : (hint == 3 || n > 96 ? 128 : 64));
+        // tile records with their own column count are honoured by every variant (blocks beyond them exit): var_n (and
+        // cap96) change nothing here.  A variant of its own for the forward VAR_N launches -- eight waves of 32 x 64 in a
+        // 4 x 2 deal, one active wave on EVERY SIMD for a one-tile group -- was built and measured SLOWER than the rows-first
+        // 2 x 4 deal of 64 x 32 wave tiles (round 6: 349 vs 328 us on the 30-filter level, profiles/r6_exp_varn_kernel.txt);
+        // removed.
+        *out = &kSplit[w == 32 ? 0 : (w == 64 ? 1 : 2)][t];
         return 0;
+    }
+    // Tile choice (measured, profiles/r1_*): 128x64 blocks (4 waves/SIMD -> 1024 resident blocks) beat 128x128
+    // (3 waves/SIMD -> 768) on every layer of the model by 1.1-1.7x: the grids here are only 1-4 "waves" of blocks,
+    // so the finer grain wastes less of the last wave.
+    const bool plain_fwd = !trans_a && !trans_b && !pairs && !stats && !res;
+    if (act_idx) {
+        HYPEL_REQUIRE(plain_fwd && !accumulate && !mfma16x4 && !var_n && act_idx <= 4,
+                      "hypel_seg_gemm_f32: HYPEL_GEMM_ACT_* needs a plain forward product (no accumulate / shortcut / statistics)");
+        const bool narrow_a = hint == 1 || n <= 32 || (hint == 0 && (int64_t)n_tiles * ((n + 63) / 64) < 1000);
+        *out = &kAct[narrow_a ? 0 : 1];
+    } else if (mfma16x4 && n <= 64 && plain_fwd) {
+        *out = &kMfma16x4;
+    } else if (var_n && n > 32 && plain_fwd && hint != 1) {
+        *out = &kVarN;
+    } else if (hint == 3 && n > 64) {
+        // hint 3 = 128x96 blocks (three 32x32 accumulators per wave, 5 resident blocks per CU): N = 240 / 480 tile without
+        // padding (5 x 96, 96 + 96 + 48) and a layer's 392 row tiles x 3 or 5 column tiles fit the resident capacity where
+        // 392 x 4 / x 8 of the 64-wide tiling overflow it by 2 %.
+        *out = &kF32x96[t];
     } else {
-    if constexpr (TM * TN == 1 && !NARROW && !MULTI) {
-        if (cap96 && !ta) {  // single-segment launches on the 7-blocks-per-CU build of the 128x32 kernel
-            if (tb)
-                hipLaunchKernelGGL((seg_gemm_kernel_s96<WM, WN, TM, TN, false, true>), dim3(grid), dim3(256), 0, st, a, lda,
-                                   b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate, res, ldr,
-                                   res_start, stats);
-            else
-                hipLaunchKernelGGL((seg_gemm_kernel_s96<WM, WN, TM, TN, false, false>), dim3(grid), dim3(256), 0, st, a, lda,
-                                   b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate, res, ldr,
-                                   res_start, stats);
-            return 0;
+        if (hint == 3) hint = 2;
+        const bool narrow = hint == 1 || (hint == 0 && (int64_t)n_tiles * ((n + 63) / 64) < 1000);
+        if (pairs) {  // data gradients only: A as stored, B transposed; n > 16
+            HYPEL_REQUIRE(!trans_a && trans_b && n > 16 && !stats, "hypel_seg_gemm_f32: paired segments");
+            *out = &kPair[n <= 32 || narrow ? 0 : 1];
+        } else if (n <= 16 && !stats) {
+            // n <= 16 (the Cout = 15 level, fc_final): 128x16 blocks on the 16x16x4 MFMA (no reduction epilogues there)
+            *out = &kF32x16[t];
+        } else if (n <= 32 || narrow) {
+            // single-segment launches with A as stored: the 7-blocks-per-CU build of the 128x32 kernel
+            *out = cap96 && !trans_a ? &kS96x32[t] : &kF32x32[t];
+        } else {
+            *out = &kF32x64[t];
         }
     }
-#define HYPEL_GO(TA_, TB_)                                                                                         \
-    hipLaunchKernelGGL((seg_gemm_kernel<WM, WN, TM, TN, TA_, TB_, NARROW, MULTI>), dim3(grid), dim3(256), 0, st, a,  \
-                       lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate, res, ldr,     \
-                       res_start, stats)
-    if constexpr (MULTI) {  // filter gradients only: A transposed, B as stored
-        HYPEL_GO(true, false);
-    } else {
-        if (!ta && !tb) HYPEL_GO(false, false);
-        else if (!ta && tb) HYPEL_GO(false, true);
-        else HYPEL_GO(true, false);
-    }
-#undef HYPEL_GO
     return 0;
-    }
 }
 
-template <int WM, int WN, int TM, int TN, bool MULTI = false>
-int launch_split(const float* a, int64_t lda, int ta, const float* b, int64_t ldb, int tb, float* c, int64_t ldc, int n,
-                 const hypel_group_t* groups, const hypel_seg_t* segs, const void* tiles, int n_tiles, const float* bias,
-                 int accumulate, const float* res, int64_t ldr, const int32_t* res_start, hipStream_t st, float* stats) {
-    constexpr int BN = WN * TN * 32;
-    const int n_nt = MULTI ? 1 : (n + BN - 1) / BN;
-    const int grid = n_tiles * n_nt;
-#define HYPEL_GO(TA_, TB_)                                                                                           \
-    hipLaunchKernelGGL((seg_gemm_split_kernel<WM, WN, TM, TN, TA_, TB_, MULTI>), dim3(grid), dim3(64 * WM * WN), 0, st, a, lda, b, \
-                       ldb, c, ldc, n, groups, segs, tiles, n_tiles, n_nt, bias, accumulate, res, ldr, res_start, stats)
-    if constexpr (MULTI) {
-        HYPEL_GO(true, false);
-    } else {
-        if (!ta && !tb) HYPEL_GO(false, false);
-        else if (!ta && tb) HYPEL_GO(false, true);
-        else HYPEL_GO(true, false);
-    }
-#undef HYPEL_GO
-    return 0;
+void launch_variant(const GemmVariant& v, GemmArgs g, hypel_stream_t stream) {
+    g.n_ntiles = v.multi ? 1 : (g.n + v.bn - 1) / v.bn;
+    hipLaunchKernelGGL(v.fn, dim3(g.n_tiles * g.n_ntiles), dim3(v.threads), 0, (hipStream_t)stream, g.a, g.lda, g.b, g.ldb,
+                       g.c, g.ldc, g.n, g.groups, g.segs, g.tiles, g.n_tiles, g.n_ntiles, g.bias, g.accumulate, g.res, g.ldr,
+                       g.res_start, g.stats);
 }
 
 }  // namespace
@@ -1278,108 +1328,13 @@ static int seg_gemm_dispatch(const float* a, int64_t lda, int32_t trans_a, const
     HYPEL_REQUIRE(n > 0 && n_tiles >= 0, "hypel_seg_gemm_f32");
     HYPEL_REQUIRE(!(trans_a && trans_b), "hypel_seg_gemm_f32: A^T B^T products are not part of the path");
     if (n_tiles == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    // Tile choice (measured, profiles/r1_*): 128x64 blocks (4 waves/SIMD -> 1024 resident blocks) beat 128x128
-    // (3 waves/SIMD -> 768) on every layer of the model by 1.1-1.7x: the grids here are only 1-4 "waves" of blocks,
-    // so the finer grain wastes less of the last wave.
-    // bits 8-9 of `accumulate`: tile-width hint of the caller (1 = 128x32, 2 = 128x64, 3 = 128x96), measured per launch
-    // class (profiles/r1_gemm_tile_choice.txt): data gradients with >= 48 reduction columns per segment and launches with
-    // few blocks run faster on the narrow tile, wide filter gradients on the wide one; without a hint: launches with
-    // fewer than ~one round of 128x64 blocks (level data gradients: 784) balance better as 128x32
-    int hint = (accumulate >> 8) & 3;
-    const bool pairs = (accumulate & HYPEL_GEMM_PAIRED_SEGS) != 0;  // segments carry HYPEL_SEG_PAIR_FLAG
-    const bool cap96 = (accumulate & HYPEL_GEMM_SINGLE_SEG) != 0;   // every group has one segment
-    const bool mfma16x4 = (accumulate & HYPEL_GEMM_MFMA16X4) != 0;  // merged level with <= 16 filters per branch
-    const bool var_n = (accumulate & HYPEL_GEMM_VAR_N) != 0;        // groups differ in their column count
-    const bool split6 = (accumulate & HYPEL_GEMM_SPLIT6) != 0;      // three-way split operands on the bf16 matrix cores
-    const int act_idx = (accumulate >> 16) & 7;                     // HYPEL_GEMM_ACT_*: leaky-ReLU of (product + bias)
-    accumulate &= 1;
-    if (split6) {
-        HYPEL_REQUIRE(!pairs && !mfma16x4 && !act_idx && n > 16,
-                      "hypel_seg_gemm_f32: HYPEL_GEMM_SPLIT6 needs a plain product with n > 16");
-        // hint: 1 = 128x32, 2 = 128x64, 3 = 128x128 blocks; 0 = by n
-        const int w = hint == 1 || n <= 32 ? 32 : (hint == 2 || n <= 64 ? 64 : (hint == 3 || n > 96 ? 128 : 64));
-        // tile records with their own column count are honoured by every variant (blocks beyond them exit).  A variant of
-        // its own for the forward VAR_N launches -- eight waves of 32 x 64 in a 4 x 2 deal, one active wave on EVERY SIMD for
-        // a one-tile group -- was built and measured SLOWER than the rows-first 2 x 4 deal of 64 x 32 wave tiles (round 6:
-        // 349 vs 328 us on the 30-filter level, profiles/r6_exp_varn_kernel.txt); removed.
-        (void)var_n;
-        if (w == 32)
-            launch_split<4, 1, 1, 1>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                                     accumulate, res, ldr, res_start, st, stats);
-        else if (w == 64)
-            launch_split<4, 2, 1, 1>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                                     accumulate, res, ldr, res_start, st, stats);
-        else
-            launch_split<2, 4, 2, 1>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                                     accumulate, res, ldr, res_start, st, stats);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    const bool plain_fwd = !trans_a && !trans_b && !pairs && !stats && !res;
-    if (act_idx) {
-        HYPEL_REQUIRE(plain_fwd && !accumulate && !mfma16x4 && !var_n && act_idx <= 4,
-                      "hypel_seg_gemm_f32: HYPEL_GEMM_ACT_* needs a plain forward product (no accumulate / shortcut / statistics)");
-        const bool narrow_a = hint == 1 || n <= 32 || (hint == 0 && (int64_t)n_tiles * ((n + 63) / 64) < 1000);
-        const int bn = narrow_a ? 32 : 64;
-        const int n_nt = (n + bn - 1) / bn;
-        if (narrow_a)
-            hipLaunchKernelGGL((seg_gemm_kernel<4, 1, 1, 1, false, false, false, false, false, false, true>),
-                               dim3(n_tiles * n_nt), dim3(256), 0, st, a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles,
-                               n_nt, bias, act_idx << 16, res, ldr, res_start, (float*)nullptr);
-        else
-            hipLaunchKernelGGL((seg_gemm_kernel<4, 1, 1, 2, false, false, false, false, false, false, true>),
-                               dim3(n_tiles * n_nt), dim3(256), 0, st, a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles,
-                               n_nt, bias, act_idx << 16, res, ldr, res_start, (float*)nullptr);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    if (mfma16x4 && n <= 64 && plain_fwd) {
-        launch_cfg<4, 1, 1, 4, true>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                                     accumulate, res, ldr, res_start, st);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    if (var_n && n > 32 && plain_fwd && hint != 1) {  // 128x64 blocks, one- and two-tile MFMA phases
-        const int n_nt = (n + 63) / 64;
-        hipLaunchKernelGGL((seg_gemm_kernel<4, 1, 1, 2, false, false, false, false, false, true>),
-                           dim3(n_tiles * n_nt), dim3(256), 0, st, a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles,
-                           n_nt, bias, accumulate, res, ldr, res_start, (float*)nullptr);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    // hint 3 = 128x96 blocks (three 32x32 accumulators per wave, 5 resident blocks per CU): N = 240 / 480 tile without
-    // padding (5 x 96, 96 + 96 + 48) and a layer's 392 row tiles x 3 or 5 column tiles fit the resident capacity where
-    // 392 x 4 / x 8 of the 64-wide tiling overflow it by 2 %.
-    if (hint == 3 && n > 64) {
-        launch_cfg<4, 1, 1, 3>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                               accumulate, res, ldr, res_start, st, stats);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    if (hint == 3) hint = 2;
-    const bool narrow = hint == 1 || (hint == 0 && (int64_t)n_tiles * ((n + 63) / 64) < 1000);
-    if (pairs) {  // data gradients only: A as stored, B transposed; n > 16
-        HYPEL_REQUIRE(!trans_a && trans_b && n > 16 && !stats, "hypel_seg_gemm_f32: paired segments");
-        if (n <= 32 || narrow)
-            launch_cfg_pair<4, 1, 1, 1>(a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, bias, accumulate, res,
-                                        ldr, res_start, st);
-        else
-            launch_cfg_pair<4, 1, 1, 2>(a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, bias, accumulate, res,
-                                        ldr, res_start, st);
-        HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
-        return 0;
-    }
-    // n <= 16 (the Cout = 15 level, fc_final): 128x16 blocks on the 16x16x4 MFMA (no reduction epilogues there)
-    if (n <= 16 && !stats)
-        launch_cfg<4, 1, 1, 1, true>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                                     accumulate, res, ldr, res_start, st);
-    else if (n <= 32 || narrow)
-        launch_cfg<4, 1, 1, 1>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                               accumulate, res, ldr, res_start, st, stats, cap96);
-    else
-        launch_cfg<4, 1, 1, 2>(a, lda, trans_a, b, ldb, trans_b, c, ldc, n, groups, segs, tiles, n_tiles, bias,
-                               accumulate, res, ldr, res_start, st, stats);
+    const GemmMode mode = decode_mode(accumulate);
+    const GemmVariant* v;
+    if (int rc = select_variant(trans_a, trans_b, n, n_tiles, mode, stats != nullptr, res != nullptr, &v)) return rc;
+    // the kernels read bit 0 and the ACT index of `accumulate` (an ACT launch has bit 0 clear); every kernel without a
+    // statistics epilogue (ACT, PAIR, VARN, MFMA16X4, 128x16) is chosen only when stats is null
+    launch_variant(*v, {a, lda, b, ldb, c, ldc, n, groups, segs, tiles, n_tiles, 0, bias, mode.accumulate | mode.act_idx << 16,
+                        res, ldr, res_start, stats}, stream);
     HYPEL_CHECK_LAUNCH("hypel_seg_gemm_f32");
     return 0;
 }
@@ -1423,27 +1378,11 @@ extern "C" int hypel_seg_gemm_multi_f32(const float* base, int32_t trans_a, int3
                   "hypel_seg_gemm_multi_f32");
     HYPEL_REQUIRE(!split6 || tile_width >= 32, "hypel_seg_gemm_multi_f32: split operands need 32- / 64- / 128-wide blocks");
     if (n_blocks == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    float* c = const_cast<float*>(base);
-    if (split6) {
-        if (tile_width == 32)
-            launch_split<4, 1, 1, 1, true>(base, 0, 1, base, 0, 0, c, 0, 32, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                           nullptr, 0, nullptr, st, nullptr);
-        else if (tile_width == 64)
-            launch_split<4, 2, 1, 1, true>(base, 0, 1, base, 0, 0, c, 0, 64, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                           nullptr, 0, nullptr, st, nullptr);
-        else
-            launch_split<2, 4, 2, 1, true>(base, 0, 1, base, 0, 0, c, 0, 128, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                           nullptr, 0, nullptr, st, nullptr);
-    } else if (tile_width == 16)
-        launch_cfg<4, 1, 1, 1, true, true>(base, 0, 1, base, 0, 0, c, 0, 16, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                           nullptr, 0, nullptr, st);
-    else if (tile_width == 32)
-        launch_cfg<4, 1, 1, 1, false, true>(base, 0, 1, base, 0, 0, c, 0, 32, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                            nullptr, 0, nullptr, st);
-    else
-        launch_cfg<4, 1, 1, 2, false, true>(base, 0, 1, base, 0, 0, c, 0, 64, nullptr, segs, blocks, n_blocks, nullptr, 0,
-                                            nullptr, 0, nullptr, st);
+    const GemmVariant& v = split6 ? kSplitMulti[tile_width == 32 ? 0 : (tile_width == 64 ? 1 : 2)]
+                                  : kMulti[tile_width == 16 ? 0 : (tile_width == 32 ? 1 : 2)];
+    // every operand of a record is addressed from `base`: no leading dimensions, groups, bias, shortcut or statistics
+    launch_variant(v, {base, 0, base, 0, const_cast<float*>(base), 0, tile_width, nullptr, segs, blocks, n_blocks, 0, nullptr, 0,
+                       nullptr, 0, nullptr, nullptr}, stream);
     HYPEL_CHECK_LAUNCH("hypel_seg_gemm_multi_f32");
     return 0;
 }

@@ -128,6 +128,7 @@ KSLICE_FRAC_MIN = 0.7    # smallest threshold (fraction of the launch's heaviest
 #                          partial traffic; the simulation, which knows nothing of two blocks sharing a CU, prefers 0.25
 KSLICE_REDUCE_COST_K = 55  # the reduce launch behind a sliced launch (~6 us), in reduction columns of a 128 x 128 block
 KSLICE_SLOTS = {1: 768, 2: 512, 3: 512}  # resident blocks of the split kernels by tile-width hint (3 / 2 / 2 per CU)
+SPLIT6_BN = {1: 32, 2: 64, 3: 128}  # output columns of their blocks, by the same hint
 GEMM_MFMA16X4 = abi.const("HYPEL_GEMM_MFMA16X4")  # 128x64 blocks on the 16x16x4 MFMA (merged level, <= 16 filters)
 GEMM_VAR_N = abi.const("HYPEL_GEMM_VAR_N")  # tile records carry their group's column count
 # Merged multi-kernel levels (include/hypel.h): the nested branches of a level share one packed weight image
@@ -331,23 +332,10 @@ class TowerPlan:
         count = pos - c_min
         if c_min % n:
             return None
-        a_ks = lda if ta else 1
-        b_ks = 1 if tb else ldb
         out = GemmTables()
         for c_off, gs, rows in groups:
-            ktot = sum(k for _, _, k in gs)
-            cuts = [((ktot * s // S) + 31) // 32 * 32 for s in range(S)] + [ktot]
-            cuts = [min(c, ktot) for c in cuts]
-            parts = [[] for _ in range(S)]
-            base = 0
-            for (a_off, b_off, k) in gs:
-                for s in range(S):
-                    lo, hi = max(cuts[s], base), min(cuts[s + 1], base + k)
-                    if hi > lo:
-                        parts[s].append((a_off + (lo - base) * a_ks, b_off + (lo - base) * b_ks, hi - lo))
-                base += k
-            for s in range(S):
-                out.add_group(s * count + (c_off - c_min), parts[s], rows)
+            for s, part in enumerate(self._cut_segments(gs, S, lda if ta else 1, 1 if tb else ldb, grain=GEMM_BK)):
+                out.add_group(s * count + (c_off - c_min), part, rows)
         return out, S, c_min, count
 
     @staticmethod
@@ -455,7 +443,7 @@ class TowerPlan:
         """Choose K-slices for a launch on the split kernels (see KSLICE_MIN_GAIN above).  Returns None (leave the launch
         alone) or {group index: number of slices}."""
         groups = tables.groups
-        bn = {1: 32, 2: 64, 3: 128}[width_hint]
+        bn = SPLIT6_BN[width_hint]
         slots = KSLICE_SLOTS[width_hint]
         ct = (n + bn - 1) // bn
         ov = KSLICE_OVERHEAD_K
@@ -540,11 +528,12 @@ class TowerPlan:
         return out
 
     @staticmethod
-    def _cut_segments(gs, s_, a_ks, b_ks):
-        """Cut a segment list into s_ slices of (nearly) equal reduction length, at multiples of 16 columns inside a
-        segment; a_ks / b_ks = element distance of one reduction column in A / B."""
+    def _cut_segments(gs, s_, a_ks, b_ks, grain=16):
+        """Cut a segment list into s_ slices of (nearly) equal reduction length, at multiples of `grain` columns of the
+        whole list (16: the split kernels' k-tile; GEMM_BK: the fp32 kernels'); a_ks / b_ks = element distance of one
+        reduction column in A / B."""
         ktot = sum(k for _, _, k in gs)
-        cuts = [min(ktot, (ktot * i // s_ + 15) // 16 * 16) for i in range(s_)] + [ktot]
+        cuts = [min(ktot, (ktot * i // s_ + grain - 1) // grain * grain) for i in range(s_)] + [ktot]
         parts = [[] for _ in range(s_)]
         base = 0
         for (a_off, b_off, k) in gs:
@@ -584,7 +573,6 @@ class TowerPlan:
                                pair and any(k <= 16 for _, gs, _ in tables.groups for _, _, k in gs))
         if sp6:
             pair, hint, single_seg = False, sp6, False
-            accumulate = int(accumulate) | GEMM_SPLIT6
         reduce_after = None
         if (sp6 and kslice and stats is None and not flags and int(ldc) == int(n) and not (ta and tb)
                 and tables.groups and not any(tables.ns)):
@@ -596,21 +584,19 @@ class TowerPlan:
         garr, sarr, tarr, macs = tables.finalize(n, pair=pair)
         if len(tarr) == 0:
             return
-        if pair and tables.paired:
-            accumulate = int(accumulate) | GEMM_PAIRED_SEGS
         g_t, s_t, t_t = self.be.upload(garr), self.be.upload(sarr), self.be.upload(tarr)
         self.tables += [g_t, s_t, t_t]
-        if single_seg and not flags:
-            accumulate = int(accumulate) | GEMM_SINGLE_SEG
-        accumulate = int(accumulate) | int(flags)
+        # the launch's `accumulate` word (include/hypel.h): bit 0, the tile-width hint in bits 8-9, the flag bits
+        word = (int(accumulate) | hint << 8 | int(flags) | (GEMM_SPLIT6 if sp6 else 0)
+                | (GEMM_PAIRED_SEGS if pair and tables.paired else 0) | (GEMM_SINGLE_SEG if single_seg and not flags else 0))
         args = (a_ref, int(lda), int(ta), b_ref, int(ldb), int(tb), c_ref, int(ldc), int(n), Ref(g_t), Ref(s_t),
-                Ref(t_t), int(len(tarr)), bias_ref, int(accumulate) | (hint << 8))
+                Ref(t_t), int(len(tarr)), bias_ref, word)
         name = "seg_gemm_f32"
         if res is not None:
             name = "seg_gemm_res_f32"
             args = args + (res[0], int(res[1]), res[2])
         elif stats is not None:
-            assert len(tables.groups) == 1 and not (int(accumulate) & 1) and int(ldc) == int(n)
+            assert len(tables.groups) == 1 and not (word & 1) and int(ldc) == int(n)
             name = "seg_gemm_stats_f32"
             args = args + (None,)
         l = Launch(name, args, flops=2 * macs, nbytes=tables.compulsory_bytes(n, lda, ta, ldb, tb), tag=tag)
@@ -1686,7 +1672,7 @@ class TowerPlan:
             """[(n0, tile width)] of a product with n output columns: one width per product.  split6 = tile-width hint of
             the split-operand kernel (widths | GEMM_MULTI_SPLIT6: their own launches)."""
             if split6:
-                wdt = {1: 32, 2: 64, 3: 128}[split6]
+                wdt = SPLIT6_BN[split6]
                 return [(n0, wdt | GEMM_MULTI_SPLIT6) for n0 in range(0, n, wdt)]
             wdt = 16 if n <= 16 else (32 if n <= 32 else 64)
             return [(n0, wdt) for n0 in range(0, n, wdt)]

@@ -10,8 +10,14 @@ import torch
 
 import ctypes
 
+from hypelcnn_amd import abi
 from hypelcnn_amd.backend import (COLLECTIVES, GROUP_DTYPE, LOSS_NONE, LOSS_TERM_DTYPE, MTILE_DTYPE, REDUCE_ENTRY_DTYPE, SEG_DTYPE, TILE_DTYPE, Ref,
                                   bind_collective)
+
+
+GEMM_PAIRED_SEGS, GEMM_MFMA16X4, GEMM_VAR_N, GEMM_SPLIT6, GEMM_MULTI_SPLIT6, SEG_PAIR_FLAG = (
+    abi.const("HYPEL_" + k) for k in ("GEMM_PAIRED_SEGS", "GEMM_MFMA16X4", "GEMM_VAR_N", "GEMM_SPLIT6", "GEMM_MULTI_SPLIT6",
+                                      "SEG_PAIR_FLAG"))
 
 
 def _arr(ref, dtype=np.float32):
@@ -256,11 +262,11 @@ class EmuBackend:
         if any(group_plain.values()):
             assert not ((accumulate_raw >> 16) & 7), "HYPEL_TILE_PLAIN records are not valid with HYPEL_GEMM_ACT_*"
         if any(group_n.values()):
-            assert accumulate_raw & 0x4000, "tile records with their own n need HYPEL_GEMM_VAR_N"
-        if accumulate_raw & 0x2000:
+            assert accumulate_raw & GEMM_VAR_N, "tile records with their own n need HYPEL_GEMM_VAR_N"
+        if accumulate_raw & GEMM_MFMA16X4:
             assert n <= 64 and not ta and not tb, "HYPEL_GEMM_MFMA16X4: forward products with n <= 64"
-        if accumulate_raw & 0x8000:  # HYPEL_GEMM_SPLIT6: same result to fp32 rounding, plain products only
-            assert n > 16 and not (ta and tb) and not (accumulate_raw & 0x2400) and not ((accumulate_raw >> 16) & 7), \
+        if accumulate_raw & GEMM_SPLIT6:  # same result to fp32 rounding, plain products only
+            assert n > 16 and not (ta and tb) and not (accumulate_raw & (GEMM_MFMA16X4 | GEMM_PAIRED_SEGS)) and not ((accumulate_raw >> 16) & 7), \
                 "HYPEL_GEMM_SPLIT6: plain NN / NT / TN products with n > 16"
         assert not (ta and tb), "A^T B^T products are not part of the path"
         n_launch = n
@@ -292,9 +298,9 @@ class EmuBackend:
             for si in range(s_lo, s_hi):
                 sg = s[si]
                 k = int(sg["k"])
-                if k & 0x40000000:  # HYPEL_SEG_PAIR_FLAG: shares a k-tile with the next segment (no effect on the result)
-                    assert (accumulate_raw & 0x400) and not ta and tb and n > 16, "pair flag without HYPEL_GEMM_PAIRED_SEGS"
-                    k &= ~0x40000000
+                if k & SEG_PAIR_FLAG:  # shares a k-tile with the next segment (no effect on the result)
+                    assert (accumulate_raw & GEMM_PAIRED_SEGS) and not ta and tb and n > 16, "pair flag without HYPEL_GEMM_PAIRED_SEGS"
+                    k &= ~SEG_PAIR_FLAG
                     assert k <= 16 and si + 1 < s_hi and 0 < int(s[si + 1]["k"]) <= 16, "malformed segment pair"
                     assert abs(int(sg["a_off"]) - int(s[si + 1]["a_off"])) * 4 < 2 ** 31
                     assert abs(int(sg["b_off"]) - int(s[si + 1]["b_off"])) * 4 < 2 ** 31
@@ -320,7 +326,7 @@ class EmuBackend:
             act_idx = (accumulate_raw >> 16) & 7  # HYPEL_GEMM_ACT_*: leaky-ReLU of (product + bias)
             if act_idx:
                 assert not ta and not tb and not accumulate and not any_split and act_idx <= 4 and \
-                    not (accumulate_raw & 0x6000), "HYPEL_GEMM_ACT_*: plain forward products only"
+                    not (accumulate_raw & (GEMM_MFMA16X4 | GEMM_VAR_N)), "HYPEL_GEMM_ACT_*: plain forward products only"
                 alpha = np.float32([0.0, 0.1, 0.18, 0.2, 0.01][act_idx]).astype(np.float64)
                 acc = np.where(acc > 0, acc, alpha * acc)
             if accumulate and not plain:
@@ -346,8 +352,8 @@ class EmuBackend:
     def k_seg_gemm_multi_f32(self, base, ta, tb, tile_width, segs, blocks, n_blocks):
         """Specification of the merged filter-gradient launch: every block record is one 128 x tile_width output
         block of its own product C = A^T B (+ C when flagged), all offsets relative to `base`."""
-        split6 = bool(tile_width & 0x100)  # HYPEL_GEMM_MULTI_SPLIT6: same result to fp32 rounding
-        tile_width &= ~0x100
+        split6 = bool(tile_width & GEMM_MULTI_SPLIT6)  # same result to fp32 rounding
+        tile_width &= ~GEMM_MULTI_SPLIT6
         assert ta == 1 and tb == 0 and tile_width in ((32, 64, 128) if split6 else (16, 32, 64))
         s = segs.t.numpy()[segs.off:].view(SEG_DTYPE)
         recs = blocks.t.numpy()[blocks.off:].view(MTILE_DTYPE)[:n_blocks]

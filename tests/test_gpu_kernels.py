@@ -43,6 +43,13 @@ def _tables(b, groups):  # (b: unused, kept for the call sites)
     (120, 1085, 15, 1, 0, 0, False),   # level-2 filter gradient: M = Cin = 120, n = 15
     (257, 49, 16, 0, 1, 1, False),
     (129, 7, 1, 0, 0, 1, False),
+    # kernels no other seg-GEMM test launches (acc = the whole `accumulate` word: bit 0 | tile-width hint << 8): the
+    # 128x96 blocks (hint 3, n > 64) in the three operand layouts and the 128x64 filter-gradient kernel (hint 2), at 129
+    # rows and k = 33 (the second row tile and k-tile ragged) and one column more than a block is wide
+    (129, 33, 97, 0, 0, 3 << 8, True),
+    (129, 33, 97, 0, 1, 3 << 8 | 1, False),
+    (129, 33, 97, 1, 0, 3 << 8, False),
+    (129, 33, 65, 1, 0, 2 << 8 | 1, False),
 ])
 def test_seg_gemm_single_segment(hip, rows, k, n, ta, tb_, acc, bias):
     rng = np.random.default_rng(rows * 7 + k)
@@ -459,6 +466,32 @@ def test_seg_gemm_multi_products(hip):
         for (ot, _, _, _), want, p in zip(outs, wants, prods):
             got = ot.cpu().numpy().reshape(p["m"], p["n"])
             np.testing.assert_allclose(got, want, rtol=2e-4, atol=2e-4 * max(1.0, np.abs(want).max()), err_msg=be.name)
+
+
+@pytest.mark.parametrize("width,split6", [(16, 0), (32, 0), (32, 1), (64, 1), (128, 1)])
+def test_seg_gemm_multi_block_widths(hip, width, split6):
+    """hypel_seg_gemm_multi_f32 at the block widths test_seg_gemm_multi_products does not launch, fp32 and split-operand
+    kernels: one product C = A^T B of 129 rows and k = 33 (the second row tile and k-tile ragged) and width + 1 columns
+    (a second column block of one column), accumulated into C."""
+    from hypelcnn_amd.backend import MTILE_DTYPE
+    from hypelcnn_amd.plan import GEMM_MULTI_SPLIT6
+    m, k, n = 129, 33, width + 1
+    rng = np.random.default_rng(width + split6)
+    x = rng.standard_normal((k, m + 3)).astype(np.float32)   # A stored [k, m], lda = m + 3
+    dy = rng.standard_normal((k, n + 1)).astype(np.float32)  # B stored [k, n], ldb = n + 1
+    out0 = rng.standard_normal(m * n).astype(np.float32)
+    want = out0.reshape(m, n) + x[:, :m].astype(np.float64).T @ dy[:, :n].astype(np.float64)
+    for be in (hip, EmuBackend()):
+        base = be.zeros(16)
+        rel = lambda t: (Ref(t).ptr() - Ref(base).ptr()) // 4
+        xt, dt, ot = be.upload(x), be.upload(dy), be.upload(out0)
+        recs = [(rel(ot), rel(xt), rel(dt), m0, m, n0, n, 0, 1, k, 1, m + 3, n + 1, n, 0)
+                for m0 in range(0, m, 128) for n0 in range(0, n, width)]
+        s_t, r_t = be.upload(np.array([(rel(xt), rel(dt), k, 0)], SEG_DTYPE)), be.upload(np.array(recs, MTILE_DTYPE))
+        be.call("seg_gemm_multi_f32", Ref(base), 1, 0, width | (GEMM_MULTI_SPLIT6 if split6 else 0), Ref(s_t), Ref(r_t), len(recs))
+        be.synchronize()
+        np.testing.assert_allclose(ot.cpu().numpy().reshape(m, n), want, rtol=2e-4, atol=2e-4 * max(1.0, np.abs(want).max()),
+                                   err_msg=be.name)
 
 
 def test_seg_gemm_empty_group_writes_zero(hip):
