@@ -51,6 +51,9 @@ SCENE_RANK_WS_WORDS = abi.const("HYPEL_SCENE_RANK_WS_WORDS")  # uint32 of worksp
 COLUMN_RANK_WS_WORDS, COLUMN_RANK_MAX_RANKS, COLUMN_RANK_MAX_BANDS = (
     abi.const("HYPEL_COLUMN_RANK_" + k) for k in ("WS_WORDS", "MAX_RANKS", "MAX_BANDS"))
 COMPACT_TILE = abi.const("HYPEL_COMPACT_TILE")  # pixels per int32 of hypel_mask_compact_points_i32's workspace
+# classes of hypel_components_votes_i32 (its exclude mask is 64 bits), status words of hypel_components_label_u8
+COMPONENTS_MAX_CLASSES = abi.const("HYPEL_COMPONENTS_MAX_CLASSES")
+COMPONENTS_OK, COMPONENTS_STEP_CAP = abi.const("HYPEL_COMPONENTS_OK"), abi.const("HYPEL_COMPONENTS_STEP_CAP")
 SUMMARY_SLICE = abi.const("HYPEL_SUMMARY_SLICE")  # elements per slice of hypel_tensor_summary_f32
 SUMMARY_MAX_LIMITS = abi.const("HYPEL_SUMMARY_MAX_LIMITS")
 # rows sorted per column for the bin edges, edges per column, classes of the LDS histogram, depth cap of the level loop

@@ -840,6 +840,45 @@ int hypel_mask_compact_points_i32(const uint8_t* mask, int64_t h, int64_t w, int
 int hypel_points_expand_i32(const int32_t* points, int64_t n, int32_t repeat, int64_t remainder, int32_t* out,
                             hypel_stream_t stream);
 
+/* ---- shadow regions of a target image (utilities/reveal_shadow_targets.py; csrc/components.hip) ------------------
+ * Rasters are [h][w] in row-major order, p = y * w + x; h * w < 2^31.  Integer work throughout: two calls write
+ * identical bytes.
+ *
+ * hypel_components_label_u8: mask uint8, non-zero = inside.  root[p] (int32) = the row-major index of the first pixel
+ *   of p's 8-connected component, -1 outside the mask.  Three launches: tiles of 64 x 16 pixels labelled in LDS, the
+ *   links across tile borders merged (parent entries touched by device-scope atomics only; no block waits for
+ *   another), every pixel walked to its root.  ws: h * w int32 (the parent table).  *status (device int32, cleared by
+ *   the call) stays HYPEL_COMPONENTS_OK unless a walk ran into its step cap (4 * h * w + 64 per union, h * w per
+ *   pixel of the last launch): then HYPEL_COMPONENTS_STEP_CAP is set, the walk is given up and root is not valid.
+ * hypel_components_compact_i32: comp[p] (int32) = the rank of root[p] among all roots (root[r] == r) in row-major
+ *   order, 0 .. n - 1, and -1 where root[p] is; *n_components (device int32) = n.  Per-tile counts, a prefix sum over
+ *   the tiles, ranks by ballot -- no counter decides an id.  ws: ceil(h * w / HYPEL_COMPACT_TILE) int32.
+ * hypel_components_votes_i32: targets uint8; votes [n_components][n_classes] int32 and size [n_components] int32 are
+ *   cleared by the call.  size[c] = pixels with comp == c.  For every pixel p with comp[p] >= 0 and every one of its 8
+ *   neighbours q inside the image with comp[q] < 0, targets[q] < n_classes and bit targets[q] of `exclude` clear:
+ *   votes[comp[p]][targets[q]] += 1 (a lit pixel counts once for every component pixel it touches).  winner[c]
+ *   (uint8) = the class with the most votes, the smallest such class on a tie, 255 where c has no vote.
+ *   1 <= n_classes <= HYPEL_COMPONENTS_MAX_CLASSES; n_components = 0 launches nothing.
+ * hypel_components_relabel_u8: out[p] = winner[comp[p]] where comp[p] >= 0 and that winner is not 255, else
+ *   targets[p]; with plus_one != 0 every value other than 255 is then raised by 1.
+ * hypel_shadow_correct_f32: out [h][w][bands] float32 = c + c * (m * r_minus_1[b]) with c = float32(sample (y, x, b))
+ *   of the strided source (dtype HYPEL_DTYPE_*, element strides sy, sx, sb as in the scene preparation), m = 1.0f where
+ *   map[y][x] != 0 and 0.0f elsewhere; both products and the sum are rounded on their own, in that order -- NumPy's
+ *   float32 expression bit for bit (no fused multiply-add). */
+#define HYPEL_COMPONENTS_MAX_CLASSES 64
+enum { HYPEL_COMPONENTS_OK = 0, HYPEL_COMPONENTS_STEP_CAP = 1 };
+int hypel_components_label_u8(const uint8_t* mask, int64_t h, int64_t w, int32_t* root, int32_t* ws, int32_t* status,
+                              hypel_stream_t stream);
+int hypel_components_compact_i32(const int32_t* root, int64_t h, int64_t w, int32_t* comp, int32_t* n_components,
+                                 int32_t* ws, hypel_stream_t stream);
+int hypel_components_votes_i32(const uint8_t* targets, const int32_t* comp, int64_t h, int64_t w, int32_t n_components,
+                               int32_t n_classes, uint64_t exclude, int32_t* votes, int32_t* size, uint8_t* winner,
+                               hypel_stream_t stream);
+int hypel_components_relabel_u8(const uint8_t* targets, const int32_t* comp, const uint8_t* winner, int64_t h, int64_t w,
+                                int32_t plus_one, uint8_t* out, hypel_stream_t stream);
+int hypel_shadow_correct_f32(const void* src, int32_t dtype, int64_t h, int64_t w, int32_t bands, int64_t sy, int64_t sx,
+                             int64_t sb, const uint8_t* map, const float* r_minus_1, float* out, hypel_stream_t stream);
+
 /* ---- tensor summaries (tf.summary.histogram of the model variables; csrc/summary.hip) -------------------------------
  * hypel_tensor_summary_f32 summarises n_segs float32 tensors that are segments of ONE device buffer, where they live:
  * segment s is base[table[2s] ... table[2s] + table[2s + 1]) (int64 element offset >= 0 and size >= 0, any alignment,
