@@ -458,6 +458,7 @@ extern "C" int hypel_augment_patches_f32(const float* x, const int64_t* idx, int
                                          const float* delta, float* out, hypel_stream_t stream) {
     HYPEL_REQUIRE(x && out && x != out && n > 0 && p > 0 && c > 0, "hypel_augment_patches_f32");
     HYPEL_REQUIRE(!shadow_pick || shadow_ratio || shadow_alt, "hypel_augment_patches_f32");
+    HYPEL_REQUIRE(!(shadow_ratio && shadow_alt), "hypel_augment_patches_f32");  // one shadow operator per call
     const int block = c >= 192 ? 256 : (c >= 96 ? 128 : 64);
     hipLaunchKernelGGL(augment_patches_kernel, dim3(hypel_grid_1d(n * p * p, 1, 256 * 32)), dim3(block), 0, ST, x, idx,
                        n, p, c, rot_k, shadow_pick, shadow_ratio, shadow_alt, flip_lr, flip_ud, delta, out);

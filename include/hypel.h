@@ -373,7 +373,14 @@ int hypel_dropout_mask(float* mask, int64_t count, float keep_prob, uint64_t see
 int hypel_step_inc(uint64_t* step_dev, hypel_stream_t stream);
 
 /* ---- evaluation (common_nn_ops.py:243-277): pred[i] = argmax logits[i] (first max, as tf.argmax);
- * confusion[label][pred] += 1 (int32 atomics). labels: int32 class ids. pred may be NULL. */
+ * confusion[label][pred] += 1 (int32 atomics; the table is not cleared, a second call accumulates). labels: int32 class
+ * ids; a row whose label lies outside [0, c) -- -1, c, the raster's "unknown" 255 -- is not counted (its pred is still
+ * written).  pred may be NULL; confusion or labels NULL -> nothing is counted.
+ * The argmax of hypel_argmax_confusion and hypel_argmax_scatter is one left-to-right pass that starts at column 0 and
+ * moves on `logits[i][j] > best` (strict): of equal maxima (+0 and -0 are equal) the first wins; a NaN never displaces a
+ * value, and a NaN in column 0 is never displaced -- [1, NaN, 3] gives 2, [NaN, 5] gives 0, an all-NaN row gives 0.  (Not
+ * numpy.argmax, where the first NaN wins.)  The label of a row with a NaN means nothing; the rule is fixed so that
+ * device and specification cannot differ on it. */
 int hypel_argmax_confusion(const float* logits, int64_t ld, int64_t n, int32_t c, const int32_t* labels,
                            int32_t* pred, int32_t* confusion, hypel_stream_t stream);
 
@@ -389,7 +396,9 @@ int hypel_argmax_confusion(const float* logits, int64_t ld, int64_t n, int32_t c
  * shadow_ratio[c] -- create_simple_shadow_struct, gan_utilities.py:17-27 -- or by taking the sample from
  * shadow_alt [n,p,p,c], the pre-computed generator output in batch order), flipped left/right and up/down when
  * flip_lr[s] / flip_ud[s], shifted by delta[s, c] (spectral augmentation).  Every selector may be NULL.  The random
- * decisions are drawn by the host iterator (seeded generator) and handed over as small device arrays.
+ * decisions are drawn by the host iterator (seeded generator) and handed over as small device arrays.  shadow_ratio
+ * and shadow_alt are two definitions of the same step: a call that gives both is refused (as is shadow_pick with
+ * neither), before anything is written.
  *
  * hypel_argmax_scatter replaces perform_prediction's per-sample Python loop (common_nn_ops.py:313-327):
  * raster[y * raster_w + x] = argmax(logits[i]) for points[i] = (x, y). */

@@ -60,6 +60,13 @@ def _mat(ref, ld, rows, cols, dtype=np.float32):
     return np.lib.stride_tricks.as_strided(a, shape=(rows, cols), strides=(ld * a.itemsize, a.itemsize))
 
 
+def _first_max(z):
+    """include/hypel.h, the argmax of hypel_argmax_confusion / hypel_argmax_scatter: the first of equal maxima; a NaN
+    never displaces a value and a NaN in column 0 is never displaced."""
+    best = np.argmax(np.where(np.isnan(z), -np.inf, z), axis=1)
+    return np.where(np.isnan(z[:, 0]), 0, best)
+
+
 def _act(v, code, alpha):
     if code == 1:
         return np.where(v > 0, v, v * alpha)
@@ -173,6 +180,8 @@ class EmuBackend:
         _arr(out_y)[: n * bands] = y.reshape(-1)
 
     def k_augment_patches_f32(self, x, idx, n, p, c, rot_k, pick, ratio, alt, flip_lr, flip_ud, delta, out):
+        assert pick is None or ratio is not None or alt is not None
+        assert ratio is None or alt is None, "shadow_ratio and shadow_alt: one shadow operator per call"
         ix = np.arange(n) if idx is None else _arr(idx, np.int64)[:n]
         xa = _arr(x)
         o = _arr(out)[: n * p * p * c].reshape(n, p, p, c)
@@ -201,7 +210,7 @@ class EmuBackend:
         z = _mat(logits, ld, n, c)
         pts = _arr(points, np.int32)[: 2 * n].reshape(n, 2)
         r = _arr(raster, np.uint8)
-        r[pts[:, 1].astype(np.int64) * raster_w + pts[:, 0]] = np.argmax(z, axis=1).astype(np.uint8)
+        r[pts[:, 1].astype(np.int64) * raster_w + pts[:, 0]] = _first_max(z).astype(np.uint8)
 
     def k_fill_f32(self, dst, count, value):
         _arr(dst)[:count] = value
@@ -637,7 +646,8 @@ class EmuBackend:
             step.t[step.off] += 1
 
     def k_sum_f32(self, x, count, scale, out, ws):
-        _arr(out)[0] = _arr(x)[:count].astype(np.float64).sum() * scale
+        import math
+        _arr(out)[0] = math.fsum(_arr(x)[:count].tolist()) * scale  # the exact sum: +v, -v pairs cancel to 0 in any order
 
     def k_adam_tf1(self, p, g, m, v, count, lr_t, b1, b2, eps):
         pv, gv, mv, vv = (_arr(t)[:count] for t in (p, g, m, v))
@@ -671,35 +681,36 @@ class EmuBackend:
         step_dev.t[step_dev.off] += 1
 
     def k_argmax_confusion(self, logits, ld, n, c, labels, pred, confusion):
-        z = _mat(logits, ld, n, c)
-        best = z.argmax(1)
+        best = _first_max(_mat(logits, ld, n, c))
         if pred is not None:
             _arr(pred, np.int32)[:n] = best
         if confusion is not None and labels is not None:
             lab = _arr(labels, np.int32)[:n]
             conf = _arr(confusion, np.int32)[: c * c].reshape(c, c)
-            np.add.at(conf, (lab, best), 1)
+            known = (lab >= 0) & (lab < c)  # a label outside [0, c) is not counted
+            np.add.at(conf, (lab[known], best[known]), 1)
 
-    def _lrn_s(self, xm, radius, bias, alpha):
-        c = xm.shape[1]
-        sq = xm * xm
-        cs = np.concatenate([np.zeros((xm.shape[0], 1)), np.cumsum(sq, 1)], 1)
-        lo = np.maximum(np.arange(c) - radius, 0)
-        hi = np.minimum(np.arange(c) + radius + 1, c)
-        return bias + alpha * (cs[:, hi] - cs[:, lo]), lo, hi
+    @staticmethod
+    def _lrn_window(t, radius):
+        """out[:, j] = sum of t[:, k] over |k - j| <= radius, term by term: a difference of prefix sums would lose a
+        small window behind one large entry"""
+        c = t.shape[1]
+        out = t.copy()
+        for d in range(1, min(int(radius), c - 1) + 1):
+            out[:, d:] += t[:, :-d]
+            out[:, :-d] += t[:, d:]
+        return out
 
     def k_lrn_fwd(self, x, ldx, rows, c, radius, bias, alpha, beta, y, ldy):
         xm = _mat(x, ldx, rows, c).astype(np.float64)
-        s, _, _ = self._lrn_s(xm, radius, bias, alpha)
+        s = bias + alpha * self._lrn_window(xm * xm, radius)
         _mat(y, ldy, rows, c)[...] = (xm * s ** (-beta)).astype(np.float32)
 
     def k_lrn_bwd(self, x, ldx, dy, lddy, rows, c, radius, bias, alpha, beta, dx, lddx, accumulate):
         xm = _mat(x, ldx, rows, c).astype(np.float64)
         g = _mat(dy, lddy, rows, c).astype(np.float64)
-        s, lo, hi = self._lrn_s(xm, radius, bias, alpha)
-        t = g * xm * s ** (-beta - 1)
-        ct = np.concatenate([np.zeros((rows, 1)), np.cumsum(t, 1)], 1)
-        res = g * s ** (-beta) - 2 * alpha * beta * xm * (ct[:, hi] - ct[:, lo])
+        s = bias + alpha * self._lrn_window(xm * xm, radius)
+        res = g * s ** (-beta) - 2 * alpha * beta * xm * self._lrn_window(g * xm * s ** (-beta - 1), radius)
         d = _mat(dx, lddx, rows, c)
         if accumulate:
             d += res.astype(np.float32)
