@@ -500,6 +500,7 @@ static int forest_model(const char* name, Model* m, const int32_t* tree_off, int
                         const hypel_forest_node_t* nodes, int32_t n_nodes, const double* leaf_value, int32_t n_leaves,
                         int32_t n_classes) {
     HYPEL_REQUIRE(tree_off && nodes && leaf_value, name);
+    HYPEL_REQUIRE(((uintptr_t)nodes & (sizeof(int4) - 1)) == 0, name);
     HYPEL_REQUIRE(n_trees > 0 && n_nodes >= n_trees && n_leaves > 0 && n_leaves <= n_nodes, name);
     HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, name);
     *m = Model{tree_off, reinterpret_cast<const int4*>(nodes), leaf_value, n_trees, n_nodes, n_classes};

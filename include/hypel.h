@@ -950,10 +950,13 @@ int hypel_tensor_summary_f32(const float* base, const int64_t* table, int32_t n_
  *   order, the r-th node that split gets left = node_base + 2r, right = left + 1 and the records (tree, start, nL,
  *   left), (tree, start + nL, count - nL, right) at next_active[2r], [2r + 1] (room for 2 * n_active records);
  *   counter[0] = 2 * (number of splits), which the host reads to size the next level, or -1 when a child's number
- *   would reach node_capacity (nothing is written past it).  split_ws: int32 [n_active].
- * Serving: a model is one array of hypel_forest_node_t over all trees -- tree t's root is node tree_off[t] (int32
- *   [n_trees]).  A node with left < 0 is a leaf and ends the walk at row -1 - left of leaf_value (fp64
- *   [n_leaves][n_classes]); otherwise the walk goes to node `left` when x[feature] <= threshold (float32 compare) and to
+ *   would reach node_capacity (nothing is written past it: such a node keeps left = right = -1 and gets no records,
+ *   the nodes that split before it keep theirs).  split_ws: int32 [n_active], left holding nL of a node that split
+ *   and 0 of a leaf.  No node array is touched outside the records of the active nodes, no record of score, best_bin,
+ *   valid or next_active outside the ones named here.
+ * Serving: a model is one array of hypel_forest_node_t over all trees, 16-byte aligned (a record is one load; another
+ *   alignment is refused) -- tree t's root is node tree_off[t] (int32 [n_trees]).  A node with left < 0 is a leaf and
+ *   ends the walk at row -1 - left of leaf_value (fp64 [n_leaves][n_classes]); otherwise the walk goes to node `left` when x[feature] <= threshold (float32 compare) and to
  *   `right` if not; child indices are absolute and greater than their parent's (the walk is also bounded by n_nodes
  *   steps).  Per row the leaf rows are summed in tree order in fp64, divided by n_trees, and the FIRST maximum wins.
  *   The serving kernels do NOT check a model on the device: tree_off, child indices, leaf rows and feature values (a

@@ -94,7 +94,7 @@ def _k_forest_split_apply(self, bins, ldn, y, weight, n, n_classes, order_in, or
                           max_features, f, score, best_bin, valid, edges, level, max_depth, node_base, node_capacity,
                           feature, thr_bin, threshold, left, right, node_tree, node_count, node_weight, value, split_ws,
                           next_active, counter):
-    assert 1 <= n_classes <= FOREST_MAX_CLASSES and 1 <= max_features <= f and n_active > 0
+    assert 1 <= n_classes <= FOREST_MAX_CLASSES and 1 <= max_features <= f and n_active > 0 and ldn >= n
     assert 0 <= max_depth <= FOREST_MAX_DEPTH and level >= 0 and 0 <= node_base <= node_capacity
     assert order_in.ptr() != order_out.ptr()
     b = _typed(bins, np.uint8, f * ldn).reshape(f, ldn)
@@ -166,6 +166,7 @@ def forest_means(read, tree_off, feature, threshold, left, right, leaf, leaf_val
 
 def _model(tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes):
     assert n_trees > 0 and n_nodes >= n_trees and 0 < n_leaves <= n_nodes and 1 <= n_classes <= FOREST_MAX_CLASSES
+    assert nodes.ptr() % FOREST_NODE_DTYPE.itemsize == 0
     rec = _typed(nodes, np.uint8, n_nodes * FOREST_NODE_DTYPE.itemsize).view(FOREST_NODE_DTYPE)
     l, r = rec["left"], rec["right"]
     lf = np.where(l < 0, -1 - l, -1)

@@ -1,0 +1,936 @@
+"""TEST INFRASTRUCTURE shared by tests/test_gpu_forest_kernels.py (the HIP kernels of csrc/forest.hip, through the C-ABI)
+and tests/test_forest_kernel_cases_emu.py (the numpy emulation, tests/emu_forest.py): case tables, operand windows and a
+brute-force reference of the six hypel_forest_* entry points.
+
+Reference.  `ref_*` below: plain Python written from include/hypel.h alone -- Python ints for the histograms, Python
+floats (IEEE double, one rounding per operation) for the score and the class fractions, per-node and per-row loops, a
+literal stable partition, a recursive walk with an np.float32 compare.  It shares no code with tests/emu_forest.py and does
+not import it.  Every reference takes the C-ABI's arguments with each pointer replaced by the flat array of the operand
+and writes into its outputs what the header says the entry point writes -- nothing else.
+
+Operands.  Every pointer argument is an `Op`: the operand's elements behind an odd number of sentinel elements (bytes
+0xA5) and in front of 64 more, row operands with ld > f, the bins with ldn > n, outputs filled with sentinels and larger
+than what the call may write (edges rows of columns >= f, node arrays past node_capacity, records past the last).
+(parity_util.Arena is a float32 window; the operands here are uint8, int32, float32, float64 and 16-byte records.)
+`launch` runs a call twice from fresh uploads, requires identical bytes of every operand of the two runs and intact
+guards; `settle` then compares every operand -- inputs too -- byte for byte with what the reference left in its copy.  So
+whatever the header does not say is written must still hold the sentinel.
+
+Everything these kernels write is an integer or a float64 whose roundings the header fixes one by one: every comparison is
+an equality of bytes and no tolerance appears in this file."""
+import bisect
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from hypelcnn_amd.backend import (FOREST_EDGE_ROWS, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH, FOREST_MAX_EDGES,
+                                  FOREST_NODE_DTYPE, HypelError, Ref)
+from hypelcnn_amd.classic.forest import scene_features
+
+E = FOREST_MAX_EDGES
+FILL = 0xA5
+TAIL = 64
+F32, I32, U8, F64 = np.float32, np.int32, np.uint8, np.float64
+FLT_MAX = np.finfo(F32).max
+REFUSED = (HypelError, AssertionError)  # the library returns nonzero (HipBackend raises), the emulation asserts
+
+
+def sent(dtype, size):
+    """`size` sentinel elements of `dtype`"""
+    return np.full(int(size) * np.dtype(dtype).itemsize, FILL, U8).view(dtype)
+
+
+class Op:
+    """One pointer argument: `a` (what the operand holds before the call, flat) at element offset `lead` of a
+    sentinel-filled allocation.  `got` is the operand after the call, `want` what the reference made of a copy."""
+
+    def __init__(self, name, a, lead=None):
+        a = np.ascontiguousarray(a).reshape(-1)
+        assert a.dtype.fields is None
+        self.name, self.init = name, a.copy()
+        self.lead = (3 if a.itemsize == 8 else 7) if lead is None else lead
+        self.buf = sent(a.dtype, self.lead + a.size + TAIL)
+        self.buf[self.lead:self.lead + a.size] = a
+        self.want = a.copy()
+        self.got = None
+
+
+def node_op(name, records):
+    """hypel_forest_node_t records as bytes, three records into the allocation: an odd record offset at the 16-byte
+    alignment of the record"""
+    return Op(name, np.ascontiguousarray(records).view(U8), lead=48)
+
+
+def same_bytes(name, got, want):
+    got, want = np.ascontiguousarray(got).reshape(-1), np.ascontiguousarray(want).reshape(-1)
+    assert got.dtype == want.dtype and got.size == want.size, name
+    if got.tobytes() != want.tobytes():
+        bad = np.unique(np.flatnonzero(got.view(U8) != want.view(U8)) // got.itemsize)
+        raise AssertionError(f"{name}: {bad.size} of {got.size} elements differ; first at element {int(bad[0])}: "
+                             f"{got[bad[0]]!r} instead of {want[bad[0]]!r}")
+
+
+def launch(be, kernel, *args, refused=False):
+    """the call twice, each from a fresh upload: the same bytes both times, guards intact; `got` of every Op.  A backend
+    that carries a list `forest_launches` gets (kernel, args) appended to it."""
+    ops = {id(a): a for a in args if isinstance(a, Op)}
+    runs = []
+    for _ in range(2):
+        tens = {k: be.upload(o.buf) for k, o in ops.items()}
+        cargs = [Ref(tens[id(a)], a.lead) if isinstance(a, Op) else a for a in args]
+        if refused:
+            with pytest.raises(REFUSED):
+                be.call(kernel, *cargs)
+        else:
+            be.call(kernel, *cargs)
+        be.synchronize()
+        runs.append({k: t.cpu().numpy().copy() for k, t in tens.items()})
+    for k, o in ops.items():
+        same_bytes(f"{kernel} {o.name}: second run against the first", runs[1][k], runs[0][k])
+        flat = runs[0][k]
+        guard = np.ones(flat.size, bool)
+        guard[o.lead:o.lead + o.init.size] = False
+        bad = np.flatnonzero(guard & (flat.view(U8).reshape(flat.size, -1) != FILL).any(1))
+        assert bad.size == 0, f"{kernel} {o.name}: written at element {int(bad[0]) - o.lead} of its {o.init.size}"
+        o.got = flat[o.lead:o.lead + o.init.size].copy()
+    if getattr(be, "forest_launches", None) is not None:
+        be.forest_launches.append((kernel, args))
+
+
+def settle(kernel, *args, tag=""):
+    """every operand of the call, inputs included, holds the bytes the reference left in `want`"""
+    for a in args:
+        if isinstance(a, Op):
+            same_bytes(f"{kernel} {a.name} {tag}", a.got, a.want)
+
+
+def run(be, kernel, ref, *args, tag="", **kw):
+    """launch, apply the reference to the `want` copies, compare"""
+    launch(be, kernel, *args)
+    ref(*[a.want if isinstance(a, Op) else a for a in args], **kw)
+    settle(kernel, *args, tag=tag)
+
+
+# =============================================================================================== the reference (hypel.h)
+def ref_bin_edges(x, ld, n, f, perm, n_bins, edges, n_edges):
+    n_s = min(n, FOREST_EDGE_ROWS)
+    rows = [int(perm[i]) for i in range(n_s)]
+    assert len(set(rows)) == n_s and min(rows) >= 0 and max(rows) < n
+    for c in range(f):
+        vals = sorted(float(x[r * ld + c]) + 0.0 for r in rows)
+        out = []
+        for j in range(1, n_bins):
+            v = vals[j * n_s // n_bins]
+            if v == vals[-1] or (out and v == out[-1]):
+                continue
+            out.append(v)
+        assert out == sorted(out) and len(out) <= E
+        n_edges[c] = len(out)
+        for j in range(E):
+            edges[c * E + j] = out[j] if j < len(out) else np.inf
+
+
+def ref_bin_u8(x, ld, n, f, edges, n_edges, bins, ldn):
+    for c in range(f):
+        e = [float(v) for v in edges[c * E:c * E + int(n_edges[c])]]
+        for i in range(n):
+            bins[c * ldn + i] = bisect.bisect_left(e, float(x[i * ld + c]))  # the number of edges < x
+
+
+def boundary_scores(hist, n_classes):
+    """[(t, sl, nl, sr, nr)] of every boundary t in 0..254 with weight on both sides"""
+    total = [sum(hist[b][k] for b in range(E + 1)) for k in range(n_classes)]
+    left, out = [0] * n_classes, []
+    for t in range(E):
+        left = [l + h for l, h in zip(left, hist[t])]
+        nl, nr = sum(left), sum(total) - sum(left)
+        if nl > 0 and nr > 0:
+            out.append((t, sum(l * l for l in left), nl, sum((a - l) * (a - l) for a, l in zip(total, left)), nr))
+    return out
+
+
+def ref_split_hist(bins, ldn, y, weight, n, n_classes, order, active, n_active, cand, max_features, f, score, best_bin,
+                   valid, exact_guard=False):
+    for a in range(n_active):
+        tree, start, count = (int(v) for v in active[4 * a:4 * a + 3])
+        for s in range(max_features):
+            at = a * max_features + s
+            c = int(cand[at])
+            score[at], best_bin[at], valid[at] = 0.0, -1, 0
+            if count < 2:
+                continue
+            hist = [[0] * n_classes for _ in range(E + 1)]
+            for i in range(count):
+                r = int(order[start + i])
+                hist[int(bins[c * ldn + r])][int(y[r])] += int(weight[tree * n + r])
+            best = None
+            bounds = boundary_scores(hist, n_classes)
+            for t, sl, nl, sr, nr in bounds:
+                sc = float(sl) / float(nl) + float(sr) / float(nr)
+                if best is None or sc > best[0]:  # scanned in bin order: the lowest bin of the largest score
+                    best = (sc, t)
+            if best is None:
+                continue
+            score[at], best_bin[at], valid[at] = best[0], best[1], 1
+            if exact_guard:  # the float64 roundings may merge scores, they must not reorder them
+                exact = max(bounds, key=lambda b: (Fraction(b[1], b[2]) + Fraction(b[3], b[4]), -b[0]))
+                if exact[0] != best[1]:
+                    assert float(exact[1]) / float(exact[2]) + float(exact[3]) / float(exact[4]) == best[0], (a, s)
+
+
+def ref_split_apply(bins, ldn, y, weight, n, n_classes, order_in, order_out, active, n_active, cand, max_features, f,
+                    score, best_bin, valid, edges, level, max_depth, node_base, node_capacity, feature, thr_bin, threshold,
+                    left, right, node_tree, node_count, node_weight, value, split_ws, next_active, counter):
+    r, overflow = 0, False
+    for a in range(n_active):
+        tree, start, count, node = (int(v) for v in active[4 * a:4 * a + 4])
+        rows = [int(order_in[start + i]) for i in range(count)]
+        cls = [0] * n_classes
+        for s in rows:
+            cls[int(y[s])] += int(weight[tree * n + s])
+        pick = None
+        for s in range(max_features):
+            at = a * max_features + s
+            if valid[at]:
+                key = (-float(score[at]), int(cand[at]), int(best_bin[at]))
+                if pick is None or key < pick:
+                    pick = key
+        leaf = count < 2 or sum(1 for v in cls if v > 0) < 2 or pick is None or level >= max_depth
+        node_tree[node], node_count[node], node_weight[node] = tree, count, sum(cls)
+        for k in range(n_classes):
+            value[node * n_classes + k] = float(cls[k]) / float(sum(cls))
+        left[node] = right[node] = -1
+        if leaf:
+            feature[node], thr_bin[node], threshold[node], split_ws[a] = -1, -1, 0.0, 0
+            continue
+        c, t = pick[1], pick[2]
+        feature[node], thr_bin[node], threshold[node] = c, t, edges[c * E + t]
+        at = start
+        for side in (True, False):  # the stable partition, literally
+            for s in rows:
+                if (int(bins[c * ldn + s]) <= t) == side:
+                    order_out[at] = s
+                    at += 1
+            if side:
+                n_left = at - start
+        split_ws[a] = n_left
+        lid = node_base + 2 * r
+        if lid + 1 < node_capacity:
+            left[node], right[node] = lid, lid + 1
+            next_active[8 * r:8 * r + 8] = (tree, start, n_left, lid, tree, start + n_left, count - n_left, lid + 1)
+        else:
+            overflow = True
+        r += 1
+    counter[0] = -1 if overflow else 2 * r
+
+
+def walk(nodes, at, read, depth=0):
+    """(the leaf row a value source `read(feature field)` ends in from node `at`, the inner nodes on the way)"""
+    feature, threshold, lo, hi = nodes[at]
+    if lo < 0:
+        return -1 - int(lo), depth
+    return walk(nodes, int(lo) if np.float32(read(int(feature))) <= np.float32(threshold) else int(hi), read, depth + 1)
+
+
+def vote(nodes, tree_off, n_trees, leaf_value, n_classes, read):
+    acc, deepest = [0.0] * n_classes, 0
+    for t in range(n_trees):  # tree order, one fp64 addition per tree and class
+        row, depth = walk(nodes, int(tree_off[t]), read)
+        deepest = max(deepest, depth)
+        for k in range(n_classes):
+            acc[k] = acc[k] + float(leaf_value[row * n_classes + k])
+    mean = [v / float(n_trees) for v in acc]
+    return mean, min(k for k in range(n_classes) if mean[k] == max(mean)), deepest
+
+
+def ref_predict_rows(x, ld, n, f, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes, class_labels,
+                     points, out, raster_w, proba, depths=None):
+    """depths: a list that receives, per row, the length of its longest walk"""
+    rec = nodes.view(FOREST_NODE_DTYPE)[:n_nodes]
+    for i in range(n):
+        mean, win, deepest = vote(rec, tree_off, n_trees, leaf_value, n_classes, lambda c: x[i * ld + c])
+        if depths is not None:
+            depths.append(deepest)
+        label = win if class_labels is None else class_labels[win]
+        out[i if points is None else int(points[2 * i + 1]) * raster_w + int(points[2 * i])] = label
+        if proba is not None:
+            proba[i * n_classes:(i + 1) * n_classes] = mean
+
+
+def ref_scene_patches(casi, lidar, hp, wp, cc, cl, points, n, p):
+    """the p x p window of every point as a row of p * p * (cc + cl) features, pixel after pixel, casi bands first"""
+    rows = np.zeros((n, p * p * (cc + cl)), F32)
+    for i in range(n):
+        x0, y0 = int(points[2 * i]), int(points[2 * i + 1])
+        assert 0 <= x0 and x0 + p <= wp and 0 <= y0 and y0 + p <= hp
+        for py in range(p):
+            for px in range(p):
+                at = ((y0 + py) * wp + x0 + px)
+                pix = list(casi[at * cc:(at + 1) * cc]) + ([] if cl == 0 else list(lidar[at * cl:(at + 1) * cl]))
+                rows[i, (py * p + px) * (cc + cl):(py * p + px + 1) * (cc + cl)] = pix
+    return rows
+
+
+# ================================================================================================= 1. bin_edges + bin_u8
+BIN_KINDS = ("equal", "two", "dups", "increasing", "wide")
+BIN_CASES = [(1, 2), (2, 3), (3, 256), (255, 256), (1023, 255), (1024, 256), (1025, 3), (16384, 256), (16385, 256)]
+PROBE_N = [1, 255, 256, 257, 513]
+
+
+def bin_columns(n, rng):
+    """[n][5]: all equal; two values; heavy duplicates with both zeros; strictly increasing (shuffled); negatives,
+    denormals and +-FLT_MAX"""
+    x = np.zeros((n, len(BIN_KINDS)), F32)
+    x[:, 0] = 3.25
+    x[:, 1] = rng.choice(np.array([-7.5, 2.0], F32), n)
+    x[:, 2] = rng.choice(np.array([-1.5, -0.0, 0.0, 0.5, 2.0], F32), n)
+    x[:, 3] = rng.permutation(n).astype(F32) * F32(0.25) - F32(100.0)
+    special = np.array([-FLT_MAX, FLT_MAX, 1e-45, -1e-45, 3e-39, -3e-39, 1.17549435e-38, -0.0, 0.0], F32)
+    x[:, 4] = np.where(rng.random(n) < 0.3, rng.choice(special, n), (rng.standard_normal(n) * 1e3).astype(F32))
+    if n > 1:
+        x[:2, 1] = (-7.5, 2.0)
+        x[:2, 2] = (-0.0, 0.0)
+    return x
+
+
+def padded_rows(x, ld):
+    out = sent(F32, x.shape[0] * ld).reshape(x.shape[0], ld)
+    out[:, :x.shape[1]] = x
+    return out
+
+
+def check_bin_property(x, ne, edges, bins, tag):
+    """from raw values only: bin <= t  <=>  x <= edges[c][t], every column, every t < n_edges[c], every row"""
+    for c in range(x.shape[1]):
+        e = edges[c * E:c * E + int(ne[c])]
+        lhs = bins[c][:, None] <= np.arange(len(e))[None, :]
+        rhs = x[:, c][:, None] <= e[None, :]
+        assert np.array_equal(lhs, rhs), f"bin <= t <=> x <= edge fails in column {c} {tag}"
+
+
+def run_bins(be, n, n_bins, k=0):
+    """the pair on one matrix, then hypel_forest_bin_u8 on probe rows built from the edges it was given: each edge, the
+    float32 on either side of it, a value below the first and above the last edge (n = the longest list, then one of
+    PROBE_N rows drawn evenly from it)"""
+    rng = np.random.default_rng(100 * n + n_bins)
+    x = bin_columns(n, rng)
+    f, ld, tag = x.shape[1], x.shape[1] + 3, f"n{n} bins{n_bins}"
+    perm = rng.permutation(n)
+    if n > FOREST_EDGE_ROWS:  # the subsample leaves out the row of the increasing column's maximum
+        top = int(np.argmax(x[:, 3]))
+        perm = np.concatenate([perm[perm != top], [top]])
+    xo, po = Op("x", padded_rows(x, ld)), Op("perm", perm[:min(n, FOREST_EDGE_ROWS)].astype(I32))
+    eo, no = Op("edges", sent(F32, (f + 1) * E)), Op("n_edges", sent(I32, f + 1))
+    run(be, "forest_bin_edges_f32", ref_bin_edges, xo, ld, n, f, po, n_bins, eo, no, tag=tag)
+    ne, edges = no.got[:f], eo.got[:f * E]
+    assert ne[0] == 0 and ne[1] <= 1 and ne.max() <= n_bins - 1
+    if n >= 1023 and n_bins >= 255:
+        assert ne[3] == n_bins - 1  # every edge exists: bin n_bins - 1 is reachable
+    matrices = [x]
+    lists = []
+    for c in range(f):
+        e = edges[c * E:c * E + int(ne[c])]
+        with np.errstate(over="ignore"):  # (beside +-FLT_MAX lies an infinity: dropped below)
+            v = np.concatenate([e, np.nextafter(e, F32(-np.inf)), np.nextafter(e, F32(np.inf)),
+                                [np.nextafter(e[0], F32(-np.inf)) if len(e) else F32(-1.0), x[:, c].max()]]).astype(F32)
+        lists.append(v[np.isfinite(v)])
+    m = max(len(v) for v in lists)
+    probe = np.stack([np.resize(v, m) for v in lists], 1)
+    matrices += [probe, probe[np.linspace(0, m - 1, PROBE_N[k % len(PROBE_N)]).astype(int)]]
+    for which, mat in enumerate(matrices):
+        rows = mat.shape[0]
+        ldn = rows + 5
+        args = (Op("x", padded_rows(mat, ld)), ld, rows, f, Op("edges", eo.got), Op("n_edges", no.got),
+                Op("bins", sent(U8, (f + 1) * ldn)), ldn)
+        run(be, "forest_bin_u8", ref_bin_u8, *args, tag=f"{tag} matrix {which}")
+        bins = args[6].got.reshape(f + 1, ldn)[:f, :rows]
+        check_bin_property(mat, ne, edges, bins, f"{tag} matrix {which}")
+        if which == 0 and n > FOREST_EDGE_ROWS:
+            assert bins[3].max() == ne[3] == E  # the left-out maximum lies above every edge: bin 255
+    return ne
+
+
+# ======================================================================================================= 2. split_hist
+def scenario(rng, counts, n_classes, f=5, n_trees=3, w_max=9, zero=0.2, bins=None):
+    """Rows, labels, weights and node segments: node a belongs to tree a % n_trees, so the segments of the trees
+    interleave in `order`, and each segment lists its (distinct) rows in random order.  Weight rows differ per tree, a
+    fraction `zero` of the weights is 0, the first two rows of a segment have weight > 0 and, with more than one class,
+    different labels."""
+    n = max(max(counts) + 3, 16)
+    d = dict(n=n, f=f, ldn=n + 5, C=n_classes, n_active=len(counts))
+    b = rng.integers(0, 256, (f, n)) if bins is None else bins(rng, f, n)
+    d["bins"] = sent(U8, (f + 1) * d["ldn"]).reshape(f + 1, d["ldn"])
+    d["bins"][:f, :n] = b
+    d["y"] = rng.integers(0, n_classes, n).astype(I32)
+    w = rng.integers(1, w_max + 1, (n_trees, n))
+    w[rng.random((n_trees, n)) < zero] = 0
+    segs, active, at = [], [], 3
+    for a, count in enumerate(counts):
+        rows = rng.permutation(n)[:count]
+        w[a % n_trees, rows[:2]] = np.maximum(w[a % n_trees, rows[:2]], 1)
+        segs.append(rows)
+        active.append((a % n_trees, at, count, 0))
+        at += count + (a % 2)  # a gap after every other segment
+    d["weight"] = w.astype(I32)
+    order = sent(I32, at + 3)
+    for rows, (_, start, count, _) in zip(segs, active):
+        order[start:start + count] = rows
+        if n_classes > 1 and count > 1:
+            d["y"][rows[0]], d["y"][rows[1]] = 0, 1
+    d["order"], d["active"], d["segs"] = order, np.array(active, I32), segs
+    return d
+
+
+def draw_cand(rng, n_active, mf, f):
+    return np.stack([rng.permutation(f)[:mf] for _ in range(n_active)]).astype(I32)
+
+
+def hist_ops(d, cand):
+    mf = cand.shape[1]
+    rec = d["n_active"] * mf + 3  # three records past the last stay untouched
+    return (Op("bins", d["bins"]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"],
+            Op("order", d["order"]), Op("active", d["active"]), d["n_active"], Op("cand", cand), mf, d["f"],
+            Op("score", sent(F64, rec)), Op("best_bin", sent(I32, rec)), Op("valid", sent(I32, rec)))
+
+
+SEG_COUNTS = [1, 2, 255, 256, 257, 1000]
+
+
+def special_bins(rng, f, n):
+    """column 0: one bin (no boundary is valid); 1: bins 0 and 255 only; 2: four bins, mirrored below; 3, 4: random"""
+    b = rng.integers(0, 256, (f, n))
+    b[0] = 77
+    b[1] = rng.choice([0, 255], n)
+    b[2] = rng.choice([10, 20, 30, 40], n)
+    return b
+
+
+def mirror(d):
+    """node 0, column 2: bins (10, 20, 30, 40) hold (5 of class 0, 3 of class 1, 3 of class 1, 5 of class 0), weight 1
+    each: the boundaries 10 and 30 score (25/5 + 61/11) and (61/11 + 25/5), 20 scores 8.5 -- the lower bin wins"""
+    rows = d["segs"][0]
+    assert len(rows) == 16
+    d["bins"][2, rows] = [10] * 5 + [20] * 3 + [30] * 3 + [40] * 5
+    d["y"][rows] = [0] * 5 + [1] * 6 + [0] * 5
+    d["weight"][0, rows] = 1
+
+
+#                 name            counts                C   mf  weights (w_max, zero fraction)   bins       guard
+HIST_CASES = {
+    "c2_mf1":     (SEG_COUNTS, 2, 1, (9, 0.2), None, True),
+    "c15_mf3":    (SEG_COUNTS, 15, 3, (9, 0.2), None, False),
+    "c32_mf5":    (SEG_COUNTS, 32, 5, (9, 0.2), None, False),
+    "c1":         ([2, 300, 40], 1, 3, (9, 0.2), None, False),
+    "one_node":   ([97], 2, 3, (9, 0.3), None, True),
+    "300_nodes":  (None, 2, 3, (9, 0.2), None, False),  # counts 1 .. 40, drawn
+    "heavy_c2":   ([1000, 999, 1000, 513, 1000], 2, 5, (1 << 15, 0.05), None, True),
+    "heavy_c32":  ([1000, 1000, 700, 1000, 1000], 32, 3, (1 << 15, 0.05), None, True),
+    "special":    ([16, 300, 2, 64, 65], 2, 5, (9, 0.2), special_bins, True),
+}
+
+
+def hist_scenario(name):
+    counts, C, mf, (w_max, zero), bins, guard = HIST_CASES[name]
+    rng = np.random.default_rng(sum(name.encode()))
+    if counts is None:
+        counts = [int(v) for v in rng.integers(1, 41, 300)]
+    d = scenario(rng, counts, C, w_max=w_max, zero=zero, bins=bins)
+    if w_max > 9:  # totals near 2^25: almost every weight in the upper half of the range
+        w = d["weight"]
+        w[w > 0] = np.maximum(w[w > 0], 1 << 14)
+    if name == "special":
+        mirror(d)
+    return d, draw_cand(rng, len(counts), mf, d["f"]), guard
+
+
+def run_hist(be, name):
+    d, cand, guard = hist_scenario(name)
+    args = hist_ops(d, cand)
+    run(be, "forest_split_hist", ref_split_hist, *args, tag=name, exact_guard=guard)
+    best, valid = args[13].want, args[14].want
+    if name.startswith("heavy"):
+        seg = d["segs"][0]
+        per_class = np.bincount(d["y"][seg], d["weight"][0, seg], d["C"]).max()
+        assert d["weight"][0, seg].sum() > 1 << 24 and per_class > 1 << 16  # squares past int32, totals near 2^25
+    if name == "special":
+        for s, c in enumerate(cand[0]):
+            assert valid[s] == (c != 0) and (c != 1 or best[s] == 0) and (c != 2 or best[s] == 10), (s, c)
+    return d, cand, args
+
+
+# ====================================================================================== 3. split_apply with compaction
+def node_ops(d, cap, n_active):
+    rows = cap + 4  # four node records past node_capacity stay untouched
+    return dict(feature=Op("feature", sent(I32, rows)), thr_bin=Op("thr_bin", sent(I32, rows)),
+                threshold=Op("threshold", sent(F32, rows)), left=Op("left", sent(I32, rows)),
+                right=Op("right", sent(I32, rows)), node_tree=Op("node_tree", sent(I32, rows)),
+                node_count=Op("node_count", sent(I32, rows)), node_weight=Op("node_weight", sent(I32, rows)),
+                value=Op("value", sent(F64, rows * d["C"])), split_ws=Op("split_ws", sent(I32, n_active + 3)),
+                next_active=Op("next_active", sent(I32, 8 * n_active + 8)), counter=Op("counter", sent(I32, 3)))
+
+
+def edges_table(rng, f):
+    return np.sort((rng.standard_normal((f, E)) * 50).astype(F32), 1)
+
+
+def run_apply(be, d, cand, score, best_bin, valid, level, max_depth, node_base, short=0, tag=""):
+    """One launch; node_capacity = node_base + 2 * (the nodes the reference splits) - short.  Returns the Ops by name."""
+    na, mf = d["n_active"], cand.shape[1]
+    rng = np.random.default_rng(na + mf)
+    d["active"][:, 3] = node_base - na + rng.permutation(na)  # the nodes of this level, not in active-node order
+    order_out = Op("order_out", sent(I32, d["order"].size))
+
+    def args(cap, o):
+        return (Op("bins", d["bins"]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"],
+                Op("order_in", d["order"]), order_out, Op("active", d["active"]), na, Op("cand", cand), mf, d["f"],
+                Op("score", score), Op("best_bin", best_bin), Op("valid", valid), Op("edges", d["edges"]), level,
+                max_depth, node_base, cap, *o.values())
+
+    dry = node_ops(d, node_base + 2 * na, na)
+    ref_split_apply(*[a.want if isinstance(a, Op) else a for a in args(node_base + 2 * na, dry)])
+    order_out.want = order_out.init.copy()
+    cap = node_base + int(dry["counter"].want[0]) - short
+    o = node_ops(d, cap, na)
+    a = args(cap, o)
+    run(be, "forest_split_apply", ref_split_apply, *a, tag=tag)
+    o["order_out"], o["cap"], o["splits"] = order_out, cap, int(dry["counter"].want[0]) // 2
+    return o
+
+
+PART_COUNTS = [2, 63, 64, 65, 255, 256, 257, 513, 1000]
+
+
+def disjoint_scenario(rng, counts, n_classes, f, **kw):
+    """scenario() whose segments share no row (a row's bin can then be set per node)"""
+    d = scenario(rng, [sum(counts)] + [1] * (len(counts) - 1), n_classes, f=f, **kw)
+    rows, at, start, segs, active = d["segs"][0], 0, 3, [], []
+    order = sent(I32, sum(counts) + 2 * len(counts) + 6)
+    for a, count in enumerate(counts):
+        seg = rows[at:at + count]
+        segs.append(seg)
+        active.append((a % 3, start, count, 0))
+        order[start:start + count] = seg
+        if count > 1:
+            d["y"][seg[0]], d["y"][seg[1]] = 0, min(1, n_classes - 1)
+        at, start = at + count, start + count + (a % 2)
+    for a, seg in enumerate(segs):
+        d["weight"][a % 3, seg[:2]] = np.maximum(d["weight"][a % 3, seg[:2]], 1)
+    d["order"], d["active"], d["segs"], d["n_active"] = order, np.array(active, I32), segs, len(counts)
+    return d
+
+
+def run_partition(be):
+    rng = np.random.default_rng(31)
+    counts = [c for c in PART_COUNTS for _ in range(3)]
+    d = disjoint_scenario(rng, counts, 3, 2, zero=0.1)
+    d["edges"] = edges_table(rng, 2)
+    na = len(counts)
+    cand = np.stack([rng.permutation(2) for _ in range(na)]).astype(I32)
+    score, best, valid = np.zeros(na * 2), np.full(na * 2, -1, I32), np.zeros(na * 2, I32)
+    want_left = []
+    for a, rows in enumerate(d["segs"]):
+        count = len(rows)
+        n_left = (1, count - 1, int(rng.integers(1, count)))[a % 3]
+        t = int(rng.integers(0, 255))
+        go = rng.permutation(count) < n_left
+        d["bins"][int(cand[a, a % 2]), rows] = np.where(go, rng.integers(0, t + 1, count), rng.integers(t + 1, 256, count))
+        score[a * 2 + a % 2], best[a * 2 + a % 2], valid[a * 2 + a % 2] = 1.0 + a, t, 1
+        want_left.append(n_left)
+    o = run_apply(be, d, cand, score, best, valid, 2, 9, 100, tag="partition")
+    assert list(o["split_ws"].want[:na]) == want_left and o["splits"] == na
+    for (_, start, count, _), rows in zip(d["active"], d["segs"]):
+        assert sorted(o["order_out"].want[start:start + count]) == sorted(rows)
+
+
+LEAF_LEVELS = [(3, 4), (4, 4), (0, 0), (5, 4)]
+
+
+def run_leaf_reasons(be, level, max_depth):
+    """Six nodes: 0 one row; 1 two classes of which one has weight 0 only; 2 no valid slot; 3, 5 split; 4 a valid slot
+    whose score is smaller than an invalid slot's.  At level < max_depth nodes 3, 4 and 5 split; at level >= max_depth
+    none does and the level is the only reason for 3, 4 and 5."""
+    rng = np.random.default_rng(7)
+    d = disjoint_scenario(rng, [1, 40, 40, 40, 40, 2], 2, 3)
+    d["edges"] = edges_table(rng, 3)
+    seg = d["segs"][1]
+    d["weight"][1, seg] = np.where(d["y"][seg] == 1, 0, 5)
+    assert (d["y"][seg] == 1).any() and (d["y"][seg] == 0).any()
+    cand = draw_cand(rng, 6, 2, 3)
+    score, best, valid = rng.random(12) + 1, np.full(12, 100, I32), np.ones(12, I32)
+    valid[4:6] = 0  # node 2
+    valid[8], score[8], score[9] = 0, 99.0, 0.5  # node 4: the invalid slot's score is ignored
+    for a in (3, 4, 5):
+        rows = d["segs"][a]
+        d["bins"][:3, rows[0]], d["bins"][:3, rows[1]] = 100, 101
+    o = run_apply(be, d, cand, score, best, valid, level, max_depth, 20, tag=f"level {level} of {max_depth}")
+    assert o["splits"] == (3 if level < max_depth else 0)
+    nodes = d["active"][:, 3]
+    assert (o["feature"].want[nodes[:3]] == -1).all() and o["feature"].want[nodes[4]] == (cand[4, 1] if level < max_depth else -1)
+
+
+def run_slot_ties(be):
+    """mf = 3; per node (columns, scores, bins, valid) -> the column that must win:
+    0: equal scores, the lower column in a later slot;  1: a three-way tie at the top score, the lowest column last;
+    2: equal score -- the lower column wins although its bin is the higher;  3: the best score in the last slot and the
+    highest column;  4: an invalid slot with the best score and the lowest column"""
+    table = [((4, 2, 0), (5.0, 5.0, 4.0), (1, 9, 0), (1, 1, 1), 2),
+             ((3, 1, 0), (7.0, 7.0, 7.0), (0, 9, 200), (1, 1, 1), 0),
+             ((4, 1, 2), (6.5, 6.5, 1.0), (3, 250, 3), (1, 1, 1), 1),
+             ((0, 1, 4), (1.0, 2.0, 3.0), (5, 5, 5), (1, 1, 1), 4),
+             ((0, 3, 2), (9.0, 5.0, 5.0), (7, 8, 6), (0, 1, 1), 2)]
+    rng = np.random.default_rng(11)
+    d = disjoint_scenario(rng, [50] * len(table), 2, 5)
+    d["edges"] = edges_table(rng, 5)
+    for rows in d["segs"]:  # every boundary of the table has rows on both sides
+        d["bins"][:5, rows[0]], d["bins"][:5, rows[1]] = 0, 255
+    cand = np.array([t[0] for t in table], I32)
+    score = np.array([t[1] for t in table], F64).reshape(-1)
+    best, valid = (np.array([t[k] for t in table], I32).reshape(-1) for k in (2, 3))
+    o = run_apply(be, d, cand, score, best, valid, 0, 64, 5, tag="slot ties")
+    assert [int(o["feature"].want[node]) for node in d["active"][:, 3]] == [t[4] for t in table]
+
+
+COMPACT_N = [1, 255, 256, 257, 600]
+COMPACT_PATTERNS = ["all", "none", "alternating", "last"]
+
+
+def run_compaction(be, n_active, pattern, short=0):
+    """n_active nodes of two rows; a node of the pattern splits (bins 0 and 1, boundary 0), the others have no valid
+    slot.  short = 1: node_capacity is one too small -- the last child has no room, counter = -1"""
+    rng = np.random.default_rng(n_active)
+    d = disjoint_scenario(rng, [2] * n_active, 2, 1, zero=0)
+    d["edges"] = edges_table(rng, 1)
+    split = {"all": np.ones(n_active, bool), "none": np.zeros(n_active, bool),
+             "alternating": np.arange(n_active) % 2 == 0, "last": np.arange(n_active) == n_active - 1}[pattern]
+    for rows in d["segs"]:
+        d["bins"][0, rows] = rng.permutation(2)
+    cand = np.zeros((n_active, 1), I32)
+    score, best, valid = np.where(split, 1.5, 0.0), np.where(split, 0, -1).astype(I32), split.astype(I32)
+    tag = f"compaction {n_active} {pattern} short {short}"
+    o = run_apply(be, d, cand, score, best, valid, 1, 8, 1000, short=short, tag=tag)
+    assert o["splits"] == split.sum()
+    if short and split.any():
+        last = d["active"][np.flatnonzero(split)[-1], 3]
+        assert o["counter"].want[0] == -1 and o["left"].want[last] == -1 and o["right"].want[last] == -1
+        written = 8 * (o["splits"] - 1)
+        assert (o["next_active"].want[written:].view(U8) == FILL).all() and (o["next_active"].want[:written] >= 0).all()
+    else:
+        assert o["counter"].want[0] == 2 * split.sum()
+
+
+def run_hist_then_apply(be, name):
+    """the score tables of a split_hist case (zero weights, 2^15 weights) through split_apply"""
+    d, cand, args = run_hist(be, name)
+    rec = d["n_active"] * cand.shape[1]
+    d["edges"] = edges_table(np.random.default_rng(5), d["f"])
+    o = run_apply(be, d, cand, args[12].got[:rec], args[13].got[:rec], args[14].got[:rec], 0, 64, 10, tag=name)
+    assert o["splits"] > 0
+
+
+# ====================================================================================================== 4. predict_rows
+GRID = np.array([-2.5, -1.0, -0.0, 0.0, 0.75, 1e-40, 3.0, 1e30], F32)
+LEAF_PARTS = np.array([0.1, 0.2, 0.3, 0.7, 1.0 / 3.0, 0.05, 0.0, 0.15])
+
+
+class ModelBuilder:
+    """Node records over all trees and the leaf table.  Thresholds come from GRID, the rows of a case from GRID and the
+    float32 on either side of each of its values: a row value equals a threshold, or lies one ulp beside it, all the time.
+    The chains alone test the last column against thresholds of their own (chain_value)."""
+
+    def __init__(self, rng, f, n_classes):
+        self.rng, self.f, self.C = rng, f, n_classes
+        self.nodes, self.leaves, self.tree_off = [], [], []
+
+    def leaf(self, row=None):
+        if row is None:
+            row = self.rng.choice(LEAF_PARTS, self.C)
+        self.leaves.append(np.asarray(row, F64))
+        self.nodes.append((0, 0.0, -len(self.leaves), -1))  # left = -1 - (the leaf's row)
+        return len(self.nodes) - 1
+
+    def inner(self):
+        self.nodes.append(None)
+        return len(self.nodes) - 1
+
+    def fill(self, at, left, right):
+        assert left > at and right > at
+        self.nodes[at] = (int(self.rng.integers(0, self.f)), self.rng.choice(GRID), left, right)
+
+    def stump(self, row=None):
+        self.tree_off.append(len(self.nodes))
+        self.leaf(row)
+
+    def chain(self, depth=FOREST_MAX_DEPTH):
+        """`depth` inner nodes in a row, all on the last column; a leaf hangs on alternating sides: level k goes on to
+        the left (x <= depth - k) when k is even and to the right (x > k - depth) when k is odd, so a value in (-1, 2]
+        reaches the chain's last leaf -- the last node of the tree -- and chain_value(k) leaves at level k"""
+        self.tree_off.append(len(self.nodes))
+        for k in range(depth):
+            at = self.inner()
+            leaf = self.leaf()
+            nxt = len(self.nodes) if k + 1 < depth else self.leaf()
+            self.nodes[at] = (self.f - 1, F32(k - depth if k % 2 else depth - k), *((leaf, nxt) if k % 2 else (nxt, leaf)))
+
+    def balanced(self, depth=3):
+        self.tree_off.append(len(self.nodes))
+
+        def grow(level):
+            if level == depth:
+                return self.leaf()
+            at = self.inner()
+            lo = grow(level + 1)
+            self.fill(at, lo, grow(level + 1))
+            return at
+        grow(0)
+
+    def arrays(self):
+        rec = np.zeros(len(self.nodes), FOREST_NODE_DTYPE)
+        for k, (feature, thr, lo, hi) in enumerate(self.nodes):
+            rec[k] = (feature, thr, lo, hi)
+        return rec, np.array(self.tree_off, I32), np.stack(self.leaves)
+
+
+def chain_value(level, depth=FOREST_MAX_DEPTH):
+    """the value that follows a chain down to its last leaf (level None: `depth` inner nodes), or turns into the side leaf
+    of inner node `level` (level + 1 inner nodes): above an even level's threshold, equal to an odd level's"""
+    if level is None:
+        return F32(0.5)
+    return F32(level - depth if level % 2 else depth - level + 0.5)
+
+
+CHAIN_LEVELS = [None, 63, 62, 32, 31, 1, 0]  # of the first rows of a serving case, as far as it has rows
+
+
+def check_chain_walks(model, depths, reader, rows):
+    """Reference side, so that the table cannot go hollow: in tree 0 (a chain) row 0 passes all 64 inner nodes and ends in
+    the tree's last node, rows 1 .. leave at the levels of CHAIN_LEVELS; `depths` (ref_predict_rows) are the walks that
+    were compared, none longer than 64.  reader(i) reads row i."""
+    rec, tree_off, _ = model
+    end = int(tree_off[1]) if len(tree_off) > 1 else len(rec)
+    for i, level in enumerate(CHAIN_LEVELS[:rows]):
+        row, depth = walk(rec, int(tree_off[0]), reader(i))
+        assert depth == (FOREST_MAX_DEPTH if level is None else level + 1), (i, level, depth)
+        assert depths[i] >= depth and (level is not None or row == -1 - int(rec[end - 1]["left"]))
+    assert max(depths) == depths[0] == FOREST_MAX_DEPTH
+
+
+def mixed_model(rng, f, n_classes, n_trees, twin=False):
+    """chains, balanced trees and stumps in turn; twin: classes 1 and 2 have equal leaf values everywhere, so their
+    means tie exactly in every row"""
+    b = ModelBuilder(rng, f, n_classes)
+    for t in range(n_trees):
+        (b.chain, b.balanced, b.stump)[t % 3]()
+    rec, tree_off, leaves = b.arrays()
+    if twin:
+        leaves[:, 2] = leaves[:, 1]
+    return rec, tree_off, leaves
+
+
+def stump_model(rows):
+    b = ModelBuilder(np.random.default_rng(0), 1, len(rows[0]))
+    for row in rows:
+        b.stump(row)
+    return b.arrays()
+
+
+def serving_rows(rng, n, f):
+    v = np.concatenate([GRID, np.nextafter(GRID, F32(np.inf)), np.nextafter(GRID, F32(-np.inf))])
+    return rng.choice(v, (n, f)).astype(F32)
+
+
+#                  n    C   trees
+PREDICT_CASES = [(1, 1, 1), (63, 2, 3), (64, 32, 50), (65, 2, 50), (130, 32, 3), (130, 1, 50), (65, 32, 1)]
+#                  class_labels  points  proba
+PREDICT_FORMS = [(False, False, True), (False, False, False), (True, True, False), (True, False, True)]
+# leaf rows of forests of stumps -> (the winner, does the fp64 sum depend on the tree order)
+TIE_MODELS = [([(0.25, 0.5, 0.5)], 1), ([(0.3, 0.3, 0.3, 0.1)], 0),
+              ([(0.5, 0.25, 0.25), (0.25, 0.5, 0.25), (0.25, 0.25, 0.5)], 0),
+              ([(0.1, 0.9, 0.0), (0.2, 0.8, 0.0), (0.3, 0.7, 0.0)], 1),
+              ([(0.1, 0.3, 0.6), (0.2, 0.2, 0.6), (0.3, 0.1, 0.6)], 2),  # 0.6000000000000001 (both ways round) < 0.6 * 3
+              ([(0.0, 0.1, 0.3), (0.0, 0.2, 0.2), (0.0, 0.3, 0.1)], 1)]  # 0.1+0.2+0.3 > 0.3+0.2+0.1: tree order decides
+
+
+def predict_args(x, ld, model, labels, points, raster_w, raster_h, proba):
+    rec, tree_off, leaves = model
+    n, f = x.shape
+    C = leaves.shape[1]
+    out = sent(U8, raster_w * raster_h if points is not None else n + 3)
+    return (Op("x", padded_rows(x, ld)), ld, n, f, Op("tree_off", tree_off), len(tree_off), node_op("nodes", rec),
+            len(rec), Op("leaf_value", leaves), len(leaves), C, None if labels is None else Op("class_labels", labels),
+            None if points is None else Op("points", points), Op("out", out), raster_w if points is not None else 0,
+            Op("proba", sent(F64, n * C + 3)) if proba else None)
+
+
+def draw_points(rng, n, w, h):
+    at = rng.permutation(w * h)[:n]
+    return np.stack([at % w, at // w], 1).astype(I32)
+
+
+def run_predict(be, n, n_classes, n_trees):
+    rng = np.random.default_rng(1000 * n + 10 * n_classes + n_trees)
+    f = 6
+    model = mixed_model(rng, f, n_classes, n_trees)
+    x = serving_rows(rng, n, f)
+    for i, level in enumerate(CHAIN_LEVELS[:n]):
+        x[i, f - 1] = chain_value(level)
+    labels = (200 - 3 * np.arange(n_classes)).astype(U8)
+    w, h = 13, n // 13 + 2
+    points = draw_points(rng, n, w, h)
+    outs = []
+    for with_labels, with_points, with_proba in PREDICT_FORMS:
+        args = predict_args(x, f + 3, model, labels if with_labels else None, points if with_points else None, w + 2, h,
+                            with_proba)
+        depths = []
+        run(be, "forest_predict_rows", ref_predict_rows, *args, tag=f"n{n} C{n_classes} trees{n_trees}", depths=depths)
+        outs.append(args[13].got)
+    assert np.array_equal(outs[0], outs[1])  # proba NULL and non-NULL: the same labels
+    check_chain_walks(model, depths, lambda i: lambda c: x[i, c], n)
+    return model, x
+
+
+def run_predict_ties(be):
+    for rows, winner in TIE_MODELS:
+        model = stump_model(rows)
+        x = np.zeros((3, 1), F32)
+        args = predict_args(x, 2, model, None, None, 0, 0, True)
+        run(be, "forest_predict_rows", ref_predict_rows, *args, tag=f"ties {rows}")
+        assert (args[13].want[:3] == winner).all(), rows
+    a = 0.1 + 0.2 + 0.3
+    assert a != 0.3 + 0.2 + 0.1  # what the last two models turn on
+
+
+def run_predict_threshold(be):
+    """one split at 0.75 on column 1: the row at the threshold goes left, the float32 above it goes right; -0.0 <= 0.0"""
+    b = ModelBuilder(np.random.default_rng(0), 2, 2)
+    b.tree_off.append(0)
+    at = b.inner()
+    b.nodes[at] = (1, F32(0.75), b.leaf((1.0, 0.0)), b.leaf((0.0, 1.0)))
+    b.tree_off.append(len(b.nodes))
+    at = b.inner()
+    b.nodes[at] = (0, F32(-0.0), b.leaf((1.0, 0.0)), b.leaf((0.0, 1.0)))
+    x = np.array([[9, 0.75], [9, np.nextafter(F32(0.75), F32(1))], [9, np.nextafter(F32(0.75), F32(0))],
+                  [0.0, 9], [-0.0, 9], [1e-45, 9], [-1e-45, -9]], F32)
+    args = predict_args(x, 5, b.arrays(), None, None, 0, 0, True)
+    run(be, "forest_predict_rows", ref_predict_rows, *args, tag="threshold")
+    assert list(args[15].want[:14:2]) == [0.5, 0.0, 0.5, 0.5, 0.5, 0.0, 1.0]
+
+
+# ===================================================================================================== 5. predict_scene
+SCENE_CASES = [(p, cc, cl, n) for p in (1, 3, 5) for cc, cl in ((3, 0), (2, 2)) for n in (1, 65)]
+
+
+def run_scene(be, p, cc, cl, n):
+    """hypel_forest_predict_scene with the model translated by forest.scene_features against the reference's walk over
+    the windows cut by definition; then the gather kernel's patches through hypel_forest_predict_rows: the same raster"""
+    rng = np.random.default_rng(100 * p + 10 * cl + n)
+    hp, wp, f = p + 7, p + 9, p * p * (cc + cl)
+    model = mixed_model(rng, f, 4, 5, twin=True)
+    rec, tree_off, leaves = model
+    corners = [(wp - p, hp - p), (0, 0), (wp - p, 0), (0, hp - p)]  # the far corner first: px + p == wp, py + p == hp
+    more = [(x, y) for x, y in draw_points(rng, 80, wp - p + 1, hp - p + 1).tolist() if (x, y) not in corners]
+    points = np.array((corners + more)[:n], I32)
+    casi, lidar = serving_rows(rng, hp * wp, cc), serving_rows(rng, hp * wp, max(cl, 1))
+    for (x0, y0), level in zip(points[:4], CHAIN_LEVELS):  # the last feature of a corner's window: its last pixel's last band
+        (lidar if cl else casi)[(y0 + p - 1) * wp + x0 + p - 1, -1] = chain_value(level)
+    labels = np.array([9, 4, 250, 17], U8)
+    raster_w = wp + 2
+    srec = rec.copy()
+    srec["feature"] = scene_features(np.where(rec["left"] < 0, -1, rec["feature"]), p, wp, cc, cl)
+    ops = dict(casi=Op("casi", casi), lidar=Op("lidar", lidar) if cl else None, points=Op("points", points),
+               tree_off=Op("tree_off", tree_off), leaves=Op("leaf_value", leaves), labels=Op("class_labels", labels))
+    out = Op("out", sent(U8, raster_w * hp))
+    tag = f"p{p} cc{cc} cl{cl} n{n}"
+    args = (ops["casi"], ops["lidar"], hp, wp, cc, cl, ops["points"], n, p, ops["tree_off"], len(tree_off),
+            node_op("scene_nodes", srec), len(rec), ops["leaves"], len(leaves), 4, ops["labels"], out, raster_w)
+    launch(be, "forest_predict_scene", *args)
+    patches = ref_scene_patches(ops["casi"].init, ops["lidar"].init if cl else None, hp, wp, cc, cl, points.reshape(-1), n, p)
+    depths = []
+    ref_predict_rows(patches.reshape(-1), f, n, f, tree_off, len(tree_off), rec.view(U8), len(rec), leaves.reshape(-1),
+                     len(leaves), 4, labels, points.reshape(-1), out.want, raster_w, None, depths=depths)
+    check_chain_walks(model, depths, lambda i: lambda c: patches[i, c], min(n, 4))
+    settle("forest_predict_scene", *args, tag=tag)
+    cut = Op("patches", sent(F32, n * f + 5))
+    launch(be, "gather_patches_f32", ops["casi"], ops["lidar"], hp, wp, cc, cl, ops["points"], n, p, cut)
+    cut.want[:n * f] = patches.reshape(-1)
+    settle("gather_patches_f32", cut, tag=tag)
+    rows = Op("out", sent(U8, raster_w * hp))
+    rows.want = out.want.copy()
+    args = (Op("x", cut.got), f, n, f, ops["tree_off"], len(tree_off), node_op("nodes", rec), len(rec), ops["leaves"],
+            len(leaves), 4, ops["labels"], ops["points"], rows, raster_w, None)
+    launch(be, "forest_predict_rows", *args)
+    settle("forest_predict_rows", *args, tag=tag + " after the gather")
+    assert np.array_equal(rows.got, out.got)
+
+
+# ========================================================================================================== 6. refusals
+def refusal_calls():
+    """(label, kernel, args): valid small launches with one argument outside its contract; every output is sentinels"""
+    rng = np.random.default_rng(3)
+    x = padded_rows(bin_columns(8, rng), 8)
+    calls = []
+
+    def edges(label, ld=8, n_bins=4):
+        calls.append((label, "forest_bin_edges_f32", (Op("x", x), ld, 8, 5, Op("perm", np.arange(8, dtype=I32)), n_bins,
+                                                      Op("edges", sent(F32, 5 * E)), Op("n_edges", sent(I32, 5)))))
+
+    def bins(label, ld=8, ldn=8):
+        calls.append((label, "forest_bin_u8", (Op("x", x), ld, 8, 5, Op("edges", np.full(5 * E, np.inf, F32)),
+                                               Op("n_edges", np.zeros(5, I32)), Op("bins", sent(U8, 5 * 8)), ldn)))
+
+    d = scenario(rng, [8, 8], 2)
+    d["edges"] = edges_table(rng, d["f"])
+    cand = draw_cand(rng, 2, 2, d["f"])
+
+    def hist(label, **kw):
+        a = list(hist_ops(d, cand))
+        for k, v in kw.items():
+            a[dict(ldn=1, C=5, mf=10)[k]] = v
+        calls.append((label, "forest_split_hist", tuple(a)))
+
+    def apply(label, alias=False, **kw):
+        o = node_ops(d, 12, 2)
+        order_in = Op("order_in", d["order"])
+        a = [Op("bins", d["bins"]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"], order_in,
+             order_in if alias else Op("order_out", sent(I32, d["order"].size)), Op("active", d["active"]), 2,
+             Op("cand", cand), 2, d["f"], Op("score", np.ones(4)), Op("best_bin", np.full(4, 100, I32)),
+             Op("valid", np.ones(4, I32)), Op("edges", d["edges"]), 0, 8, 8, 12, *o.values()]
+        for k, v in kw.items():
+            a[dict(ldn=1, C=5, mf=11, max_depth=18, cap=20)[k]] = v
+        calls.append((label, "forest_split_apply", tuple(a)))
+
+    model = mixed_model(rng, 5, 2, 2)
+
+    def rows(label, ld=8, C=2, node_lead=48):
+        a = list(predict_args(x[:, :5].copy(), 8, model, None, None, 0, 0, True))
+        a[1], a[10] = ld, C
+        a[6] = Op("nodes", model[0].view(U8), lead=node_lead)
+        calls.append((label, "forest_predict_rows", tuple(a)))
+
+    def scene(label, C=4, node_lead=48):
+        p, cc, cl, hp, wp = 3, 2, 1, 5, 6
+        rec, tree_off, leaves = mixed_model(rng, p * p * (cc + cl), 4, 2)
+        rec["feature"] = scene_features(np.where(rec["left"] < 0, -1, rec["feature"]), p, wp, cc, cl)
+        calls.append((label, "forest_predict_scene",
+                      (Op("casi", serving_rows(rng, hp * wp, cc)), Op("lidar", serving_rows(rng, hp * wp, cl)), hp, wp, cc,
+                       cl, Op("points", np.array([[0, 0], [3, 2]], I32)), 2, p, Op("tree_off", tree_off), len(tree_off),
+                       Op("scene_nodes", rec.view(U8), lead=node_lead), len(rec), Op("leaf_value", leaves), len(leaves), C,
+                       Op("class_labels", np.arange(4, dtype=U8)), Op("out", sent(U8, hp * 8)), 8)))
+
+    edges("n_bins 1", n_bins=1), edges("n_bins 257", n_bins=257), edges("ld < f", ld=4)
+    bins("ld < f", ld=4), bins("ldn < n", ldn=7)
+    hist("n_classes 0", C=0), hist("n_classes 33", C=FOREST_MAX_CLASSES + 1), hist("max_features > f", mf=d["f"] + 1)
+    hist("ldn < n", ldn=d["n"] - 1)
+    apply("n_classes 0", C=0), apply("n_classes 33", C=FOREST_MAX_CLASSES + 1), apply("max_features > f", mf=d["f"] + 1)
+    apply("ldn < n", ldn=d["n"] - 1), apply("order_in == order_out", alias=True)
+    apply("max_depth 65", max_depth=FOREST_MAX_DEPTH + 1), apply("node_capacity < node_base", cap=7)
+    rows("ld < f", ld=4), rows("n_classes 0", C=0), rows("n_classes 33", C=FOREST_MAX_CLASSES + 1)
+    scene("n_classes 0", C=0), scene("n_classes 33", C=FOREST_MAX_CLASSES + 1)
+    rows("nodes 4 bytes off their alignment", node_lead=52), scene("nodes 8 bytes off their alignment", node_lead=56)
+    return calls
+
+
+def run_refusals(be):
+    for label, kernel, args in refusal_calls():
+        launch(be, kernel, *args, refused=True)
+        settle(kernel, *args, tag="refused: " + label)  # want = what was uploaded: not a byte has changed

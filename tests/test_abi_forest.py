@@ -1,7 +1,7 @@
 """CPU: the random-forest entry points are declared in include/hypel.h, exported by the library (their binding:
 tests/test_abi.py, which checks every prototype of the header), and refuse null pointers, zero or negative sizes,
-n_classes above the LDS cap and max_features > F with a message before anything is launched.  The ABI version is still
-8: new symbols only."""
+n_classes above the LDS cap, max_features > F and node records off their 16-byte alignment with a message before
+anything is launched.  The ABI version is still 8: new symbols only."""
 import ctypes
 import re
 
@@ -27,8 +27,8 @@ def test_version_8_new_symbols_and_constants(lib):  # noqa: F811
 
 
 def test_bad_arguments_are_refused_with_a_message(lib):  # noqa: F811
-    buf = (ctypes.c_uint8 * 4096)()
-    p = ctypes.addressof(buf)  # never dereferenced: every call below fails its argument check first
+    buf = (ctypes.c_uint8 * (4096 + 16))()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16  # never dereferenced: every call below fails its argument check first
     q = p + 2048
     too_many = 33
 
@@ -85,12 +85,13 @@ def test_bad_arguments_are_refused_with_a_message(lib):  # noqa: F811
             rows(x=None), rows(out=None), rows(tree_off=None), rows(nodes=None), rows(leaf_value=None), rows(n=0),
             rows(n=-1), rows(f=0), rows(ld=3),
             rows(n_trees=0), rows(n_nodes=0), rows(n_leaves=0), rows(n_leaves=4), rows(n_classes=0),
-            rows(n_classes=too_many), rows(points=p, raster_w=0)],
+            rows(n_classes=too_many), rows(points=p, raster_w=0), rows(nodes=p + 4), rows(nodes=p + 8)],
         "hypel_forest_predict_scene": [
             scene(casi=None), scene(lidar=None), scene(points=None), scene(out=None), scene(tree_off=None),
             scene(scene_nodes=None), scene(leaf_value=None), scene(n=0), scene(p=0), scene(hp=4), scene(wp=4),
             scene(cc=0), scene(cl=-1),
-            scene(raster_w=0), scene(n_trees=0), scene(n_leaves=0), scene(n_classes=too_many), scene(hp=-9)],
+            scene(raster_w=0), scene(n_trees=0), scene(n_leaves=0), scene(n_classes=0), scene(n_classes=too_many),
+            scene(hp=-9), scene(scene_nodes=p + 4), scene(scene_nodes=p + 8)],
     }
     for name, bad in calls.items():
         fn = getattr(lib, name)
