@@ -54,6 +54,10 @@ COMPACT_TILE = abi.const("HYPEL_COMPACT_TILE")  # pixels per int32 of hypel_mask
 # classes of hypel_components_votes_i32 (its exclude mask is 64 bits), status words of hypel_components_label_u8
 COMPONENTS_MAX_CLASSES = abi.const("HYPEL_COMPONENTS_MAX_CLASSES")
 COMPONENTS_OK, COMPONENTS_STEP_CAP = abi.const("HYPEL_COMPONENTS_OK"), abi.const("HYPEL_COMPONENTS_STEP_CAP")
+# hypel_match_ccorr_f32: side of an output tile, image rows and template columns of one staged chunk, output columns of a
+# block, and the most column-chunk splits a call takes
+MATCH_TILE, MATCH_ROW_CHUNK, MATCH_COL_CHUNK, MATCH_BLOCK_COLS, MATCH_MAX_SPLITS = (
+    abi.const("HYPEL_MATCH_" + k) for k in ("TILE", "ROW_CHUNK", "COL_CHUNK", "BLOCK_COLS", "MAX_SPLITS"))
 SUMMARY_SLICE = abi.const("HYPEL_SUMMARY_SLICE")  # elements per slice of hypel_tensor_summary_f32
 SUMMARY_MAX_LIMITS = abi.const("HYPEL_SUMMARY_MAX_LIMITS")
 # rows sorted per column for the bin edges, edges per column, classes of the LDS histogram, depth cap of the level loop

@@ -1002,6 +1002,55 @@ int hypel_forest_predict_scene(const float* casi, const float* lidar, int64_t hp
                                int32_t n_leaves, int32_t n_classes, const uint8_t* class_labels, uint8_t* out,
                                int64_t raster_w, hypel_stream_t stream);
 
+/* ---- template matching (utilities/lidar_matcher.py: cv2.resize INTER_AREA by an integer factor, cv2.matchTemplate
+ * TM_CCORR_NORMED, cv2.minMaxLoc's max_loc; csrc/match.hip) ------------------------------------------------------------
+ * A raster is ONE float32 band read in place: sample (y, x) of the [h][w] source is src[y*sy + x*sx] (element strides
+ * >= 0; band b of a pixel-major [h][w][bands] scene is src + b with sx = bands), enlarged by pixel replication with the
+ * integer factor scale >= 1: R'(Y, X) = R(Y / scale, X / scale), H = h * scale rows of W = w * scale columns.  The
+ * enlarged raster is never written anywhere.  Image I' is H x W, template T' is HT x WT with HT <= H and WT <= W, the
+ * output surface is hout x wout = (H - HT + 1) x (W - WT + 1), row-major; H * W, HT * WT and hout * wout are below
+ * 2^31.  Inputs are finite (a NaN or an infinity anywhere is not supported: it spreads over every window it touches).
+ *
+ * hypel_match_ccorr_f32: num[y*wout + x] = sum_{i < HT, j < WT} T'(i, j) * I'(y + i, x + j) in float32 on the fp32
+ *   matrix cores (v_mfma_f32_16x16x4_f32, an fmaf chain: every product exact, one rounding per addition).  HYPEL_MATCH_TILE
+ *   output rows are the product of a Toeplitz band of one template column with a shifted window of the image,
+ *   accumulated over the template's columns in chunks of HYPEL_MATCH_COL_CHUNK and over HYPEL_MATCH_TILE - 1 + HT image
+ *   rows in chunks of HYPEL_MATCH_ROW_CHUNK; a block owns HYPEL_MATCH_TILE x HYPEL_MATCH_BLOCK_COLS outputs.  `splits`
+ *   (1 .. HYPEL_MATCH_MAX_SPLITS) deals the (column chunk, row chunk) pairs, in that order, evenly to that many blocks
+ *   per tile so that a surface of few tiles still fills the device: split s writes its partial surface to
+ *   ws[s * hout * wout ...] and a second launch adds the partials in the order of s -- no float atomics, two calls
+ *   give identical bits.  ws: splits * hout * wout float32, unused (may be null) when splits is 1;
+ *   splits * hout * wout < 2^31.
+ * hypel_match_window_energy_f64: energy[y*wout + x] = sum over the win_h x win_w window at (y, x) of R'^2 in double
+ *   (a float32 squared is exact in double), hout x wout = (H - win_h + 1) x (W - win_w + 1).  Two separable passes:
+ *   window sums along every SOURCE row into ws (h * wout doubles; a wavefront per 64 outputs: the first window summed
+ *   by all lanes, the others by a prefix sum of what enters and what leaves), then down the columns (a thread per 32
+ *   outputs: the first summed, the others slid).  At most 2 * (W + H) + 128 roundings per output, each relative to a
+ *   partial sum of non-negative terms; a result the subtractions leave below zero (over a stretch of zeros) is stored
+ *   as 0.  The window equal to the whole raster gives the template's energy as a 1 x 1 output.
+ * hypel_match_best_f32: R = (float)((double)num / sqrt(energy * *e_t)), 0 where energy * *e_t == 0; division and square
+ *   root are IEEE double.  score_map (optional) [hout * wout] float32 = R.  result: 16 bytes, 8-byte aligned -- float32
+ *   best R at byte 0, zero at byte 4, int64 row-major index of it at byte 8; among equal values the smallest index (what
+ *   cv2.minMaxLoc reports as max_loc = (index % wout, index / wout)).  The reduction is an integer atomic maximum of
+ *   (R's bits in sortable order, ~index) and does not depend on the order of arrival.
+ * hypel_match_render_u8: out [H][W] uint8 = (uint8)(R'(Y, X) / *max * 255), float32 division and product rounded on their
+ *   own and truncated -- NumPy's (band / numpy.max(band) * 255).astype('uint8') for 0 <= band <= max; values outside
+ *   0 .. 255 are clamped, *max <= 0 gives 0.  max: device float32 (hypel_scene_extrema of the band). */
+#define HYPEL_MATCH_TILE 16
+#define HYPEL_MATCH_ROW_CHUNK 32
+#define HYPEL_MATCH_COL_CHUNK 32
+#define HYPEL_MATCH_BLOCK_COLS 128
+#define HYPEL_MATCH_MAX_SPLITS 4096
+int hypel_match_ccorr_f32(const float* image, int64_t h, int64_t w, int64_t sy, int64_t sx, int32_t scale,
+                          const float* tmpl, int64_t ht, int64_t wt, int64_t tsy, int64_t tsx, int32_t tscale, float* num,
+                          float* ws, int32_t splits, hypel_stream_t stream);
+int hypel_match_window_energy_f64(const float* src, int64_t h, int64_t w, int64_t sy, int64_t sx, int32_t scale,
+                                  int64_t win_h, int64_t win_w, double* energy, double* ws, hypel_stream_t stream);
+int hypel_match_best_f32(const float* num, const double* energy, const double* e_t, int64_t hout, int64_t wout,
+                         float* score_map, void* result, hypel_stream_t stream);
+int hypel_match_render_u8(const float* src, int64_t h, int64_t w, int64_t sy, int64_t sx, int32_t scale, const float* max,
+                          uint8_t* out, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
