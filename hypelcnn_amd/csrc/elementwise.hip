@@ -949,23 +949,30 @@ __global__ void dropout_mask_kernel(float* __restrict__ mask, int64_t count, flo
 
 // ------------------------------------------------------------------------------------- small-rows BN
 // Fully-connected tail of the models: activations are [N x C] with N = the batch (1024 rows), so every channel's
-// statistics fit in ONE block.  A block owns a 32-channel stripe for ALL rows: statistics, finaliser and the
+// statistics fit in ONE block.  A block owns a stripe of TX channels for ALL rows: statistics, finaliser and the
 // normalise/activate pass (forward), or the two reductions and the gradient (backward), in a single launch instead
 // of three -- no cross-block dependency, hence none of the cross-XCD coherence cost of the ticket scheme.
-constexpr int SMALL_TX = 32;    // channels per block
-constexpr int SMALL_TY = 32;    // row lanes (block = 1024 threads)
+// Every thread keeps 32 rows of one channel in registers and the block has 32 row lanes, whatever the stripe width: the
+// block is 32 x TX threads.  A wide layer takes TX = 32 (1024 threads); a layer that would leave most CUs idle at that
+// width takes 16-, 8- or 4-channel stripes (512, 256 or 128 threads): the same loads and stores go through 2-8x as many
+// CUs' memory pipelines (small_stripe() picks the width on the host).  The sums of a channel are the same 32 chains of 32
+// rows, paired and added in the same order at every width, so the result does not depend on the width bit for bit.
+constexpr int SMALL_TX = 32;    // widest stripe: channels per block
+constexpr int SMALL_TY = 32;    // row lanes
 constexpr int SMALL_R = 32;     // rows per thread, kept in registers between the reduction and the apply pass
 constexpr int SMALL_MAX_ROWS = SMALL_TY * SMALL_R;
 
-// Both column sums of a kernel in ONE exchange: a wave holds two row lanes of its 32 columns, which one cross-lane add
-// combines (fixed order); the 16 wave partials go through LDS as float2 and every thread adds them up in wave order
-// -- one barrier and 16 ds_read_b64 per thread instead of four barriers and 64 ds_read_b32 (the two separate
-// 32-deep exchanges were 3.7 of the 7 us such a kernel spends, phase-stamped copy in tools/exp/probe).
-__device__ __forceinline__ void small_lane_sum2(float& a, float& b, float2 (*sh)[SMALL_TX]) {
-    const int tx = threadIdx.x & (SMALL_TX - 1), wave = threadIdx.x >> 6;
-    a += __shfl_xor(a, 32, 64);
-    b += __shfl_xor(b, 32, 64);
-    if ((threadIdx.x & 63) < SMALL_TX) sh[wave][tx] = make_float2(a, b);
+// Both column sums of a kernel in ONE exchange: row lanes 2 j and 2 j + 1 of a channel sit TX lanes apart in one wave,
+// which one cross-lane add combines (fixed order); the 16 pair sums go through LDS as float2 and every thread adds
+// them up in pair order -- one barrier and 16 ds_read_b64 per thread instead of four barriers and 64 ds_read_b32 (the
+// two separate 32-deep exchanges were 3.7 of the 7 us such a kernel spends, phase-stamped copy in tools/exp/probe).
+// tests/bn_ref.py FORMS["small"] = (32, 17): 32 row lanes, one pair add and 16 additions to 0.
+template <int TX>
+__device__ __forceinline__ void small_lane_sum2(float& a, float& b, float2 (*sh)[TX]) {
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    a += __shfl_xor(a, TX, 64);
+    b += __shfl_xor(b, TX, 64);
+    if ((ty & 1) == 0) sh[ty >> 1][tx] = make_float2(a, b);
     __syncthreads();
     float ta = 0.0f, tb = 0.0f;
 #pragma unroll
@@ -997,13 +1004,14 @@ __device__ __forceinline__ uint32_t small_row_off(uint32_t v0, int last_row_minu
     return v0 | (uint32_t)((last_row_minus_ty - i * SMALL_TY) >> 31);
 }
 
-template <bool FULL>
+template <int TX, bool FULL>
 __device__ __forceinline__ void small_load_rows(const float* p, int ld, int rows, int col, bool ok, float (&v)[SMALL_R]) {
-    const int ty = threadIdx.x / SMALL_TX;
+    constexpr int TY = SMALL_TY;
+    const int ty = threadIdx.x / TX;
     const __amdgpu_buffer_rsrc_t rs = small_rsrc(p);
     const uint32_t v0 = ok ? (uint32_t)(ty * ld + col) * 4u : SMALL_OOB;
     const int last = rows - 1 - ty;
-    const int step = SMALL_TY * ld * 4;
+    const int step = TY * ld * 4;
     int so = 0;
 #pragma unroll
     for (int i = 0; i < SMALL_R; ++i) {
@@ -1013,13 +1021,14 @@ __device__ __forceinline__ void small_load_rows(const float* p, int ld, int rows
     }
 }
 
-template <bool FULL>
+template <int TX, bool FULL>
 __device__ __forceinline__ void small_store_rows(float* p, int ld, int rows, int col, bool ok, const float (&v)[SMALL_R]) {
-    const int ty = threadIdx.x / SMALL_TX;
+    constexpr int TY = SMALL_TY;
+    const int ty = threadIdx.x / TX;
     const __amdgpu_buffer_rsrc_t rs = small_rsrc(p);
     const uint32_t v0 = ok ? (uint32_t)(ty * ld + col) * 4u : SMALL_OOB;
     const int last = rows - 1 - ty;
-    const int step = SMALL_TY * ld * 4;
+    const int step = TY * ld * 4;
     int so = 0;
 #pragma unroll
     for (int i = 0; i < SMALL_R; ++i) {
@@ -1029,20 +1038,22 @@ __device__ __forceinline__ void small_store_rows(float* p, int ld, int rows, int
     }
 }
 
-template <bool FULL>  // FULL: rows == SMALL_MAX_ROWS, no row guards at all
-__global__ __launch_bounds__(1024) void bn_act_small_fwd_kernel(
+// TX: channels per block (32 x TX threads); FULL: rows == SMALL_MAX_ROWS, no row guards at all
+template <int TX, bool FULL>
+__global__ __launch_bounds__(SMALL_TY * TX) void bn_act_small_fwd_kernel(
     const float* __restrict__ y, int ldy, int rows, int c, float eps, const float* __restrict__ beta, int act,
     float alpha, const float* __restrict__ mask, int ldm, float* __restrict__ mean_out,
     float* __restrict__ rstd_out, float* __restrict__ moving_mean, float* __restrict__ moving_var, float decay,
     float* __restrict__ z, int ldz) {
-    __shared__ float2 sh[SMALL_TY / 2][SMALL_TX];
-    const int tx = threadIdx.x & (SMALL_TX - 1), ty = threadIdx.x / SMALL_TX;
-    const int col = blockIdx.x * SMALL_TX + tx;
+    constexpr int TY = SMALL_TY;
+    __shared__ float2 sh[SMALL_TY / 2][TX];
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    const int col = blockIdx.x * TX + tx;
     const bool ok = col < c;
     const int colc = ok ? col : c - 1;
     float v[SMALL_R], mk[SMALL_R];
-    small_load_rows<FULL>(y, ldy, rows, col, ok, v);
-    if (mask) small_load_rows<FULL>(mask, ldm, rows, col, ok, mk);
+    small_load_rows<TX, FULL>(y, ldy, rows, col, ok, v);
+    if (mask) small_load_rows<TX, FULL>(mask, ldm, rows, col, ok, mk);
     const float shift = y[colc];  // first row: keeps the fp32 sums well conditioned
     // everything the tail needs is requested now: a load behind the block barriers below would be one more memory
     // round trip in a kernel that is nothing but latency
@@ -1051,11 +1062,11 @@ __global__ __launch_bounds__(1024) void bn_act_small_fwd_kernel(
     float s = 0.0f, ss = 0.0f;
 #pragma unroll
     for (int i = 0; i < SMALL_R; ++i) {
-        const float d = (FULL || ty + i * SMALL_TY < rows) ? v[i] - shift : 0.0f;
+        const float d = (FULL || ty + i * TY < rows) ? v[i] - shift : 0.0f;
         s += d;
         ss += d * d;
     }
-    small_lane_sum2(s, ss, sh);
+    small_lane_sum2<TX>(s, ss, sh);
     const double ts = (double)s, tss = (double)ss;
     const double n = (double)rows;
     const double mean = (double)shift + ts / n;
@@ -1086,28 +1097,29 @@ __global__ __launch_bounds__(1024) void bn_act_small_fwd_kernel(
 #pragma unroll
         for (int i = 0; i < SMALL_R; ++i) v[i] *= mk[i];
     }
-    small_store_rows<FULL>(z, ldz, rows, col, ok, v);
+    small_store_rows<TX, FULL>(z, ldz, rows, col, ok, v);
 }
 
-template <bool FULL>
-__global__ __launch_bounds__(1024) void bn_act_small_bwd_kernel(
+template <int TX, bool FULL>
+__global__ __launch_bounds__(SMALL_TY * TX) void bn_act_small_bwd_kernel(
     const float* dz, int lddz, const float* __restrict__ y, int ldy, int rows, int c,
     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ beta, int act,
     float alpha, const float* __restrict__ mask, int ldm, float* dy, int lddy,
     float* __restrict__ dparam, int accumulate) {
-    __shared__ float2 sh[SMALL_TY / 2][SMALL_TX];
-    const int tx = threadIdx.x & (SMALL_TX - 1), ty = threadIdx.x / SMALL_TX;
-    const int col = blockIdx.x * SMALL_TX + tx;
+    constexpr int TY = SMALL_TY;
+    __shared__ float2 sh[SMALL_TY / 2][TX];
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    const int col = blockIdx.x * TX + tx;
     const bool ok = col < c;
     const int colc = ok ? col : c - 1;
     float g[SMALL_R], xh[SMALL_R];  // dyh and xhat of this thread's rows
     const float mu = mean[colc], rs = rstd[colc], be = beta[colc];
     const float dp0 = (dparam && accumulate) ? dparam[colc] : 0.0f;  // requested before the barriers (see forward)
-    small_load_rows<FULL>(y, ldy, rows, col, ok, xh);
-    small_load_rows<FULL>(dz, lddz, rows, col, ok, g);
+    small_load_rows<TX, FULL>(y, ldy, rows, col, ok, xh);
+    small_load_rows<TX, FULL>(dz, lddz, rows, col, ok, g);
     if (mask) {
         float mk[SMALL_R];
-        small_load_rows<FULL>(mask, ldm, rows, col, ok, mk);
+        small_load_rows<TX, FULL>(mask, ldm, rows, col, ok, mk);
 #pragma unroll
         for (int i = 0; i < SMALL_R; ++i) g[i] *= mk[i];
     }
@@ -1117,18 +1129,18 @@ __global__ __launch_bounds__(1024) void bn_act_small_bwd_kernel(
         xh[i] = hypel_bn_xhat(xh[i], mu, rs);
         const float p = hypel_bn_pre(xh[i], be);
         const float slope = act == HYPEL_ACT_LRELU ? (p > 0.0f ? 1.0f : alpha) : hypel_act_grad(p, act, alpha);
-        g[i] = (FULL || ty + i * SMALL_TY < rows) ? g[i] * slope : 0.0f;
+        g[i] = (FULL || ty + i * TY < rows) ? g[i] * slope : 0.0f;
         s0 += g[i];
         s1 += g[i] * xh[i];
     }
-    small_lane_sum2(s0, s1, sh);
+    small_lane_sum2<TX>(s0, s1, sh);
     const float t0 = s0, t1 = s1;
     if (ok && ty == 0 && dparam) dparam[col] = dp0 + t0;
     const float inv_m = 1.0f / (float)rows;
     const float m0 = t0 * inv_m, m1 = t1 * inv_m;
 #pragma unroll
     for (int i = 0; i < SMALL_R; ++i) g[i] = rs * (g[i] - m0 - xh[i] * m1);
-    small_store_rows<FULL>(dy, lddy, rows, col, ok, g);
+    small_store_rows<TX, FULL>(dy, lddy, rows, col, ok, g);
 }
 
 // ------------------------------------------------------------------------------------- 2-D block copies
@@ -1483,6 +1495,40 @@ extern "C" int hypel_act_bias_bwd_reduce(const float* dz, int64_t lddz, const fl
 // byte offsets of the small-rows kernels are 32-bit buffer offsets
 static inline bool small_span_ok(int64_t rows, int64_t ld) { return ld > 0 && rows * ld * 4 < 0x7ffffff0ll; }
 
+// Channels per block of the small-rows kernels, from the per-width timings of tools/exp/fc_tail_probe.py
+// (profiles/fc_tail_stamps.txt, 1024 rows, forward / backward us per launch): 4-channel stripes are fastest up to 32
+// blocks (c = 108: 5.2 / 8.8 against 6.4 / 9.0 at 8 channels and 13.1 / 17.8 at 32), 8-channel stripes up to 64 blocks
+// (c = 405: 7.9 / 10.5 against 8.4 / 11.6 at 16 channels), 16-channel stripes up to 64 blocks again (c = 980: 8.9 / 12.0
+// against 10.1 / 13.4 at 8 and 10.5 / 14.2 at 32 channels); beyond that the short row pieces of a narrow stripe cost
+// more than the spread buys (c = 2048: 10.4 / 14.5 at 16 channels, 9.9 / 13.2 at 32), so wider layers keep the
+// 32-channel block.  The result does not depend on the choice.
+#ifndef HYPEL_SMALL_FORCE_TX  // -DHYPEL_SMALL_FORCE_TX=4|8|16|32 pins the width: how the probe prices the shapes
+#define HYPEL_SMALL_FORCE_TX 0
+#endif
+static inline int small_stripe(int32_t c) {
+    if (HYPEL_SMALL_FORCE_TX) return HYPEL_SMALL_FORCE_TX;
+    if ((c + 3) / 4 <= 32) return 4;
+    if ((c + 7) / 8 <= 64) return 8;
+    if ((c + 15) / 16 <= 64) return 16;
+    return SMALL_TX;
+}
+
+#define SMALL_LAUNCH(kernel, tx, ...)                                                                  \
+    do {                                                                                               \
+        const dim3 grid((c + (tx) - 1) / (tx));                                                        \
+        if (rows == SMALL_MAX_ROWS)                                                                    \
+            hipLaunchKernelGGL((kernel<tx, true>), grid, dim3(SMALL_TY * (tx)), 0, ST, __VA_ARGS__);              \
+        else                                                                                           \
+            hipLaunchKernelGGL((kernel<tx, false>), grid, dim3(SMALL_TY * (tx)), 0, ST, __VA_ARGS__);             \
+    } while (0)
+#define SMALL_DISPATCH(kernel, ...)                                                                    \
+    switch (small_stripe(c)) {                                                                         \
+        case 4: SMALL_LAUNCH(kernel, 4, __VA_ARGS__); break;                                           \
+        case 8: SMALL_LAUNCH(kernel, 8, __VA_ARGS__); break;                                           \
+        case 16: SMALL_LAUNCH(kernel, 16, __VA_ARGS__); break;                                         \
+        default: SMALL_LAUNCH(kernel, SMALL_TX, __VA_ARGS__); break;                                   \
+    }
+
 extern "C" int hypel_bn_act_small_fwd(const float* y, int64_t ldy, int64_t rows, int32_t c, float eps,
                                       const float* beta, int32_t act, float alpha, const float* mask, int64_t ldm,
                                       float* mean, float* rstd, float* moving_mean, float* moving_var, float decay,
@@ -1492,13 +1538,8 @@ extern "C" int hypel_bn_act_small_fwd(const float* y, int64_t ldy, int64_t rows,
     HYPEL_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "hypel_bn_act_small_fwd");
     HYPEL_REQUIRE(small_span_ok(rows, ldy) && small_span_ok(rows, ldz) && (!mask || small_span_ok(rows, ldm)),
                   "hypel_bn_act_small_fwd");
-    const dim3 grid((c + SMALL_TX - 1) / SMALL_TX);
-    if (rows == SMALL_MAX_ROWS)
-        hipLaunchKernelGGL(bn_act_small_fwd_kernel<true>, grid, dim3(1024), 0, ST, y, (int)ldy, (int)rows, c, eps, beta,
-                           act, alpha, mask, (int)ldm, mean, rstd, moving_mean, moving_var, decay, z, (int)ldz);
-    else
-        hipLaunchKernelGGL(bn_act_small_fwd_kernel<false>, grid, dim3(1024), 0, ST, y, (int)ldy, (int)rows, c, eps, beta,
-                           act, alpha, mask, (int)ldm, mean, rstd, moving_mean, moving_var, decay, z, (int)ldz);
+    SMALL_DISPATCH(bn_act_small_fwd_kernel, y, (int)ldy, (int)rows, c, eps, beta, act, alpha, mask, (int)ldm, mean, rstd,
+                   moving_mean, moving_var, decay, z, (int)ldz)
     HYPEL_CHECK_LAUNCH("hypel_bn_act_small_fwd");
     return 0;
 }
@@ -1512,13 +1553,8 @@ extern "C" int hypel_bn_act_small_bwd(const float* dz, int64_t lddz, const float
     HYPEL_REQUIRE(small_span_ok(rows, lddz) && small_span_ok(rows, ldy) && small_span_ok(rows, lddy) &&
                       (!mask || small_span_ok(rows, ldm)),
                   "hypel_bn_act_small_bwd");
-    const dim3 grid((c + SMALL_TX - 1) / SMALL_TX);
-    if (rows == SMALL_MAX_ROWS)
-        hipLaunchKernelGGL(bn_act_small_bwd_kernel<true>, grid, dim3(1024), 0, ST, dz, (int)lddz, y, (int)ldy, (int)rows,
-                           c, mean, rstd, beta, act, alpha, mask, (int)ldm, dy, (int)lddy, dparam, accumulate);
-    else
-        hipLaunchKernelGGL(bn_act_small_bwd_kernel<false>, grid, dim3(1024), 0, ST, dz, (int)lddz, y, (int)ldy,
-                           (int)rows, c, mean, rstd, beta, act, alpha, mask, (int)ldm, dy, (int)lddy, dparam, accumulate);
+    SMALL_DISPATCH(bn_act_small_bwd_kernel, dz, (int)lddz, y, (int)ldy, (int)rows, c, mean, rstd, beta, act, alpha, mask,
+                   (int)ldm, dy, (int)lddy, dparam, accumulate)
     HYPEL_CHECK_LAUNCH("hypel_bn_act_small_bwd");
     return 0;
 }
