@@ -60,6 +60,7 @@ MATCH_TILE, MATCH_ROW_CHUNK, MATCH_COL_CHUNK, MATCH_BLOCK_COLS, MATCH_MAX_SPLITS
     abi.const("HYPEL_MATCH_" + k) for k in ("TILE", "ROW_CHUNK", "COL_CHUNK", "BLOCK_COLS", "MAX_SPLITS"))
 SUMMARY_SLICE = abi.const("HYPEL_SUMMARY_SLICE")  # elements per slice of hypel_tensor_summary_f32
 SUMMARY_MAX_LIMITS = abi.const("HYPEL_SUMMARY_MAX_LIMITS")
+ACT_MAX_BINS = abi.const("HYPEL_ACT_MAX_BINS")  # bins of hypel_view_histogram_f32 (its LDS table and histogram)
 # rows sorted per column for the bin edges, edges per column, classes of the LDS histogram, depth cap of the level loop
 FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = (
     abi.const("HYPEL_FOREST_" + k) for k in ("EDGE_ROWS", "MAX_EDGES", "MAX_CLASSES", "MAX_DEPTH"))

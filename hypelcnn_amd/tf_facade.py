@@ -635,9 +635,12 @@ class ReferenceModel:
                 self.ref_ops.ModelInputParams(x=eng.wrap(x), y=None, device_id=model_input_params.device_id,
                                               is_training=model_input_params.is_training), class_count, algorithm_params)
         sym = lambda t: None if t is None else t.sym  # noqa: E731
+        # the tapped activations (utilities/nn_layer_activation_graph.py), under the reference's names
+        taps = [self.product_ops.HistogramTensorPair(pair.tensor.sym, pair.name)
+                for pair in getattr(out, "histogram_tensors", None) or []]
         return self.product_ops.ModelOutputTensors(
             y_conv=out.y_conv.sym, image_output=sym(getattr(out, "image_output", None)),
-            image_original=sym(getattr(out, "image_original", None)), histogram_tensors=[])
+            image_original=sym(getattr(out, "image_original", None)), histogram_tensors=taps)
 
     def get_loss_func(self, tensor_output, label):
         eng = GraphEngine(tensor_output.y_conv.tower)

@@ -1051,6 +1051,35 @@ int hypel_match_best_f32(const float* num, const double* energy, const double* e
 int hypel_match_render_u8(const float* src, int64_t h, int64_t w, int64_t sy, int64_t sx, int32_t scale, const float* max,
                           uint8_t* out, hypel_stream_t stream);
 
+/* ---- layer-activation range and histogram (utilities/nn_layer_activation_graph.py: numpy.histogram of the tapped
+ * activations between their global minimum and maximum; common/device_activation.py, csrc/activation.hip) -------------
+ * A VIEW is rows x cols float32 inside a row-major buffer with leading dimension ld >= cols: element (r, j) is
+ * src[r * ld + j].  src is 4-byte aligned only (a tap's channel offset may be odd); what lies between the rows is never
+ * read.  That is how a tap of a tower lies in its pixel-major plan buffer [npix][nb][ld]: one view of npix * nb rows at
+ * its channel offset, or one view per run of consecutive pixels of a pixel map.  rows >= 0 (0: nothing is launched, the
+ * outputs are untouched), cols >= 1, rows * cols < 2^37 (a block counts its share in 32 bits) and rows * ld <= 2^62;
+ * anything else is refused.  Both calls ACCUMULATE into outputs the caller initialised, so that one tap is folded over
+ * many batches and several views; the results are exact and independent of launch geometry and call order (integer
+ * atomics only).
+ *
+ * hypel_view_range_f32: range[0] = min(range[0], v), range[1] = max(range[1], v) over the FINITE elements v (start them
+ *   at +FLT_MAX / -FLT_MAX; a NaN or a -0.0 there is not supported), count[0] += the number of finite elements,
+ *   count[1] += the number of NaN and +-Inf.  -0.0 counts as +0.0: which of the two a zero extreme comes back as is
+ *   unspecified.  The extremes are integer atomics on the float's bits: signed order for v >= 0, reversed unsigned order
+ *   for v < 0.
+ * hypel_view_histogram_f32: edges is device float64 [n_bins + 1], strictly ascending, 1 <= n_bins <= HYPEL_ACT_MAX_BINS.
+ *   A finite v with edges[0] <= v <= edges[n_bins] adds one to counts[k] for the k with edges[k] <= v < edges[k + 1], the
+ *   last bin closed on the right (numpy.histogram on float64 data); a finite v outside adds one to outside[0]; NaN and
+ *   +-Inf are counted nowhere.  The table decides the bin: it is estimated as (v - edges[0]) * n_bins / (edges[n_bins] -
+ *   edges[0]) and corrected against the edges, held in LDS rounded up to float32 -- a few comparisons for a uniform
+ *   table, a binary search for one that is far from it, exact for both.  One LDS histogram per block (8 * n_bins bytes of
+ *   LDS), flushed once with 64-bit integer atomics on the non-zero counters. */
+#define HYPEL_ACT_MAX_BINS 4096
+int hypel_view_range_f32(const float* src, int64_t rows, int64_t ld, int32_t cols, float* range, int64_t* count,
+                         hypel_stream_t stream);
+int hypel_view_histogram_f32(const float* src, int64_t rows, int64_t ld, int32_t cols, const double* edges,
+                             int32_t n_bins, int64_t* counts, int64_t* outside, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
