@@ -325,3 +325,10 @@ class HipBackend:
 
         replay.handle = handle
         return replay
+
+    def destroy_graph(self, replay):
+        """Give a captured graph back to the runtime (hipGraphExecDestroy).  The caller has synchronised: no replay of
+        it is in flight, and it is not replayed again."""
+        handle, replay.handle = getattr(replay, "handle", None), None
+        if handle:
+            self.lib.hypel_graph_destroy(handle)

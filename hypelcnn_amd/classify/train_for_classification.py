@@ -4,8 +4,16 @@
         --neighborhood 3 --model_name HYPELCNNModel --algorithm_param_path <json> --batch_size 64 --step 300
 
 Multi-GPU: launch with torch.distributed.run (one rank per GPU); gradients are all-reduced over RCCL.
-The optuna mode of the reference (--flag_config_file_opt) is not on the hot path and is not provided."""
+
+Hyper-parameter search, the reference's --flag_config_file_opt mode: a study of --opt_trial_count trials, each the worst
+1 - validation accuracy of --opt_run_count whole episodes (common/hyperopt.py).  The search-space file carries the
+algorithm parameters, as constants or ranges; --batch_size comes from the flags:
+
+    python -m hypelcnn_amd.classify.train_for_classification --loader_name SyntheticDataLoader --path grss2013 \
+        --neighborhood 3 --batch_size 64 --step 300 --perform_validation true --flag_config_file_opt <json> \
+        --opt_trial_count 10 --opt_run_count 3 [--opt_seed 0] [--opt_sampler tpe|random] [--opt_storage <file>]"""
 import argparse
+import functools
 import json
 import os
 import time
@@ -15,8 +23,8 @@ from numpy import mean, std
 from hypelcnn_amd.classify.monitored_session_runner import add_classification_summaries, run_monitored_session, \
     set_run_seed
 from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_importers, add_parse_cmds_for_loaders, \
-    add_parse_cmds_for_loggers, add_parse_cmds_for_models, add_parse_cmds_for_opt, add_parse_cmds_for_trainers, \
-    type_ensure_strtobool
+    add_parse_cmds_for_loggers, add_parse_cmds_for_models, add_parse_cmds_for_opt, add_parse_cmds_for_opt_study, \
+    add_parse_cmds_for_trainers, type_ensure_strtobool
 from hypelcnn_amd.common.common_nn_ops import AugmentationInfo, TrainingResult, create_graph, \
     get_importer_from_name, get_model_from_name
 from hypelcnn_amd.common.common_ops import path_leaf, replace_abbrs
@@ -61,12 +69,15 @@ def perform_an_episode(flags, algorithm_params, model, base_log_path, backend=No
     summary_fn = add_classification_summaries(cross_entropy, learning_rate, flags.log_model_params, testing_nn_params,
                                               validation_nn_params, tensorboard_events=flags.tensorboard_events)
     start = time.time()
-    result = run_monitored_session(cross_entropy, base_log_path, class_range, flags.save_checkpoint_steps,
-                                   flags.validation_steps, train_step, required_steps, augmentation_info,
-                                   training_nn_params, training_tensor, testing_nn_params, testing_tensor,
-                                   validation_nn_params, validation_tensor, data_importer,
-                                   json.dumps(vars(flags), indent=3), json.dumps(algorithm_params, indent=3),
-                                   summary_fn=summary_fn)
+    try:
+        result = run_monitored_session(cross_entropy, base_log_path, class_range, flags.save_checkpoint_steps,
+                                       flags.validation_steps, train_step, required_steps, augmentation_info,
+                                       training_nn_params, training_tensor, testing_nn_params, testing_tensor,
+                                       validation_nn_params, validation_tensor, data_importer,
+                                       json.dumps(vars(flags), indent=3), json.dumps(algorithm_params, indent=3),
+                                       summary_fn=summary_fn)
+    finally:
+        train_step.ctx.close()  # the episode's plans, captured graphs and flat buffers (a study runs many episodes)
     print(f"Done training for {time.time() - start:.3f} sec")
     if flags.perform_validation:
         print(f"Validation accuracy={result.validation_accuracy:g}, Testing accuracy={result.test_accuracy:g}, "
@@ -109,13 +120,38 @@ def get_log_suffix(flags):
 def build_parser():
     parser = argparse.ArgumentParser()
     for add in (add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, add_parse_cmds_for_trainers,
-                add_parse_cmds_for_models, add_parse_cmds_for_importers, add_parse_cmds_for_app, add_parse_cmds_for_opt):
+                add_parse_cmds_for_models, add_parse_cmds_for_importers, add_parse_cmds_for_app, add_parse_cmds_for_opt,
+                add_parse_cmds_for_opt_study):
         add(parser)
     return parser
 
 
-def main(argv=None):
+def run_study(flags, nn_model, backend=None, callbacks=()):
+    """The reference's optimisation mode (:201-218): study "classification_opt", minimising the worst
+    1 - validation accuracy of --opt_run_count episodes per trial.  callbacks: see hyperopt.Study.optimize."""
+    from hypelcnn_amd.common import hyperopt
+    print("Running in hyper parameter optimization mode")
+    hyperopt.refuse_data_parallel("train_for_classification --flag_config_file_opt")
+    if not flags.perform_validation:
+        raise ValueError("--flag_config_file_opt minimises 1 - validation accuracy, and without --perform_validation an "
+                         "episode has no validation_accuracy: pass --perform_validation true")
+    flags_from_json_opt = json.load(open(flags.flag_config_file_opt, "r"))
+
+    def run_session(params, base_log_path):
+        return 1 - perform_an_episode(flags, params, nn_model, base_log_path, backend=backend).validation_accuracy
+
+    objective_func = functools.partial(hyperopt.objective, params=dict(vars(flags)),
+                                       params_from_json_opt=flags_from_json_opt, opt_run_count=flags.opt_run_count,
+                                       func_to_run=run_session, base_log_path=flags.base_log_path)
+    study = hyperopt.create_study("classification_opt", flags.opt_storage,
+                                  hyperopt.get_sampler(flags.opt_sampler, flags.opt_seed), load_if_exists=True)
+    return study.optimize(objective_func, n_trials=flags.opt_trial_count, callbacks=callbacks)
+
+
+def main(argv=None, backend=None):
     flags, _unknown = build_parser().parse_known_args(argv)  # unknown flags are ignored, as in the reference
+    if flags.flag_config_file_opt:
+        return run_study(flags, get_model_from_name(flags.model_name), backend)
     import torch
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
@@ -126,7 +162,8 @@ def main(argv=None):
         raise IOError("Algorithm parameter file is not given")
     algorithm_params = json.load(open(flags.algorithm_param_path, "r"))
     algorithm_params["batch_size"] = flags.batch_size  # the CLI overrides the JSON (reference :225)
-    return perform_an_episode(flags, algorithm_params, nn_model, os.path.join(flags.base_log_path, get_log_suffix(flags)))
+    return perform_an_episode(flags, algorithm_params, nn_model, os.path.join(flags.base_log_path, get_log_suffix(flags)),
+                              backend=backend)
 
 
 if __name__ == "__main__":

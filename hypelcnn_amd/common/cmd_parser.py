@@ -61,3 +61,13 @@ def add_parse_cmds_for_opt(parser):
                         help="Flag config file for hyper parameter optimization")
     parser.add_argument("--opt_trial_count", nargs="?", type=int, default=10, help="Trial count")
     parser.add_argument("--opt_run_count", nargs="?", type=int, default=3, help="Runs per trial")
+
+
+def add_parse_cmds_for_opt_study(parser):
+    """This package's additions to the reference's three (common/hyperopt.py); a group of their own, so that
+    add_parse_cmds_for_opt stays the reference's flag set."""
+    parser.add_argument("--opt_seed", nargs="?", type=int, default=None, help="Sampler seed (default: unseeded)")
+    parser.add_argument("--opt_sampler", nargs="?", type=str, default="tpe", choices=("tpe", "random"),
+                        help="Sampler of the study")
+    parser.add_argument("--opt_storage", nargs="?", type=str, default=None,
+                        help="SQLite file of the study (default: <study_name>.db in the working directory)")

@@ -551,6 +551,12 @@ class GraphContext:
             self._session.init_data_parallel()
         return self._session
 
+    def close(self):
+        """Release the device session (runtime.Session.close); session() would start a fresh one."""
+        if self._session is not None:
+            self._session.close()
+            self._session = None
+
 
 class LossFetch:
     """The `cross_entropy` tensor of the reference: value of the last executed training step."""

@@ -7,8 +7,19 @@ One loop iteration = one `session.run(global_step_inc_op)` of the reference with
 every phase (generator, discriminator[, feature discriminator]) is a pre-planned list of HIP launches replayed as
 a HIP graph; the paired samples stay resident in HBM.  --band_ratio_stats true also writes the band-ratio figure and
 its numbers for the closing statistic, band_ratio_<suffix>_<step>.pdf / .json, into the log directory
-(common/band_ratio.py)."""
+(common/band_ratio.py).
+
+--validate_while_training true installs the reference's peer validation hook on the training session: every
+--validation_steps steps the generators run forward on --validation_sample_count fixed samples, best_ratio_<suffix>.json
+and summaries.jsonl are updated in the log directory, and the session returns the best divergences seen instead of the
+closing statistic.  Hyper-parameter search, the reference's --flag_config_file_opt mode, minimises exactly that
+(common/hyperopt.py; the flag is set by the study):
+
+    python -m hypelcnn_amd.gan.gan_train_for_shadow --loader_name SyntheticDataLoader --path gulfport \
+        --pairing_method dummy --step 1000 --validation_steps 100 --flag_config_file_opt <json> \
+        --opt_trial_count 10 --opt_run_count 3 [--opt_seed 0] [--opt_sampler tpe|random] [--opt_storage <file>]"""
 import argparse
+import functools
 import json
 import os
 from types import SimpleNamespace
@@ -17,7 +28,8 @@ import numpy
 import torch
 
 from hypelcnn_amd.common.cmd_parser import add_parse_cmds_for_json_loader, add_parse_cmds_for_loaders, \
-    add_parse_cmds_for_loggers, add_parse_cmds_for_opt, add_parse_cmds_for_trainers, type_ensure_strtobool
+    add_parse_cmds_for_loggers, add_parse_cmds_for_opt, add_parse_cmds_for_opt_study, add_parse_cmds_for_trainers, \
+    type_ensure_strtobool
 from hypelcnn_amd.backend import Ref
 from hypelcnn_amd.common.common_nn_ops import get_loader_from_name
 from hypelcnn_amd.common.common_ops import replace_abbrs
@@ -45,6 +57,9 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--gen_disc_reg_scale", nargs="?", type=float, default=0.0001)
     parser.add_argument("--pairing_method", nargs="?", type=str, default="random")
     parser.add_argument("--band_ratio_stats", nargs="?", type=b, default=False)  # band-ratio figure + numbers, log dir
+    # the peer validation hook on the training session (best_ratio_*.json, summaries.jsonl, the best divergences as the
+    # session's result); off: the closing statistic alone, nothing but checkpoints in the log directory
+    parser.add_argument("--validate_while_training", nargs="?", const=True, type=b, default=False)
     parser.add_argument("--master", nargs="?", type=str, default="")      # TF1 parameter-server flags: accepted,
     parser.add_argument("--ps_tasks", nargs="?", type=int, default=0)     # ignored (vestigial)
     parser.add_argument("--task", nargs="?", type=int, default=0)
@@ -159,8 +174,9 @@ def save_gan_checkpoint(sess, log_dir, step):
     return path
 
 
-def gan_train(train_ops, iterator, log_dir, max_steps, save_checkpoint_steps=None, log_every=1000):
-    """reference :80-144: loop until the step budget or the data runs out; returns the last global step."""
+def gan_train(train_ops, iterator, log_dir, max_steps, save_checkpoint_steps=None, log_every=1000, hooks=()):
+    """reference :80-144: loop until the step budget or the data runs out; returns the last global step.
+    hooks: their after_run(step) is called after every step (the peer validation hook)."""
     sess = train_ops.ctx.session()
     while sess.global_step < max_steps:
         batch = iterator.next_batch()
@@ -172,6 +188,8 @@ def gan_train(train_ops, iterator, log_dir, max_steps, save_checkpoint_steps=Non
             print(f"Starting train step: {step}", {k: round(v, 5) for k, v in train_ops.losses().items()})
         if save_checkpoint_steps and log_dir and step % save_checkpoint_steps == 0:
             save_gan_checkpoint(sess, log_dir, step)
+        for hook in hooks:
+            hook.after_run(step)
     return sess.global_step
 
 
@@ -181,6 +199,8 @@ def run_session(params, base_log_path, backend=None):
     log_dir = f"{base_log_path}_{get_log_suffix(flags)}"
     neighborhood = 0  # 1x1 spectral "patches" (reference :249)
     loader = get_loader_from_name(flags.loader_name, flags.path)
+    if backend is not None and getattr(loader, "backend", backend) is None:
+        loader.backend = backend  # a scene prepared on the device is prepared on the backend the session runs on
     data_set = loader.load_data(neighborhood, True)
     shadow_map, shadow_ratio = loader.load_shadow_map(neighborhood, data_set)
     normal, shadow = read_hsi_data(loader, data_set, shadow_map, flags.pairing_method, get_sampling_map())
@@ -194,9 +214,48 @@ def run_session(params, base_log_path, backend=None):
     train_ops = wrapper.define_train_ops(the_gan_model, the_gan_loss, max_number_of_steps=flags.step,
                                          generator_lr=flags.generator_lr, discriminator_lr=flags.discriminator_lr,
                                          gen_discriminator_lr=flags.gen_discriminator_lr)
+    try:
+        return _train_and_score(flags, log_dir, loader, data_set, shadow_map, shadow_ratio, normal, shadow, bands, wrapper,
+                                tower, images_x, images_y, the_gan_model, the_gan_loss, train_ops)
+    finally:
+        train_ops.close()  # the episode's plans, captured graphs, pools and flat buffers (a study runs many episodes)
+
+
+def _peer_validation_hook(flags, log_dir, loader, data_set, shadow_map, shadow_ratio, bands, wrapper, images_x, images_y,
+                          the_gan_model, train_ops):
+    """The reference's peer validation hook (:270-272) on the training tower and its session; the chief rank writes."""
+    from hypelcnn_amd.classify.monitored_session_runner import is_chief
+    from hypelcnn_amd.common.device_scene import DeviceBasicDataSet
+    chief = is_chief()
+    if chief:
+        os.makedirs(log_dir, exist_ok=True)
+    ratio = shadow_ratio if shadow_ratio is not None else numpy.ones(bands, numpy.float32)
+    hook = wrapper.create_training_validation_hook(
+        the_gan_model, train_ops, images_x, images_y, data_set=data_set, loader=loader, log_dir=log_dir, neighborhood=0,
+        shadow_map=shadow_map, shadow_ratio=ratio, validation_iteration_count=flags.validation_steps,
+        validation_sample_count=flags.validation_sample_count, device_samples=isinstance(data_set, DeviceBasicDataSet))
+    hook.on_training_session(write_files=chief)
+    hook.band_ratio_stats = bool(getattr(flags, "band_ratio_stats", False))
+    return hook
+
+
+def _train_and_score(flags, log_dir, loader, data_set, shadow_map, shadow_ratio, normal, shadow, bands, wrapper, tower,
+                     images_x, images_y, the_gan_model, the_gan_loss, train_ops):
     sess = train_ops.ctx.session()
     iterator = PairIterator(normal, shadow, flags.batch_size, flags.step, shadow_ratio,
                             flags.regularization_support_rate, sess.backend.device, backend=sess.backend)
+    if getattr(flags, "validate_while_training", False):
+        hook = _peer_validation_hook(flags, log_dir, loader, data_set, shadow_map, shadow_ratio, bands, wrapper, images_x,
+                                     images_y, the_gan_model, train_ops)
+        gan_train(train_ops, iterator, log_dir, flags.step, save_checkpoint_steps=flags.validation_steps, hooks=[hook])
+        save_gan_checkpoint(sess, log_dir, sess.global_step)
+        # Use the return value for hyperparameter optimization (reference :302-305)
+        best_upper_div, best_mean_div = hook.get_best_upper_div(), hook.get_best_mean_div()
+        if best_upper_div is None or best_upper_div == []:
+            raise ValueError(f"--validate_while_training: no validation ran in {sess.global_step} steps with "
+                             f"--validation_steps {flags.validation_steps}")
+        return [max(best_upper_div) if isinstance(best_upper_div, list) else best_upper_div,
+                max(best_mean_div) if isinstance(best_mean_div, list) else best_mean_div]
     gan_train(train_ops, iterator, log_dir, flags.step, save_checkpoint_steps=flags.validation_steps)
     save_gan_checkpoint(sess, log_dir, sess.global_step)
     # final quality statistic on a sample of the pairs (the reference's PeerValidationHook tracks the same scalars)
@@ -224,21 +283,42 @@ def run_session(params, base_log_path, backend=None):
 def build_parser():
     parser = argparse.ArgumentParser()
     for add in (add_parse_cmds_for_loaders, add_parse_cmds_for_loggers, add_parse_cmds_for_trainers,
-                add_parse_cmds_for_json_loader, add_parse_cmds_for_app, add_parse_cmds_for_opt):
+                add_parse_cmds_for_json_loader, add_parse_cmds_for_app, add_parse_cmds_for_opt,
+                add_parse_cmds_for_opt_study):
         add(parser)
     return parser
 
 
-def main(argv=None):
+def run_study(flags, params, backend=None, callbacks=()):
+    """The reference's optimisation mode (:215-229): study "gan_shadow_opt", minimising the worst mean of the best
+    [upper, mean] divergences that the peer validation hook saw in --opt_run_count sessions per trial.
+    callbacks: see hyperopt.Study.optimize."""
+    from hypelcnn_amd.common import hyperopt
+    print("Running on hyper parameter optimization mode")
+    hyperopt.refuse_data_parallel("gan_train_for_shadow --flag_config_file_opt")
+    flags_from_json_opt = json.load(open(flags.flag_config_file_opt, "r"))
+    params = dict(params, validate_while_training=True)
+    objective_func = functools.partial(hyperopt.objective, params=params, params_from_json_opt=flags_from_json_opt,
+                                       opt_run_count=flags.opt_run_count,
+                                       func_to_run=functools.partial(run_session, backend=backend),
+                                       base_log_path=params["base_log_path"])
+    study = hyperopt.create_study("gan_shadow_opt", flags.opt_storage,
+                                  hyperopt.get_sampler(flags.opt_sampler, flags.opt_seed), load_if_exists=True)
+    return study.optimize(objective_func, n_trials=flags.opt_trial_count, callbacks=callbacks)
+
+
+def main(argv=None, backend=None):
     flags, _ = build_parser().parse_known_args(argv)
     params = dict(vars(flags))
     if flags.flag_config_file:
         params.update(json.load(open(flags.flag_config_file, "r")))
+    if params["flag_config_file_opt"]:
+        return run_study(SimpleNamespace(**params), params, backend)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl")
-    print("Output divergence values:", run_session(params, flags.base_log_path))
+    print("Output divergence values:", run_session(params, flags.base_log_path, backend=backend))
 
 
 if __name__ == "__main__":

@@ -100,6 +100,9 @@ class CUTWrapper(Wrapper):
     def get_train_hooks_fn(self):
         return lambda train_ops: [train_ops.run_step]
 
+    def create_training_validation_hook(self, model, train_ops, images_x, images_y, **hook_args):
+        return C.create_one_way_training_hook(model, train_ops, self._swap_inputs, images_x, images_y, **hook_args)
+
 
 class CUTInferenceWrapper(GANInferenceWrapper):
     """reference :668-670: the CUT generator lives in Model/Generator like the GAN's."""

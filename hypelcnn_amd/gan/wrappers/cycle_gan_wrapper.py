@@ -11,15 +11,24 @@ model_backward_generator_name = "ModelY2X"
 
 def create_base_validation_hook(data_set, loader, log_dir, neighborhood, shadow_map, shadow_ratio,
                                 validation_iteration_count, validation_sample_count, model_forward, model_backward,
-                                x_input_tensor, y_input_tensor, ctx):
+                                x_input_tensor, y_input_tensor, ctx, device_samples=False):
     """reference :22-45: X2Y scored on lit samples ("shadowed"), Y2X on shadowed samples with the inverse ratio."""
     common = dict(iteration_freq=validation_iteration_count, sample_count=validation_sample_count, log_dir=log_dir,
-                  loader=loader, data_set=data_set, neighborhood=neighborhood, shadow_map=shadow_map, ctx=ctx)
+                  loader=loader, data_set=data_set, neighborhood=neighborhood, shadow_map=shadow_map, ctx=ctx,
+                  device_samples=device_samples)
     shadowed = C.ValidationHook(shadow_ratio=shadow_ratio, input_tensor=x_input_tensor, infer_model=model_forward,
                                 fetch_shadows=False, name_suffix="shadowed", **common)
     de_shadowed = C.ValidationHook(shadow_ratio=1. / shadow_ratio, input_tensor=y_input_tensor,
                                    infer_model=model_backward, fetch_shadows=True, name_suffix="deshadowed", **common)
     return C.PeerValidationHook(shadowed, de_shadowed)
+
+
+def create_two_way_training_hook(model, train_ops, images_x, images_y, **hook_args):
+    """The peer hook of a two-generator model on the TRAINING tower's own symbols and session (the reference installs
+    its hook on the training session, gan_train_for_shadow.py:270-294): G_x2y(x) from x, G_y2x(y) from y."""
+    return create_base_validation_hook(model_forward=model.model_x2y.generated_data,
+                                       model_backward=model.model_y2x.generated_data, x_input_tensor=images_x,
+                                       y_input_tensor=images_y, ctx=train_ops.ctx, **hook_args)
 
 
 class CycleGANWrapper(Wrapper):
@@ -79,6 +88,9 @@ class CycleGANWrapper(Wrapper):
 
     def get_train_hooks_fn(self):
         return lambda train_ops: [train_ops.run_step]
+
+    def create_training_validation_hook(self, model, train_ops, images_x, images_y, **hook_args):
+        return create_two_way_training_hook(model, train_ops, images_x, images_y, **hook_args)
 
 
 class CycleGANInferenceWrapper(InferenceWrapper):

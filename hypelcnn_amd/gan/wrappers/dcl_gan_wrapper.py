@@ -6,7 +6,7 @@ import collections
 from hypelcnn_amd import graph as G
 from hypelcnn_amd.gan.wrappers import gan_common as C
 from hypelcnn_amd.gan.wrappers.cut_wrapper import cut_model, cut_phases, cut_train_ops
-from hypelcnn_amd.gan.wrappers.cycle_gan_wrapper import CycleGANInferenceWrapper
+from hypelcnn_amd.gan.wrappers.cycle_gan_wrapper import CycleGANInferenceWrapper, create_two_way_training_hook
 from hypelcnn_amd.gan.wrappers.wrapper import Wrapper
 
 DCLGANModel = collections.namedtuple("DCLGANModel", ("model_x2y", "model_y2x"))
@@ -49,6 +49,9 @@ class DCLGANWrapper(Wrapper):
 
     def get_train_hooks_fn(self):
         return lambda train_ops: [train_ops.run_step]
+
+    def create_training_validation_hook(self, model, train_ops, images_x, images_y, **hook_args):
+        return create_two_way_training_hook(model, train_ops, images_x, images_y, **hook_args)
 
 
 class DCLGANInferenceWrapper(CycleGANInferenceWrapper):

@@ -169,6 +169,12 @@ class GANTrainOps:
     def losses(self):
         return {k: ct.loss_value() for k, ct in self.last_losses.items()}
 
+    def close(self):
+        """End of an episode: the pooled batches, the compiled phases and the device session (GanContext.close)."""
+        self.pools.clear()
+        self.last_losses.clear()
+        self.ctx.close()
+
 
 class GanContext:
     """Holds the recorded tower's variable store and (lazily) the device session."""
@@ -190,6 +196,12 @@ class GanContext:
             self._session.finalize_variables(group_affinity=self.group_affinity)
             self._session.init_data_parallel()
         return self._session
+
+    def close(self):
+        """Release the device session (runtime.Session.close); session() would start a fresh one."""
+        if self._session is not None:
+            self._session.close()
+            self._session = None
 
 
 def define_standard_train_ops(gan_model, gan_loss, max_number_of_steps, generator_lr, discriminator_lr, backend=None):
@@ -282,8 +294,15 @@ class BaseValidationHook:
     def after_create_session(self, session=None, coord=None):
         pass
 
+    # the reference's hook fires on the iteration AFTER a multiple of the frequency (and so never on the last step of a
+    # run); a hook installed on a training session here (--validate_while_training) fires on the multiples themselves:
+    # the steps that are checkpointed, the closing step included, so that best_ratio_*.json names existing checkpoints
+    on_checkpoint_steps = False
+
     def _is_validation_itr(self, current_iteration):
         if self._iteration_frequency != 0:
+            if self.on_checkpoint_steps:
+                return current_iteration % self._iteration_frequency == 0
             return current_iteration % self._iteration_frequency == 1 and current_iteration != 1
         return True
 
@@ -308,6 +327,11 @@ class PeerValidationHook:
     def band_ratio_stats(self, on):
         for hook in self._validation_base_hooks:
             hook.band_ratio_stats = on
+
+    def on_training_session(self, write_files=True):
+        for hook in self._validation_base_hooks:
+            hook.on_training_session(write_files)
+        return self
 
     def after_create_session(self, session=None, coord=None):
         for hook in self._validation_base_hooks:
@@ -343,9 +367,12 @@ class ValidationHook(BaseValidationHook):
     generated tensor where it is)."""
 
     band_ratio_stats = False
+    write_files = True  # data parallel: every rank validates (the same parameters), only the chief writes
 
     def __init__(self, iteration_freq, sample_count, log_dir, loader, data_set, neighborhood, shadow_map, shadow_ratio,
-                 input_tensor, infer_model, name_suffix, fetch_shadows, ctx, seed=1234):
+                 input_tensor, infer_model, name_suffix, fetch_shadows, ctx, seed=1234, device_samples=False):
+        """device_samples: take the samples of a device-resident scene (common/device_scene.py) where they are -- one
+        gather on the device -- instead of through get_data_point, which downloads the scene."""
         super().__init__(iteration_freq, log_dir, shadow_ratio)
         self._ctx = ctx
         self._infer_model = infer_model
@@ -356,8 +383,16 @@ class ValidationHook(BaseValidationHook):
         self._bands = loader.get_band_measurements()
         self.sample_indices = sample_indices_for_testing(sample_count, neighborhood, shadow_map, fetch_shadows,
                                                          numpy.random.default_rng(seed))
-        self._data_sample_list = load_samples_for_testing(data_set, self.sample_indices)
+        self._data_sample_list = load_samples_on_device(data_set, self.sample_indices) if device_samples else \
+            load_samples_for_testing(data_set, self.sample_indices)
         self.last_stats = None
+
+    def on_training_session(self, write_files=True):
+        """The hook rides on a training session (--validate_while_training): it fires on the checkpointed steps, and
+        only the chief rank writes."""
+        self.on_checkpoint_steps = True
+        self.write_files = bool(write_files)
+        return self
 
     def last_divergences(self):
         """[mean divergence] of the last validation run ([] before one)"""
@@ -379,19 +414,34 @@ class ValidationHook(BaseValidationHook):
         div_mean, div_upper, mean, std = create_stats(generated, x, ratio)
         self.last_stats = (div_mean, div_upper, mean.cpu().numpy(), std.cpu().numpy())
         self.best_mean_div_holder.add_point(current_iteration, div_mean)
-        self.best_mean_div_holder.save(self._best_mean_div_addr)
         self.best_upper_div_holder.add_point(current_iteration, div_upper)
-        with open(os.path.join(self._log_dir, "summaries.jsonl"), "a") as f:
-            f.write(json.dumps({"step": int(current_iteration), f"divergence_{self._name_suffix}": div_mean}) + "\n")
+        if self.write_files:
+            self.best_mean_div_holder.save(self._best_mean_div_addr)
+            with open(os.path.join(self._log_dir, "summaries.jsonl"), "a") as f:
+                f.write(json.dumps({"step": int(current_iteration), f"divergence_{self._name_suffix}": div_mean}) + "\n")
         print(f"Validation metrics for {self._name_suffix} #{current_iteration}")
         print_overall_info(self.last_stats[2], self.last_stats[3])
-        if self.band_ratio_stats:
+        if self.band_ratio_stats and self.write_files:
             from hypelcnn_amd.common.band_ratio import band_ratio_stats, write_band_ratio
             self.last_band_ratio = write_band_ratio(
                 self._log_dir, f"band_ratio_{self._name_suffix}", current_iteration, self._bands,
                 band_ratio_stats(sess.backend, generated, x, ratio), "p50", "p10", "p90")
         print(f"Divergence for {self._name_suffix}; mean:{div_mean}, upper:{div_upper}")
         print(f"Best {self._name_suffix} options:{self.best_mean_div_holder}")
+
+
+def create_one_way_training_hook(model, train_ops, fetch_shadows, images_x, images_y, data_set, loader, log_dir,
+                                 neighborhood, shadow_map, shadow_ratio, validation_iteration_count,
+                                 validation_sample_count, device_samples=False):
+    """The hook of a one-generator model (gan_x2y / gan_y2x, cut_x2y / cut_y2x) on the TRAINING tower's own symbols and
+    session: the model's generated_data from the placeholder it is fed by -- y and the shadowed pixels with the inverse
+    ratio when the inputs are swapped (what GANInferenceWrapper.create_inference_hook builds on a tower of its own)."""
+    return ValidationHook(iteration_freq=validation_iteration_count, sample_count=validation_sample_count,
+                          log_dir=log_dir, loader=loader, data_set=data_set, neighborhood=neighborhood,
+                          shadow_map=shadow_map, shadow_ratio=adj_shadow_ratio(shadow_ratio, fetch_shadows),
+                          input_tensor=images_y if fetch_shadows else images_x, infer_model=model.generated_data,
+                          fetch_shadows=fetch_shadows, name_suffix="deshadowed" if fetch_shadows else "shadowed",
+                          ctx=train_ops.ctx, device_samples=device_samples)
 
 
 def sample_indices_for_testing(sample_count, neighborhood, shadow_map, fetch_shadows, rng):
@@ -410,6 +460,17 @@ def load_samples_for_testing(data_set, sample_indices):
     band_size = data_set.get_casi_band_count()
     samples = [data_set.get_data_point(int(x), int(y))[:, :, 0:band_size] for x, y in sample_indices]
     return numpy.ascontiguousarray(numpy.asarray(samples, numpy.float32).reshape(len(samples), band_size))
+
+
+def load_samples_on_device(data_set, sample_indices):
+    """load_samples_for_testing for a device-resident scene at neighbourhood 0: [n, bands] float32 gathered from the
+    prepared raster where it is (a device tensor; the scene is not downloaded)."""
+    n = int(data_set.neighborhood)
+    if n != 0:
+        raise ValueError("load_samples_on_device takes single spectra: a scene prepared with neighborhood 0")
+    casi = data_set.casi_dev
+    idx = torch.as_tensor(numpy.ascontiguousarray(sample_indices), dtype=torch.long).to(casi.device)
+    return casi[idx[:, 1], idx[:, 0], :data_set.get_casi_band_count()].contiguous()
 
 
 def print_overall_info(mean, std):

@@ -28,6 +28,22 @@ class CompiledTower:
         self._graph_all = None
         self._segments = None  # graph replay callables of [fwd + bwd up to sync point 0], [.. sync point 1], ...
         self.sync_points = list(getattr(plan, "sync_points", []))
+        self._captured = []  # replay callables of every graph capture() made: close() hands them back
+
+    def close(self):
+        """Destroy the captured graphs and let go of the plan: its buffers, tables and bound launches.  Called by
+        Session.close() on an idle device; the tower cannot run afterwards."""
+        for replay in self._captured:
+            self.be.destroy_graph(replay)
+        self._captured = []
+        self._segments = None
+        self._graph_fwd = self._graph_all = self._closed
+        self.fwd = self.bwd = ()
+        self.plan = None
+
+    @staticmethod
+    def _closed():
+        raise RuntimeError("this compiled tower was closed with its session")
 
     def serial_launches(self):
         """Every launch of the step, bound one by one (eager replay for per-kernel timing)."""
@@ -179,6 +195,7 @@ class CompiledTower:
         if settle is not None:
             settle()  # once for the whole chain of segments: no collective is issued between their captures
         graphs = [(kind, self.be.capture(v, True) if kind == "run" else v) for kind, v in items]
+        self._captured += [g for kind, g in graphs if kind == "run"]
         if len(graphs) == 1 and graphs[0][0] == "run":
             if self.bwd:
                 self._graph_all = graphs[0][1]
@@ -217,6 +234,26 @@ class Session:
         self.shared_inputs = {}  # (name, rows, c) -> device buffer shared by every GAN phase plan
         self.dist = None  # (world_size, rank) once init_data_parallel() ran
         self.sync_bn = False
+
+    def close(self):
+        """End of an episode: wait for the device, destroy every captured HIP graph, and drop the compiled towers, the
+        shared input slabs, the flat parameter / gradient / slot / state buffers and the pinned guard ring, so that the
+        allocator can hand the memory to the next session of the process (a hyper-parameter study runs many, with
+        different shapes).  Read what you need (state_dict, values) before.  Idempotent."""
+        if self.params is None and not self._compiled:
+            return
+        sync = getattr(self.backend, "synchronize", None)
+        if sync is not None:
+            sync()
+        for ct in self._compiled.values():
+            ct.close()
+        self._compiled.clear()
+        self.shared_inputs.clear()
+        for name, value in list(vars(self).items()):
+            if isinstance(value, torch.Tensor):
+                setattr(self, name, None)
+        if hasattr(self, "_guard_q"):  # (the verdict, _guard_bad, stays readable)
+            self._guard_q, self._guard_free = [], None
 
     # ---- variables ----
     def finalize_variables(self, rng=None, group_affinity=()):
