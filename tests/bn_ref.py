@@ -170,6 +170,8 @@ def _w(a):
 
 
 def pre_def(y, mean, rstd, beta):
+    if mean is None:                                   # a layer without batch norm: pre = xhat = y
+        return _w(y), _w(y)
     xhat = (_w(y) - _w(mean)) * _w(rstd)
     return xhat, xhat + _w(beta)
 
@@ -199,14 +201,15 @@ def fwd_f32(y, mean, rstd, beta, act, alpha):
 
 
 def bwd_def(dz, y, mean, rstd, beta, act, alpha, mask=None, stat_rows=None, sums=None):
-    """dict(dyh, xhat, s0, s1, dy).  sums: (s0, s1) to use instead of this matrix's own (the global-batch form)."""
+    """dict(dyh, xhat, s0, s1, dy).  sums: (s0, s1) to use instead of this matrix's own (the global-batch form).
+    mean None (with rstd and beta): a layer without batch norm, pre = xhat = y and dy = dyh (hypel_act_bias_bwd_reduce)."""
     xhat, pre = pre_def(y, mean, rstd, beta)
     g = _w(dz) if mask is None else _w(dz) * _w(mask)
     dyh = g * act_grad_def(pre, act, alpha)
     s0, s1 = dyh.sum(0), (dyh * xhat).sum(0)
     n = float(y.shape[0] if stat_rows is None else stat_rows)
     u0, u1 = (s0, s1) if sums is None else (_w(sums[0]), _w(sums[1]))
-    dy = _w(rstd) * (dyh - u0 / n - xhat * u1 / n)
+    dy = dyh if mean is None else _w(rstd) * (dyh - u0 / n - xhat * u1 / n)   # no statistics: dy = dyh
     return {"dyh": dyh, "xhat": xhat, "pre": pre, "s0": s0, "s1": s1, "dy": dy}
 
 
@@ -399,6 +402,8 @@ def _act_bounds(pre, e_pre, act, alpha):
 def pre_bound(y, mean, rstd, beta):
     """xhat = fl(fl(y - mean) * rstd): 2 U |xhat|; pre = fl(xhat + beta): one more rounding."""
     xhat, pre = pre_def(y, mean, rstd, beta)
+    if mean is None:                                   # pre = xhat = y, an input: no rounding
+        return np.zeros_like(xhat), np.zeros_like(xhat)
     e_x = 2 * U * np.abs(xhat) + TINY
     return e_x, e_x + rnd(pre)
 
@@ -452,6 +457,6 @@ def bwd_bounds(dz, y, mean, rstd, beta, act, alpha, mask, chunk_rows, form, stat
     xm = xhat * m1
     inner = (e_dyh + e_m0 + np.abs(xhat) * e_m1 + np.abs(m1) * e_x + rnd(xm)
              + 2 * U * (np.abs(dyh) + np.abs(m0) + np.abs(xm)))
-    e_dy = np.abs(_w(rstd)) * inner + rnd(d["dy"])
+    e_dy = e_dyh if mean is None else np.abs(_w(rstd)) * inner + rnd(d["dy"])   # no statistics: dy = dyh
     k = MARGIN * SLACK
     return {"s0": k * e_s0, "s1": k * e_s1, "dy": k * e_dy, "def": d}
