@@ -12,7 +12,7 @@ import torch
 
 from hypelcnn_amd.backend import (MATCH_BLOCK_COLS, MATCH_COL_CHUNK, MATCH_MAX_SPLITS, MATCH_ROW_CHUNK, MATCH_TILE, OUT_DTYPES,
                                   Ref)
-from hypelcnn_amd.common.device_scene import EXTREMA_SLICES
+from hypelcnn_amd.common.device_scene import EXTREMA_SLICES, resident_view
 
 LIMIT = 2 ** 31
 # hypel_match_ccorr_f32's splits.  Measured at the contest geometry (NOTES.md, "Template matching"): the launch gets
@@ -57,18 +57,8 @@ class _Band:
             a = numpy.asarray(array)
             if a.ndim != 2 or 0 in a.shape:
                 raise ValueError(f"device_match: the {what} must be a non-empty 2-D raster")
-            if a.dtype != numpy.float32:
-                a = a.astype(numpy.float32)
-            root = a
-            while isinstance(root.base, numpy.ndarray):
-                root = root.base
-            in_place = (root.flags.c_contiguous and root.dtype == a.dtype and root.size < LIMIT
-                        and all(n == 1 or (s > 0 and s % 4 == 0) for n, s in zip(a.shape, a.strides)))
-            if not in_place:
-                root = a = numpy.ascontiguousarray(a)
+            root, offset, (self.sy, self.sx) = resident_view(a, numpy.float32, root_limit=LIMIT)
             self.h, self.w = (int(v) for v in a.shape)
-            self.sy, self.sx = (0 if n == 1 else int(s) // 4 for n, s in zip(a.shape, a.strides))
-            offset = (a.__array_interface__["data"][0] - root.__array_interface__["data"][0]) // 4
             self.flat = backend.upload(root)
             self.ref = Ref(self.flat, offset)
         self.H, self.W = self.h * self.scale, self.w * self.scale

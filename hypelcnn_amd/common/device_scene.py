@@ -64,6 +64,26 @@ def percentile_from_ranks(a, b, t, dtype):
     return out.astype(dtype)
 
 
+def resident_view(a, dtype, root_limit=None):
+    """What to upload so that the kernels read the NumPy view `a`, as `dtype`, in place: -> (root, element offset of
+    a's first item in root, element strides with 0 for an axis of extent 1).  root is the array at the end of a's
+    .base chain where that one is C-contiguous, of this dtype and (root_limit) has fewer items than that, and a's
+    strides are positive multiples of the item size; else a contiguous copy of a."""
+    dtype = numpy.dtype(dtype)
+    if a.dtype != dtype:
+        a = a.astype(dtype)
+    root = a
+    while isinstance(root.base, numpy.ndarray):
+        root = root.base
+    item = dtype.itemsize
+    in_place = (root.flags.c_contiguous and root.dtype == dtype and (root_limit is None or root.size < root_limit)
+                and all(n == 1 or (s > 0 and s % item == 0) for n, s in zip(a.shape, a.strides)))
+    if not in_place:
+        root = a = numpy.ascontiguousarray(a)
+    offset = (a.__array_interface__["data"][0] - root.__array_interface__["data"][0]) // item
+    return root, offset, tuple(0 if n == 1 else int(s) // item for n, s in zip(a.shape, a.strides))
+
+
 class _Source:
     """A raster in device memory, as the kernels address it: flat byte tensor, element offset, (h, w, bands) and
     element strides.  A view whose root array is contiguous is uploaded as that root and read in place; a
@@ -85,20 +105,12 @@ class _Source:
         a = numpy.asarray(array)
         if a.ndim != 3 or a.dtype not in OUT_DTYPES:
             raise ValueError("scene rasters are [h, w, bands] of float32, uint16, int16 or uint8")
-        root = a
-        while isinstance(root.base, numpy.ndarray):
-            root = root.base
-        item = a.dtype.itemsize
-        in_place = root.flags.c_contiguous and root.dtype == a.dtype and all(n == 1 or (s > 0 and s % item == 0) for n, s in zip(a.shape, a.strides))
-        if not in_place:
-            root = a = numpy.ascontiguousarray(a)
+        root, offset, self.strides = resident_view(a, a.dtype)
         self.dtype = a.dtype
         self.code = OUT_DTYPES[a.dtype]
         self.h, self.w, self.bands = (int(v) for v in a.shape)
-        self.strides = tuple(0 if n == 1 else int(s) // item for n, s in zip(a.shape, a.strides))
-        offset = (a.__array_interface__["data"][0] - root.__array_interface__["data"][0]) // item
         self.bytes = torch.from_numpy(root.reshape(-1).view(numpy.uint8)).to(backend.device)
-        self.ref = Ref(self.bytes, offset * item)
+        self.ref = Ref(self.bytes, offset * a.dtype.itemsize)
 
     def geometry(self):
         return (self.h, self.w, self.bands) + self.strides

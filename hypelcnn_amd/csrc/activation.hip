@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -80,11 +81,6 @@ __device__ __forceinline__ void walk_spans(const float* __restrict__ src, int64_
     }
 }
 
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-
 // ---- range ----------------------------------------------------------------------------------------------------------
 struct RangeTake {
     float mn = FLT_MAX, mx = -FLT_MAX;
@@ -123,12 +119,9 @@ __global__ __launch_bounds__(THREADS) void view_range_kernel(const float* __rest
     __shared__ int64_t wnum[WAVES], wbad[WAVES];
     RangeTake f;
     walk_spans(src, rows, ld, cols, f);
-    float mn = f.mn, mx = f.mx;
-    for (int d = 32; d > 0; d >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, d));
-        mx = fmaxf(mx, __shfl_down(mx, d));
-    }
-    const int64_t num = wave_sum(f.num), bad = wave_sum(f.bad);
+    float mn = wave_reduce(f.mn, [](float a, float b) { return fminf(a, b); });
+    float mx = wave_reduce(f.mx, [](float a, float b) { return fmaxf(a, b); });
+    const int64_t num = wave_sum((int64_t)f.num), bad = wave_sum((int64_t)f.bad);
     if ((threadIdx.x & 63) == 0) {
         const int w = threadIdx.x >> 6;
         wmn[w] = mn, wmx[w] = mx, wnum[w] = num, wbad[w] = bad;
@@ -227,7 +220,7 @@ __global__ __launch_bounds__(THREADS) void view_histogram_kernel(const float* __
     __syncthreads();
     HistTake f{fe, hist, n_bins, fe[0], hi, (float)((double)n_bins / (last - first))};
     walk_spans(src, rows, ld, cols, f);
-    const int64_t out = wave_sum(f.outside);
+    const int64_t out = wave_sum((int64_t)f.outside);
     if ((tid & 63) == 0) wout[tid >> 6] = out;
     __syncthreads();
     for (int i = tid; i < n_bins; i += THREADS) {

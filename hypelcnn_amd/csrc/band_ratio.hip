@@ -13,6 +13,7 @@
 // 500 000 rows, which is all a wavefront-wide merge of equal counters, as summary.hip has it, could win back.)
 // Integer counts only: two calls give identical bits.
 #include "common.h"
+#include "wave.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -89,7 +90,7 @@ __global__ void __launch_bounds__(THREADS) band_ratio_kernel(const float* __rest
     // one integer add per block: adds to one address queue up behind each other, a few thousand of them cost more
     // than the ratios of the validation sample
     __shared__ unsigned int per_wave[THREADS / 64];
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
+    mine = wave_sum(mine);
     if (lane == 0) per_wave[wave] = mine;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -208,11 +209,7 @@ __global__ void __launch_bounds__(64) column_pick_kernel(uint32_t* __restrict__ 
     const uint32_t want = FIRST ? ranks.r[r] : sel[(int64_t)i * 2 + 1];
     const uint32_t prefix = FIRST ? 0u : sel[(int64_t)i * 2];
     const uint32_t s = c.x + c.y + c.z + c.w;
-    uint32_t incl = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
+    const uint32_t incl = wave_scan(s, WaveAdd());
     const uint32_t excl = incl - s;
     const unsigned long long hit = __ballot(want >= excl && want < incl);
     // (no lane only if `kept` was not the number of kept rows: the result is then meaningless, the accesses still safe)

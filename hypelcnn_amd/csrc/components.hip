@@ -11,20 +11,18 @@
 // device-scope atomics (another block, possibly on another XCD, may be lowering the same entry); a third launch walks
 // every pixel to its root.  No block waits for another one: a union that loses a race continues from what the atomic
 // returned.  Every walk is bounded by a step cap derived from h * w; running into it sets *status and gives up.
-#include "common.h"
+#include "compact.h"
 
 #define ST ((hipStream_t)stream)
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
 constexpr int TW = 64, TH = 16;             // a labelling tile
 constexpr int PER = TW * TH / THREADS;      // pixels of one thread in it
 constexpr int BORDER = TW + 2 * (TH - 1);   // pixels of a tile with a link that leaves it: first row, side columns
 constexpr int BORDER_THREADS = 128;
-constexpr int ITEMS = HYPEL_COMPACT_TILE / THREADS;
-static_assert(TW * TH % THREADS == 0 && HYPEL_COMPACT_TILE % THREADS == 0, "tiles are whole block-wide strips");
+static_assert(TW * TH % THREADS == 0, "a labelling tile is a whole number of block-wide strips");
 
 // ------------------------------------------------------------------------------------------------ union-find
 // LDS flavour: the tile's own table, workgroup-scope atomics.  A chain only ever descends, so TW * TH steps reach a
@@ -187,90 +185,21 @@ __global__ void __launch_bounds__(THREADS) flatten_kernel(const int32_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ compaction
-// The scheme of hypel_mask_compact_points_i32 with "p is its own root" as the predicate: a tile is HYPEL_COMPACT_TILE
-// consecutive pixels, wave k of the block owns its k-th quarter in ITEMS strips of 64, ranks inside a strip come from
-// a ballot, across strips, waves and tiles from sums in that fixed order.
-__device__ __forceinline__ unsigned long long root_ballot(const int32_t* __restrict__ root, int64_t n, int64_t p) {
-    return __ballot(p < n && root[p] == (int32_t)p);
-}
+// compact.h with "p is its own root" as the predicate.  comp[p] = rank for a root, -1 outside the mask; the other
+// pixels are written by spread_rank_kernel, which reads only the entries of roots -- those the rank launch wrote.
+struct IsRoot {
+    const int32_t* __restrict__ root;
+    __device__ __forceinline__ bool operator()(int64_t p) const { return root[p] == (int32_t)p; }
+};
 
-__global__ void __launch_bounds__(THREADS) root_count_kernel(const int32_t* __restrict__ root, int64_t n,
-                                                             int32_t* __restrict__ tile_count) {
-    __shared__ int wave_count[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * HYPEL_COMPACT_TILE + (int64_t)wv * 64 * ITEMS;
-    int count = 0;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) count += __popcll(root_ballot(root, n, base + j * 64 + lane));
-    if (lane == 0) wave_count[wv] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-        for (int k = 0; k < WAVES; ++k) sum += wave_count[k];
-        tile_count[blockIdx.x] = sum;
+struct RootRank {
+    const int32_t* __restrict__ root;
+    int32_t* __restrict__ comp;
+    __device__ __forceinline__ void operator()(int64_t p, int rank) const { comp[p] = rank; }
+    __device__ __forceinline__ void miss(int64_t p) const {
+        if (root[p] < 0) comp[p] = -1;
     }
-}
-
-// one block: tile_count[0 .. tiles) becomes its exclusive prefix sum in place, *total the sum
-__global__ void __launch_bounds__(THREADS) count_scan_kernel(int32_t* __restrict__ tile_count, int64_t tiles,
-                                                             int32_t* __restrict__ total) {
-    __shared__ int wave_sum[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int carry = 0;
-    for (int64_t t0 = 0; t0 < tiles; t0 += THREADS) {
-        const int64_t t = t0 + threadIdx.x;
-        const int own = t < tiles ? tile_count[t] : 0;
-        int v = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(v, d, 64);
-            if (lane >= d) v += o;
-        }
-        if (lane == 63) wave_sum[wv] = v;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < WAVES; ++k) {
-            if (k < wv) before += wave_sum[k];
-            all += wave_sum[k];
-        }
-        __syncthreads();
-        if (t < tiles) tile_count[t] = carry + before + v - own;
-        carry += all;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// comp[p] = rank for a root, -1 outside the mask; the other pixels are written by spread_rank_kernel, which reads
-// only the entries of roots -- those this launch wrote.
-__global__ void __launch_bounds__(THREADS) root_rank_kernel(const int32_t* __restrict__ root, int64_t n,
-                                                            const int32_t* __restrict__ tile_offset,
-                                                            int32_t* __restrict__ comp) {
-    __shared__ int wave_count[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * HYPEL_COMPACT_TILE + (int64_t)wv * 64 * ITEMS;
-    unsigned long long bits[ITEMS];
-    int count = 0;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        bits[j] = root_ballot(root, n, base + j * 64 + lane);
-        count += __popcll(bits[j]);
-    }
-    if (lane == 0) wave_count[wv] = count;
-    __syncthreads();
-    int at = tile_offset[blockIdx.x];
-    for (int k = 0; k < wv; ++k) at += wave_count[k];
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        const int64_t p = base + j * 64 + lane;
-        if ((bits[j] >> lane) & 1ull)
-            comp[p] = at + __popcll(bits[j] & below);
-        else if (p < n && root[p] < 0)
-            comp[p] = -1;
-        at += __popcll(bits[j]);
-    }
-}
+};
 
 __global__ void __launch_bounds__(THREADS) spread_rank_kernel(const int32_t* __restrict__ root, int64_t n,
                                                               int32_t* comp) {
@@ -396,10 +325,8 @@ extern "C" int hypel_components_compact_i32(const int32_t* root, int64_t h, int6
                                             int32_t* n_components, int32_t* ws, hypel_stream_t stream) {
     HYPEL_REQUIRE(root && comp && n_components && ws && root != comp, "hypel_components_compact_i32");
     HYPEL_REQUIRE(image_ok(h, w), "hypel_components_compact_i32");
-    const int64_t n = h * w, tiles = (n + HYPEL_COMPACT_TILE - 1) / HYPEL_COMPACT_TILE;
-    hipLaunchKernelGGL(root_count_kernel, dim3((unsigned)tiles), dim3(THREADS), 0, ST, root, n, ws);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(THREADS), 0, ST, ws, tiles, n_components);
-    hipLaunchKernelGGL(root_rank_kernel, dim3((unsigned)tiles), dim3(THREADS), 0, ST, root, n, ws, comp);
+    const int64_t n = h * w;
+    compact::launch(IsRoot{root}, RootRank{root, comp}, n, ws, n_components, ST);
     hipLaunchKernelGGL(spread_rank_kernel, dim3(hypel_grid_1d(n, THREADS)), dim3(THREADS), 0, ST, root, n, comp);
     HYPEL_CHECK_LAUNCH("hypel_components_compact_i32");
     return 0;

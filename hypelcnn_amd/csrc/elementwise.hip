@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wave.h"
 
 
 namespace {
@@ -762,18 +763,6 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int64_t ld
 }
 
 constexpr int RED_BLOCKS = 1024;
-
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    // wave64 shuffle reduce, then 4 waves through LDS
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    float t = 0.0f;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
 
 __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ a, int64_t lda,
                                                            const float* __restrict__ b, int64_t ldb, int64_t rows,

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
     const uint8_t* bf = bins + (int64_t)p.feature * ldn;
     int mine = 0;
     for (int i = tid; i < count; i += THREADS) mine += (int)bf[order_in[start + i]] <= p.bin;
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
+    mine = wave_sum(mine);
     if (lane == 0 && mine) atomicAdd(&n_left_s, mine);
     __syncthreads();
     const int n_left = n_left_s;
@@ -277,22 +278,14 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
             wcount[wave] = __popcll(bl);
             wcount[WAVES + wave] = __popcll(br);
         }
-        __syncthreads();
-        int before_l = 0, before_r = 0, all_l = 0, all_r = 0;
-        for (int w = 0; w < WAVES; ++w) {
-            const int cl = wcount[w], cr = wcount[WAVES + w];
-            if (w < wave) {
-                before_l += cl;
-                before_r += cr;
-            }
-            all_l += cl;
-            all_r += cr;
-        }
-        const unsigned long long below = (1ull << lane) - 1ull;
+        __syncthreads();  // one barrier for both sides
+        int before_l, before_r, all_l, all_r;
+        waves_before<WAVES>(wcount, before_l, all_l);
+        waves_before<WAVES>(wcount + WAVES, before_r, all_r);
         if (go_left)
-            order_out[start + run_l + before_l + __popcll(bl & below)] = s;
+            order_out[start + run_l + before_l + wave_rank(bl)] = s;
         else if (live)
-            order_out[start + n_left + run_r + before_r + __popcll(br & below)] = s;
+            order_out[start + n_left + run_r + before_r + wave_rank(br)] = s;
         run_l += all_l;
         run_r += all_r;
         __syncthreads();
@@ -308,23 +301,17 @@ __global__ __launch_bounds__(THREADS) void level_compact_kernel(const int32_t* _
                                                                 int32_t* __restrict__ counter) {
     __shared__ int wcount[WAVES];
     __shared__ int overflow;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) overflow = 0;
     int run = 0;
     for (int base = 0; base < n_active; base += THREADS) {
         const int a = base + tid;
         const int n_left = a < n_active ? split_ws[a] : 0;
         const bool sp = n_left > 0;
-        const unsigned long long b = __ballot(sp);
-        if (lane == 0) wcount[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < WAVES; ++w) {
-            if (w < wave) before += wcount[w];
-            all += wcount[w];
-        }
+        int before, all;
+        const int rank = block_offsets<WAVES>(sp, wcount, before, all);
         if (sp) {
-            const int r = run + before + __popcll(b & ((1ull << lane) - 1ull));
+            const int r = run + before + rank;
             const int tree = active[4 * a], start = active[4 * a + 1], count = active[4 * a + 2], node = active[4 * a + 3];
             const int l = node_base + 2 * r;
             if (l + 1 < node_capacity) {

@@ -4,6 +4,7 @@
 // runs the whole 7-layer generator of a sample out of LDS (activations, skip sums and weights never leave the
 // CU), and the backward kernel recomputes that forward instead of storing 13 intermediate tensors.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -527,17 +528,6 @@ __global__ __launch_bounds__(GT_SLOT_THREADS * GT_WAVES) void gan_generator_bwd_
 }
 
 // ------------------------------------------------------------------------------------- losses
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    float t = 0.0f;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
-
 // mode 0: weight*mean((a-target)^2)   mode 1: weight*mean(|a-b|)   mode 2: weight*mean(a)
 __global__ __launch_bounds__(256) void gan_loss_partial_kernel(int mode, const float* __restrict__ a, int64_t lda,
                                                                 const float* __restrict__ b, int64_t ldb,

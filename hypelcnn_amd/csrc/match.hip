@@ -14,6 +14,7 @@
 // outputs, four 16x16x4 MFMA tiles that share the A fragment.  m runs over 15 + HT rows, so 15 / (15 + HT) of the MFMA
 // work multiplies zeros.  The next chunk's samples are fetched into registers while the current one is multiplied.
 #include "common.h"
+#include "wave.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -166,12 +167,6 @@ __global__ void __launch_bounds__(THREADS) add_partials_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ window energy
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;  // the same bits in every lane: both operands of every addition are exchanged
-}
-
 // a wavefront per (source row, 64 outputs): rows[r][x] = sum_{j < win_w} I'(r * s, x + j)^2
 __global__ void __launch_bounds__(THREADS) row_window_kernel(Band img, int32_t h_src, int32_t win_w, int32_t wout,
                                                              int32_t n_seg, double* __restrict__ rows) {
@@ -187,20 +182,13 @@ __global__ void __launch_bounds__(THREADS) row_window_kernel(Band img, int32_t h
     };
     double part = 0.0;
     for (int t = lane; t < win_w; t += 64) part += sq((int64_t)x0 + t);
-    const double first = wave_sum(part);
+    const double first = wave_reduce_all(part, WaveAdd());  // the same bits in every lane
     // output x0 + lane = the first window + what entered - what left on the way there: two inclusive scans, shifted
     // by one lane
-    double lv = sq((int64_t)x0 + lane), en = sq((int64_t)x0 + win_w + lane);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double a = __shfl_up(lv, d, 64), b = __shfl_up(en, d, 64);
-        if (lane >= d) {
-            lv += a;
-            en += b;
-        }
-    }
-    lv = __shfl_up(lv, 1, 64);
-    en = __shfl_up(en, 1, 64);
+    double lv = wave_scan(sq((int64_t)x0 + lane), WaveAdd());
+    double en = wave_scan(sq((int64_t)x0 + win_w + lane), WaveAdd());
+    lv = wave_up(lv, 1);
+    en = wave_up(en, 1);
     if (lane == 0) lv = en = 0.0;
     // (a sum of squares: what the subtraction leaves below zero over a stretch of zeros is rounding)
     if (x0 + lane < wout) rows[(int64_t)r * wout + x0 + lane] = fmax((first + en) - lv, 0.0);
@@ -246,11 +234,7 @@ __global__ void __launch_bounds__(THREADS) score_kernel(const float* __restrict_
         const unsigned long long cand = ((unsigned long long)sortable(r) << 32) | (0xffffffffu - (uint32_t)p);
         best = cand > best ? cand : best;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(best, d, 64);
-        best = o > best ? o : best;
-    }
+    best = wave_reduce_all(best, [](unsigned long long a, unsigned long long o) { return o > a ? o : a; });
     if ((threadIdx.x & 63) == 0 && best != 0ull) atomicMax(key, best);
 }
 

@@ -8,7 +8,7 @@
 // All of them stream bytes: lanes run along a row on consecutive addresses, ranks inside a wave come from a ballot
 // and a population count, ranks across waves and blocks from prefix sums in a fixed order -- no atomics, so two runs
 // write identical bytes.
-#include "common.h"
+#include "compact.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -17,18 +17,12 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr int FAR = 0x3fffffff;  // "no set pixel in this row": |dy| + FAR cannot wrap
-constexpr int ITEMS = HYPEL_COMPACT_TILE / THREADS;  // pixels of one lane in a compaction tile
-static_assert(HYPEL_COMPACT_TILE % THREADS == 0, "a compaction tile is a whole number of block-wide strips");
 
 // running maximum over the block in thread order (reverse: from the last thread down), own value included; every
 // thread also receives the block's maximum
 __device__ __forceinline__ int block_scan_max(int v, bool reverse, int* wave_max, int* total) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = reverse ? __shfl_down(v, d, 64) : __shfl_up(v, d, 64);
-        if (reverse ? lane + d < 64 : lane >= d) v = o > v ? o : v;
-    }
+    v = wave_scan(v, [](int a, int o) { return o > a ? o : a; }, reverse);
     if (lane == (reverse ? 0 : 63)) wave_max[wv] = v;
     __syncthreads();
     int before = -FAR, all = -FAR;
@@ -104,87 +98,22 @@ __global__ void __launch_bounds__(THREADS) pair_masks_kernel(const uint8_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------ compaction
-// A tile is HYPEL_COMPACT_TILE consecutive pixels of the flattened mask, one per block; wave k of the block owns the
-// k-th quarter and reads it in ITEMS strips of 64 consecutive bytes, so scan order is (tile, wave, strip, lane).
-__device__ __forceinline__ unsigned long long strip_ballot(const uint8_t* __restrict__ mask, int64_t n, int64_t p) {
-    return __ballot(p < n && mask[p] != 0);
-}
+// compact.h with "the mask byte is set" as the predicate; a hit writes its (x, y) to its rank's row
+struct MaskSet {
+    const uint8_t* __restrict__ mask;
+    __device__ __forceinline__ bool operator()(int64_t p) const { return mask[p] != 0; }
+};
 
-__global__ void __launch_bounds__(THREADS) tile_count_kernel(const uint8_t* __restrict__ mask, int64_t n,
-                                                             int32_t* __restrict__ tile_count) {
-    __shared__ int wave_count[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * HYPEL_COMPACT_TILE + (int64_t)wv * 64 * ITEMS;
-    int count = 0;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) count += __popcll(strip_ballot(mask, n, base + j * 64 + lane));
-    if (lane == 0) wave_count[wv] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-        for (int k = 0; k < WAVES; ++k) sum += wave_count[k];
-        tile_count[blockIdx.x] = sum;
+struct PointRow {
+    int2* __restrict__ points;
+    int64_t capacity;
+    uint32_t w;
+    __device__ __forceinline__ void operator()(int64_t p, int rank) const {
+        const uint32_t y = (uint32_t)p / w;  // h * w < 2^31
+        if (rank < capacity) points[rank] = make_int2((int)((uint32_t)p - y * w), (int)y);
     }
-}
-
-// one block: tile_count[0 .. tiles) becomes its exclusive prefix sum in place, *count the total
-__global__ void __launch_bounds__(THREADS) tile_scan_kernel(int32_t* __restrict__ tile_count, int64_t tiles,
-                                                            int32_t* __restrict__ count) {
-    __shared__ int wave_sum[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int carry = 0;
-    for (int64_t t0 = 0; t0 < tiles; t0 += THREADS) {
-        const int64_t t = t0 + threadIdx.x;
-        const int own = t < tiles ? tile_count[t] : 0;
-        int v = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(v, d, 64);
-            if (lane >= d) v += o;
-        }
-        if (lane == 63) wave_sum[wv] = v;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < WAVES; ++k) {
-            if (k < wv) before += wave_sum[k];
-            all += wave_sum[k];
-        }
-        __syncthreads();
-        if (t < tiles) tile_count[t] = carry + before + v - own;
-        carry += all;
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
-__global__ void __launch_bounds__(THREADS) tile_scatter_kernel(const uint8_t* __restrict__ mask, int64_t n, int64_t w,
-                                                               const int32_t* __restrict__ tile_offset,
-                                                               int64_t capacity, int2* __restrict__ points) {
-    __shared__ int wave_count[WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * HYPEL_COMPACT_TILE + (int64_t)wv * 64 * ITEMS;
-    unsigned long long bits[ITEMS];
-    int count = 0;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        bits[j] = strip_ballot(mask, n, base + j * 64 + lane);
-        count += __popcll(bits[j]);
-    }
-    if (lane == 0) wave_count[wv] = count;
-    __syncthreads();
-    int64_t at = tile_offset[blockIdx.x];
-    for (int k = 0; k < wv; ++k) at += wave_count[k];
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        if ((bits[j] >> lane) & 1ull) {
-            const int64_t p = base + j * 64 + lane, dst = at + __popcll(bits[j] & below);
-            const uint32_t y = (uint32_t)p / (uint32_t)w;  // h * w < 2^31
-            if (dst < capacity) points[dst] = make_int2((int)((uint32_t)p - y * (uint32_t)w), (int)y);
-        }
-        at += __popcll(bits[j]);
-    }
-}
+    __device__ __forceinline__ void miss(int64_t) const {}
+};
 
 // ------------------------------------------------------------------------------------------------ expansion
 __global__ void __launch_bounds__(THREADS) points_expand_kernel(const int2* __restrict__ points, int64_t body,
@@ -223,11 +152,7 @@ extern "C" int hypel_mask_compact_points_i32(const uint8_t* mask, int64_t h, int
     HYPEL_REQUIRE(mask && points && count && ws && capacity >= 0, "hypel_mask_compact_points_i32");
     HYPEL_REQUIRE(h > 0 && w > 0 && h < (1ll << 31) && w < (1ll << 31) && h * w < (1ll << 31),
                   "hypel_mask_compact_points_i32");
-    const int64_t n = h * w, tiles = (n + HYPEL_COMPACT_TILE - 1) / HYPEL_COMPACT_TILE;
-    hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(THREADS), 0, ST, mask, n, ws);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(THREADS), 0, ST, ws, tiles, count);
-    hipLaunchKernelGGL(tile_scatter_kernel, dim3((unsigned)tiles), dim3(THREADS), 0, ST, mask, n, w, ws, capacity,
-                       (int2*)points);
+    compact::launch(MaskSet{mask}, PointRow{(int2*)points, capacity, (uint32_t)w}, h * w, ws, count, ST);
     HYPEL_CHECK_LAUNCH("hypel_mask_compact_points_i32");
     return 0;
 }

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -127,27 +128,25 @@ __device__ __forceinline__ void take(Acc& acc, unsigned* hist, const float* flim
 
 // Fixed-order reduction of one Partial per thread to thread 0 (shuffle tree inside a wavefront, then the wavefronts in
 // order).
+__device__ __forceinline__ Partial merged(Partial p, const Partial& q) {
+    p.mn = fmin(p.mn, q.mn);
+    p.mx = fmax(p.mx, q.mx);
+    p.sum += q.sum;
+    p.sq += q.sq;
+    p.num += q.num;
+    p.bad += q.bad;
+    return p;
+}
+__device__ __forceinline__ Partial wave_down(Partial p, int d) {  // (for wave_reduce)
+    return Partial{__shfl_down(p.mn, d), __shfl_down(p.mx, d), __shfl_down(p.sum, d),
+                   __shfl_down(p.sq, d), __shfl_down(p.num, d), __shfl_down(p.bad, d)};
+}
 __device__ __forceinline__ Partial block_reduce(Partial p, Partial* wred) {
-    for (int d = 32; d > 0; d >>= 1) {
-        p.mn = fmin(p.mn, __shfl_down(p.mn, d));
-        p.mx = fmax(p.mx, __shfl_down(p.mx, d));
-        p.sum += __shfl_down(p.sum, d);
-        p.sq += __shfl_down(p.sq, d);
-        p.num += __shfl_down(p.num, d);
-        p.bad += __shfl_down(p.bad, d);
-    }
+    p = wave_reduce(p, [](Partial a, Partial b) { return merged(a, b); });
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = p;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < WAVES; ++w) {
-            const Partial q = wred[w];
-            p.mn = fmin(p.mn, q.mn);
-            p.mx = fmax(p.mx, q.mx);
-            p.sum += q.sum;
-            p.sq += q.sq;
-            p.num += q.num;
-            p.bad += q.bad;
-        }
+        for (int w = 1; w < WAVES; ++w) p = merged(p, wred[w]);
     }
     return p;
 }
@@ -241,15 +240,7 @@ __global__ __launch_bounds__(THREADS) void summary_final_kernel(const int64_t* _
         return;
     }
     Partial p = {DBL_MAX, -DBL_MAX, 0.0, 0.0, 0, 0};
-    for (int64_t s = prefix[seg] + threadIdx.x; s < prefix[seg + 1]; s += THREADS) {
-        const Partial q = parts[s];
-        p.mn = fmin(p.mn, q.mn);
-        p.mx = fmax(p.mx, q.mx);
-        p.sum += q.sum;
-        p.sq += q.sq;
-        p.num += q.num;
-        p.bad += q.bad;
-    }
+    for (int64_t s = prefix[seg] + threadIdx.x; s < prefix[seg + 1]; s += THREADS) p = merged(p, parts[s]);
     p = block_reduce(p, wred);
     if (threadIdx.x == 0) {
         double* o = stats + 5 * (int64_t)seg;

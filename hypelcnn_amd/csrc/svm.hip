@@ -11,6 +11,7 @@
 //   scatter_coef   the multipliers of one gamma's jobs -> a dense coefficient matrix over all training rows
 //   vote_score     vote's rule per (row, cell) -> the number of correct rows per cell
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -18,12 +19,6 @@ constexpr int SVM_THREADS = 256;
 constexpr int SVM_WAVES = SVM_THREADS / 64;
 constexpr double SVM_TAU = 1e-12;  // libsvm's floor of a non-positive curvature
 constexpr int SVM_LDS_BYTES = 48 * 1024;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // ---- rows - mean, |row|^2 ------------------------------------------------------------------------------------------
 // one wave per row; the sum of squares is taken over the values as STORED (after the fp32 subtraction), in fp64, so
@@ -168,20 +163,14 @@ struct MaxIdx {
 __device__ __forceinline__ MaxIdx max_idx(MaxIdx a, MaxIdx b) {
     return (b.v > a.v || (b.v == a.v && b.i > a.i)) ? b : a;
 }
+__device__ __forceinline__ MaxIdx wave_down(MaxIdx m, int d) {  // (for wave_reduce)
+    return MaxIdx{__shfl_down(m.v, d, 64), __shfl_down(m.i, d, 64)};
+}
 __device__ __forceinline__ MaxIdx wave_max_idx(MaxIdx m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        MaxIdx t;
-        t.v = __shfl_down(m.v, o, 64);
-        t.i = __shfl_down(m.i, o, 64);
-        m = max_idx(m, t);
-    }
-    return m;
+    return wave_reduce(m, [](MaxIdx a, MaxIdx b) { return max_idx(a, b); });
 }
 __device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-    return v;
+    return wave_reduce(v, [](double a, double b) { return fmax(a, b); });
 }
 
 // One workgroup = one pair problem (hypel_svm_smo_ovo: one class pair of a fit; hypel_svm_smo_grid: one class pair of one
@@ -497,8 +486,7 @@ __global__ void __launch_bounds__(SVM_THREADS) svm_vote_score_kernel(const float
             hit += best == truth[r];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) hit += __shfl_down(hit, o, 64);
+    hit = wave_sum(hit);
     if (lane == 0) part[wave] = hit;
     __syncthreads();
     if (tid == 0) {

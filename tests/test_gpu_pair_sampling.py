@@ -81,7 +81,10 @@ def compact_raw(be, mask, h, w):
     return points.cpu().numpy().reshape(n, 2), int(count.cpu()[0])
 
 
-@pytest.mark.parametrize("shape", [(1, 1), (1, 255), (1, 256), (1, 257), (1, 65537), (130, 259)])
+BIG = (1, 256 * COMPACT_TILE + 1)  # 257 tiles: the one-block scan over the tile counts takes a second trip
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 255), (1, 256), (1, 257), (1, 65537), (130, 259), BIG])
 def test_compaction(be, shape):
     h, w = shape
     n = h * w
@@ -90,7 +93,7 @@ def test_compaction(be, shape):
     one[h - 1, w - 1] = 3
     masks = {"none": np.zeros((h, w), np.uint8), "one": one, "all": np.ones((h, w), np.uint8),
              "random": (rng.random((h, w)) < 0.4).astype(np.uint8)}
-    if shape == (130, 259):
+    if shape in ((130, 259), BIG):
         masks = {"all": masks["all"], "random": masks["random"]}
     for name, mask in masks.items():
         ys, xs = np.nonzero(mask)
