@@ -18,32 +18,21 @@ import os
 
 import numpy as np
 
-from . import abi, graph as G
-from .backend import COPY_BLOCK_DTYPE, GEMM_BM, MTILE_DTYPE, REDUCE_ENTRY_DTYPE, SEG_DTYPE, Ref
-from .gemm_tables import SEG_PAIR_FLAG, GemmTables, Launch  # noqa: F401 (re-exported: tests and tools build tables through plan)
+from . import abi, gemm_policy, gemm_tables as T, graph as G
+from .backend import COPY_BLOCK_DTYPE, GEMM_BM, REDUCE_ENTRY_DTYPE, Ref
+# (the flag bits of the ABI, the tables and the launch record are re-exported: tests and tools reach them through plan;
+# how a product is cut into launches -- and every tunable of that -- lives in gemm_policy and is read through it)
+from .gemm_tables import (GEMM_MFMA16X4, GEMM_MULTI_SPLIT6, GEMM_PAIRED_SEGS, GEMM_SINGLE_SEG, GEMM_SPLIT6,  # noqa: F401
+                          GEMM_VAR_N, SEG_PAIR_FLAG, GemmShape, GemmTables, Launch)
 
+MSE_PARTIALS = abi.const("HYPEL_MSE_PARTIALS")
 STAT_CHUNK_ROWS = 256  # upper bound; see stat_chunk_rows()
 STAT_BLOCKS = 256            # blocks per 64-column stripe aimed at
-
-
-def stat_chunk_rows(rows):
-    """Rows per partial-reduction block: ~256 blocks per 64-column stripe, between 16 and 256 rows each
-    (a thread walks chunk/4 rows serially, so short matrices get short chunks)."""
-    c = (rows + STAT_BLOCKS - 1) // STAT_BLOCKS
-    c = max(16, min(STAT_CHUNK_ROWS, c))
-    return (c + 3) // 4 * 4
 WGRAD_ROW_CHUNK = 512
-TARGET_BLOCKS = 1536  # blocks a filter-gradient product is split towards
-WGRAD_MAX_SPLITS = 64
-WGRAD_MIN_SPLITS = 0  # 0 = one split per 64 batch rows once a launch fills the device unsplit
 DGRAD_MAX_SEGS = 18  # segments per data-gradient tile (0 = never split)
 MAX_TAPS_PER_TILE = 9  # taps per forward tile of a multi-kernel level
 L2_CHUNK_BYTES = int(3.5 * (1 << 20))  # X working set an XCD's L2 keeps
-SPLITK_BELOW = 400    # FC-shaped products with fewer 128x64 blocks are cut along K
-SPLITK_TARGET = 768  # ... into slices that give about this many blocks
 TAP_SPLIT_MIN_BATCH = 64  # below this a pixel block has too few rows for splitting to pay
-
-
 # bias + leaky-ReLU of a normaliser-less fully-connected layer in the product's epilogue (HYPEL_GEMM_ACT_*): no post-op launch
 ACT_IN_GEMM = True
 SMALL_BN_ROWS = 1024  # hypel_bn_act_small_*: rows kept in registers (32 row lanes x 32 rows)
@@ -51,34 +40,6 @@ SMALL_BN_ROWS = 1024  # hypel_bn_act_small_*: rows kept in registers (32 row lan
 # collected and go out as ONE hypel_seg_gemm_multi_f32 per tile width (+ ONE hypel_reduce_splits_multi_f32) at the end
 # of the backward pass (and at every data-parallel sync point).  A step's twenty ~25 us launch ramps/drains become three.
 MERGE_WGRAD = True
-
-
-class Storage:
-    """Where a SymTensor lives for a given batch size."""
-
-    def __init__(self, buf, nb, ld, pixmap, ch_off, c, npix):
-        self.buf = buf
-        self.nb = nb
-        self.ld = ld
-        self.pixmap = pixmap
-        self.ch_off = ch_off
-        self.c = c
-        self.npix = npix
-
-    def pix_off(self, p):
-        q = p if self.pixmap is None else self.pixmap[p]
-        return q * self.nb * self.ld + self.ch_off
-
-    @property
-    def contiguous(self):
-        return self.pixmap is None
-
-    @property
-    def rows(self):
-        return self.npix * self.nb
-
-
-MSE_PARTIALS = abi.const("HYPEL_MSE_PARTIALS")
 DP_SYNC_WORK = 0.5  # share of the filter-gradient work before the sync point
 # Gradient buckets of the data-parallel exchange: two by default (one sync point: >= 60 % of the bytes leave under the
 # second half of the backward pass).  More buckets are available for large models -- one sync point per DP_BUCKET_BYTES
@@ -89,48 +50,6 @@ DP_SYNC_WORK = 0.5  # share of the filter-gradient work before the sync point
 DP_TWO_BUCKET_BYTES = int(float(os.environ.get("HYPEL_DP_TWO_BUCKET_MB", "1048576")) * (1 << 20))
 DP_BUCKET_BYTES = int(float(os.environ.get("HYPEL_DP_BUCKET_MB", "256")) * (1 << 20))
 DP_MAX_BUCKETS = 8
-HINT_OVERRIDE = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("HYPEL_HINT_OVERRIDE", "").split(",") if kv)}
-RESIDENT_BLOCKS_64 = 6 * 256  # 128x64 (and multi-segment 128x32) blocks the device holds at once
-GEMM_SINGLE_SEG = abi.const("HYPEL_GEMM_SINGLE_SEG")
-GEMM_PAIRED_SEGS = abi.const("HYPEL_GEMM_PAIRED_SEGS")  # (bit of `accumulate`)
-GEMM_BK = 32  # reduction columns per k-tile of the kernel
-# fp32 products on the bf16 matrix cores with three-way split operands and six partial products (include/hypel.h
-# HYPEL_GEMM_SPLIT6): "0" = never, "6" = wherever the launch is eligible and large enough (widths by column count),
-# "6:W" = the same with the tile width forced to hint W (1 = 128x32, 2 = 128x64, 3 = 128x128; per-launch A/B).
-# HYPEL_SPLIT_OVERRIDE="fwd:conv_dec_0=3,dgrad:conv_dec_0=0": per launch tag, 0 = fp32 MFMA kernel.
-GEMM_SPLIT6 = abi.const("HYPEL_GEMM_SPLIT6")  # (bit of `accumulate`)
-GEMM_MULTI_SPLIT6 = abi.const("HYPEL_GEMM_MULTI_SPLIT6")  # (bit of hypel_seg_gemm_multi_f32's tile_width)
-_gs = os.environ.get("HYPEL_GEMM_SPLIT", "6").split(":")
-GEMM_SPLIT = int(_gs[0] or 0)
-GEMM_SPLIT_WIDTH = int(_gs[1]) if len(_gs) > 1 else 0
-GEMM_SPLIT_MIN_FLOPS = float(os.environ.get("HYPEL_GEMM_SPLIT_MIN_GFLOP", "2")) * 1e9  # ... of the launch at SPLIT_NOMINAL_BATCH samples
-SPLIT_NOMINAL_BATCH = 1024  # batch the size rule prices a classifier launch at (the kernel family is chosen per layer, not per batch)
-SPLIT_NOMINAL_BATCH_GAN = 4096  # ... and a GAN train op's (PhasePlan: the pair batch of BASELINE's CUT configuration)
-# narrow products stage a whole 128-row A tile per 32 output columns: the split costs more than the matrix rate returns
-# (H13 level 1, 30 filters per branch: 382 -> 397 us forward, 103 -> 95 TFLOP/s filter gradient; per-launch A/B, round 5)
-GEMM_SPLIT_MIN_N = 32
-SPLIT_OVERRIDE = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("HYPEL_SPLIT_OVERRIDE", "").split(",") if kv)}
-# K-slice records for the split-operand kernels (include/hypel.h HYPEL_TILE_PLAIN; round-5 verdict item 1).  The 128-wide
-# split blocks have 512 resident slots (two per CU), a third of what the fp32 kernels had: a data gradient of 392 x 4 = 1 568
-# equal blocks runs 3.06 rounds and pays for 4, and the 392 blocks of a multi-kernel level's data gradient are all resident
-# at once and the launch lasts as long as its heaviest tile (the centre pixel sums 1.57x the mean).  The planner SIMULATES the
-# launch -- list scheduling of the blocks in table order on 64 slots per XCD -- for a few slicings (every tile above a K
-# threshold cut into equal slices; the tiles of each XCD's last, partly filled round cut into s slices) and takes the best
-# one if it beats the unsliced launch by KSLICE_MIN_GAIN.  Slices >= 1 write plain partials to scratch, one
-# hypel_reduce_splits_multi_sized_f32 adds them in slice order.
-KSLICE_MIN_GAIN = 0.10
-KSLICE_OVERHEAD_K = 24   # fixed cost of a block in reduction columns (prologue, pipeline fill, epilogue)
-KSLICE_MIN_K = 48        # shortest slice (reduction columns)
-KSLICE_MAX_SLICES = 16
-KSLICE_FRAC_MIN = 0.7    # smallest threshold (fraction of the launch's heaviest tile) above which tiles are sliced.  Same box
-#                          (profiles/r6_exp_kslice.txt), the 60-filter level's data gradient, 392 tiles: unsliced 319 us; threshold
-#                          0.7 (496 records) 279 us; 0.5 (688: a second round) 299; 0.25 (960) 267 -- but with three times the
-#                          partial traffic; the simulation, which knows nothing of two blocks sharing a CU, prefers 0.25
-KSLICE_REDUCE_COST_K = 55  # the reduce launch behind a sliced launch (~6 us), in reduction columns of a 128 x 128 block
-KSLICE_SLOTS = {1: 768, 2: 512, 3: 512}  # resident blocks of the split kernels by tile-width hint (3 / 2 / 2 per CU)
-SPLIT6_BN = {1: 32, 2: 64, 3: 128}  # output columns of their blocks, by the same hint
-GEMM_MFMA16X4 = abi.const("HYPEL_GEMM_MFMA16X4")  # 128x64 blocks on the 16x16x4 MFMA (merged level, <= 16 filters)
-GEMM_VAR_N = abi.const("HYPEL_GEMM_VAR_N")  # tile records carry their group's column count
 # Merged multi-kernel levels (include/hypel.h): the nested branches of a level share one packed weight image
 # W_pack[offset][Cin][C]; per output pixel and ring of input offsets ONE product on the column range of the branches
 # that contain the ring.  HYPEL_MERGE_LEVELS: comma list of the passes that use it -- "fwd", "dgrad", "wgrad"; default all
@@ -172,13 +91,56 @@ MERGE_SPLIT_KPARTS = False  # channel parts (L2_CHUNK_BYTES) for a merged forwar
 MERGE_FWD_HINT = 2
 
 
-# Same-box A/B of the planner's constants without editing the file: HYPEL_PLAN_SET="GEMM_SPLIT_MIN_N=64,TARGET_BLOCKS=768"
-# (integers / floats; names must exist in this module).  Not read by any test or benchmark default.
+# Same-box A/B of the planner's constants without editing a file: HYPEL_PLAN_SET="GEMM_SPLIT_MIN_N=64,TARGET_BLOCKS=768"
+# (integers / floats; names must exist in this module or in gemm_policy, whichever is the constant's one home).  Not read
+# by any test or benchmark default.
+def _numeric_constants(module_vars):
+    return {k for k, v in module_vars.items() if isinstance(v, (bool, int, float)) and not k.startswith("_")}
+
+
+_both = _numeric_constants(globals()) & _numeric_constants(vars(gemm_policy))
+if _both:
+    raise ImportError(f"planner constants {sorted(_both)} are defined in hypelcnn_amd.plan AND hypelcnn_amd.gemm_policy: "
+                      "a constant has one home")
 for _kv in filter(None, os.environ.get("HYPEL_PLAN_SET", "").split(",")):
     _k, _, _v = _kv.partition("=")
-    if not isinstance(globals().get(_k), (bool, int, float)) or _k.startswith("_"):
-        raise ValueError(f"HYPEL_PLAN_SET: {_k!r} is not a numeric constant of hypelcnn_amd.plan")
-    globals()[_k] = type(globals()[_k])(float(_v)) if not isinstance(globals()[_k], bool) else bool(int(_v))
+    _home = next((m for m in (globals(), vars(gemm_policy)) if _k in _numeric_constants(m)), None)
+    if _home is None:
+        raise ValueError(f"HYPEL_PLAN_SET: {_k!r} is not a numeric constant of hypelcnn_amd.plan or hypelcnn_amd.gemm_policy")
+    _home[_k] = type(_home[_k])(float(_v)) if not isinstance(_home[_k], bool) else bool(int(_v))
+
+
+def stat_chunk_rows(rows):
+    """Rows per partial-reduction block: ~256 blocks per 64-column stripe, between 16 and 256 rows each
+    (a thread walks chunk/4 rows serially, so short matrices get short chunks)."""
+    c = (rows + STAT_BLOCKS - 1) // STAT_BLOCKS
+    c = max(16, min(STAT_CHUNK_ROWS, c))
+    return (c + 3) // 4 * 4
+
+
+class Storage:
+    """Where a SymTensor lives for a given batch size."""
+
+    def __init__(self, buf, nb, ld, pixmap, ch_off, c, npix):
+        self.buf = buf
+        self.nb = nb
+        self.ld = ld
+        self.pixmap = pixmap
+        self.ch_off = ch_off
+        self.c = c
+        self.npix = npix
+
+    def pix_off(self, p):
+        q = p if self.pixmap is None else self.pixmap[p]
+        return q * self.nb * self.ld + self.ch_off
+
+    @property
+    def contiguous(self):
+        return self.pixmap is None
+
+    @property
+    def rows(self):
+        return self.npix * self.nb
 
 
 class TowerPlan:
@@ -307,255 +269,32 @@ class TowerPlan:
                 raise RuntimeError(f"variables {a.name} / {b.name} of a merged level are not contiguous")
 
     # ------------------------------------------------------------------ gemm emission
-    def _split_k(self, tables, n, lda, ta, ldb, tb, ldc):
-        """FC-shaped products have too few 128x128 output tiles to fill 256 CUs (fc_0 forward: 64 blocks;
-        image_gen_net_4 data gradient: 32).  When the output is one dense range, cut every group's K into S
-        slices that write partial slabs; hypel_reduce_splits_f32 sums them in a fixed order."""
-        groups = tables.groups
-        if ldc != n or not groups:
-            return None
-        n_nt = (n + 63) // 64 if n > 32 else 1
-        blocks = sum((rows + GEMM_BM - 1) // GEMM_BM for _, _, rows in groups) * n_nt
-        kmax = max(sum(k for _, _, k in gs) for _, gs, _ in groups)
-        if blocks >= SPLITK_BELOW or kmax < 512:
-            return None
-        S = min((SPLITK_TARGET + blocks - 1) // blocks, kmax // 128, 32)
-        if S < 2:
-            return None
-        order = sorted(groups, key=lambda g: g[0])
-        c_min = order[0][0]
-        pos = c_min
-        for c_off, _, rows in order:  # dense, gap-free cover
-            if c_off != pos:
-                return None
-            pos += rows * n
-        count = pos - c_min
-        if c_min % n:
-            return None
-        out = GemmTables()
-        for c_off, gs, rows in groups:
-            for s, part in enumerate(self._cut_segments(gs, S, lda if ta else 1, 1 if tb else ldb, grain=GEMM_BK)):
-                out.add_group(s * count + (c_off - c_min), part, rows)
-        return out, S, c_min, count
-
-    @staticmethod
-    def _tile_hint(tables, n, ta, tb, folded):
-        """Tile-width hint for hypel_seg_gemm_f32 (bits 8-9 of `accumulate`), from the per-launch A/B measurements in
-        profiles/r1_gemm_tile_choice*.txt (HYPELCNN at N=1024 and DUALCNN at N=512): 1 = 128x32, 2 = 128x64.
-        Wide tiles win whenever a launch has plenty of blocks; narrow ones balance small launches, and the data
-        gradients that also gather the shortcut gradient in their epilogue (more, shorter epilogues overlap better)."""
-        if n <= 32:
-            return 0
-        n_tiles = sum((rows + GEMM_BM - 1) // GEMM_BM for _, _, rows in tables.groups)
-        blocks64 = n_tiles * ((n + 63) // 64)
-        if tb and not ta:
-            ks = [k for _, segs, _ in tables.groups for _, _, k in segs]
-            if ks and sum(ks) / len(ks) < 48:
-                # short segments: per-k-tile overhead dominates, keep the wide tile -- unless that leaves the launch
-                # with under ~1000 blocks (the n = 120 data gradient of the 15-filter level: 142 us on 128x32 tiles,
-                # 154 on 128x64, round-2 A/B with paired segments)
-                if blocks64 < 1000:
-                    return 1
-                # ... and unless the 64-wide tiling overflows the resident capacity (6 blocks per CU) by a few blocks: the
-                # level-1 data gradient of H13 (392 x 4 = 1568 on 1536) then ends in a round of 32 lone blocks, and the
-                # 32-wide tiling (3136 blocks, two even rounds) is 46 us faster per step
-                over = blocks64 % RESIDENT_BLOCKS_64
-                return 1 if blocks64 < 2 * RESIDENT_BLOCKS_64 and 0 < over <= RESIDENT_BLOCKS_64 // 10 else 2
-            if folded and blocks64 < 4000:
-                return 1
-            return 1 if blocks64 < 900 else 2
-        if ta:
-            return 1 if blocks64 < 900 else 2
-        # forward.  Round-2 per-launch A/B of the three tile widths (tools/gemm_microbench.py, HYPEL_GEMM_FORCE_WIDTH):
-        # single-segment products (1x1 convolutions, n <= 512) run fastest on 128x32 tiles -- except n = 480, which
-        # tiles 5 x 96 without padding and whose 392 x 5 blocks are just under two resident rounds of the 128x96
-        # variant (conv_dec_0 218 vs 227 (32) vs 244 (64) us; conv_enc_2 129 vs 134 vs 138) -- multi-segment levels
-        # and the very wide dense layers on 128x64.
-        if n <= 512 and all(len(segs) == 1 for _, segs, _ in tables.groups):
-            if n >= 480 and n % 96 == 0:
-                return 3
-            return 1
-        return 1 if blocks64 < 768 else 2
-
+    # (what a product needs is decided here, per node; how it becomes launches -- split-K, tile width, kernel family,
+    # K-slices, filter-gradient splits -- in gemm_policy; the tables are built in gemm_tables.  The emitters below ask the
+    # policy, call the table function, allocate, upload, keep the tables alive and append Launches.)
     def nominal_batch(self):
-        return SPLIT_NOMINAL_BATCH
+        return gemm_policy.SPLIT_NOMINAL_BATCH
 
-    @staticmethod
-    def _split6_width(n):
-        """Tile-width hint of a split-operand launch by its column count: 128x128 blocks unless the last column tile
-        would be more than half empty."""
-        if GEMM_SPLIT_WIDTH:
-            return GEMM_SPLIT_WIDTH
-        if n <= 32:
-            return 1
-        rem = n % 128
-        return 2 if n <= 64 or 0 < rem <= 64 and n < 256 else 3
+    def _split6(self, tag, tables, shape, flags, paired, in_multi=False):
+        return gemm_policy.split6(tag, tables, shape, flags, paired, self.nb, self.nominal_batch(), in_multi=in_multi)
 
-    def _split6(self, tag, tables, n, ta, tb, flags, paired, in_multi=False):
-        """0 = fp32 MFMA kernel, else the tile-width hint of the split-operand kernel for this launch.  in_multi: a product
-        of the merged filter-gradient launch -- it shares its launch with the other products of its width class, so its
-        own size does not matter (left on the fp32 kernels, the few small ones formed a 102 us launch of 4.4 GFLOP).
-        The choice is a function of the LAYER, not of the batch: the size rule prices the launch at SPLIT_NOMINAL_BATCH
-        samples (every product of the path is linear in the batch), so that a sample meets the same arithmetic at batch
-        64, 512 and 1024 and on 1 or 8 ranks (round-5 verdict: the FLOP count of the launch itself made it batch-dependent)."""
-        eligible = n > 16 and not (ta and tb) and not (flags & ~GEMM_VAR_N) and not paired
-        if tag in SPLIT_OVERRIDE:
-            w = SPLIT_OVERRIDE[tag]
-            if w and not eligible:
-                raise ValueError(f"HYPEL_SPLIT_OVERRIDE: launch {tag!r} (n = {n}, trans = {int(bool(ta))}{int(bool(tb))}, "
-                                 f"flags = {flags:#x}, paired segments = {bool(paired)}) cannot run on the split-operand "
-                                 "kernels (they need n > 16, a plain NN / NT / TN product, no 16x16x4 / activation epilogue)")
-            if w not in (0, 1, 2, 3):
-                raise ValueError(f"HYPEL_SPLIT_OVERRIDE: width hint {w} for {tag!r} (0 = fp32 kernel, 1 / 2 / 3 = 128x32 / x64 / x128)")
-            return w
-        if GEMM_SPLIT != 6 or n <= GEMM_SPLIT_MIN_N or not eligible:
-            return 0
-        if in_multi:
-            return self._split6_width(n)
-        macs = sum(rows * sum(k for _, _, k in gs) * tables.n_of(gi, n) for gi, (_, gs, rows) in enumerate(tables.groups))
-        if 2 * macs * self.nominal_batch() < GEMM_SPLIT_MIN_FLOPS * self.nb:
-            return 0
-        return self._split6_width(n)
+    def _upload(self, array):
+        """Upload a host table and keep it alive with the plan."""
+        self.tables.append(self.be.upload(array))
+        return Ref(self.tables[-1])
 
-    @staticmethod
-    def _kslice_makespan(shares, extra, slots):
-        """Simulated duration of a launch: shares = eight lists of block costs in dispatch order, extra = block costs dealt
-        heaviest first to the end of the least loaded share (GemmTables.finalize does the same); every XCD runs its list on
-        slots / 8 block slots, next block to the slot that frees first."""
-        import heapq
-        shares = [list(sh) for sh in shares]
-        work = [sum(sh) for sh in shares]
-        for c in sorted(extra, reverse=True):
-            x = min(range(8), key=lambda i: (work[i], i))
-            shares[x].append(c)
-            work[x] += c
-        per = max(1, slots // 8)
-        worst = 0.0
-        for sh in shares:
-            free = [0.0] * per
-            for c in sh:
-                t = heapq.heappop(free)
-                heapq.heappush(free, t + c)
-            worst = max(worst, max(free))
-        return worst
-
-    def _kslice(self, tables, n, ta, tb, lda, ldb, width_hint):
-        """Choose K-slices for a launch on the split kernels (see KSLICE_MIN_GAIN above).  Returns None (leave the launch
-        alone) or {group index: number of slices}."""
-        groups = tables.groups
-        bn = SPLIT6_BN[width_hint]
-        slots = KSLICE_SLOTS[width_hint]
-        ct = (n + bn - 1) // bn
-        ov = KSLICE_OVERHEAD_K
-        # tile records in dispatch order (GemmTables.finalize: key-major, heavy first), one entry per record
-        order = []
-        for gi, (c_off, gs, rows) in enumerate(groups):
-            ksum = sum(k for _, _, k in gs)
-            for m0 in range(0, rows, GEMM_BM):
-                key = (tables.keys[gi] if tables.keys[gi] is not None else m0 // GEMM_BM, tables.subkeys[gi])
-                order.append((key, -ksum * min(GEMM_BM, rows - m0), gi, ksum))
-        order.sort(key=lambda t: (t[0], t[1]))
-
-        def shares_of(recs):
-            q, r = divmod(len(recs), 8)
-            out, pos = [], 0
-            for x in range(8):
-                cnt = q + (1 if x < r else 0)
-                out.append(recs[pos:pos + cnt])
-                pos += cnt
-            return out
-
-        def evaluate(slices):  # slices: {gi: s}
-            main = [t for t in order if slices.get(t[2], 1) == 1]
-            extra, pieces = [], 0
-            for t in order:
-                s_ = slices.get(t[2], 1)
-                if s_ > 1:
-                    extra += [t[3] / s_ + ov] * (s_ * ct)
-                    pieces += (s_ - 1) * ct
-            sh = [[t[3] + ov for t in share for _ in range(ct)] for share in shares_of(main)]
-            # + what the partials cost: a 128 x bn partial is written, read back and added into the output (~3 passes of
-            # 512 bn bytes at ~4 TB/s; one reduction column of a 128 x 128 block is ~0.11 us), + the reduce launch (~6 us)
-            traffic = pieces * (3 * 512 * bn / 4e12) / (0.11e-6 * bn / 128)
-            return self._kslice_makespan(sh, extra, slots) + (traffic + KSLICE_REDUCE_COST_K if pieces else 0)
-
-        base = evaluate({})
-        kmax = max(t[3] for t in order)
-        cands = []
-        for f in (0.75, 0.6, 0.5, 0.4, 0.33, 0.25):  # every tile above a threshold, in equal slices
-            if f < KSLICE_FRAC_MIN:
-                continue
-            T = max(kmax * f, KSLICE_MIN_K)
-            sl = {}
-            for gi, (c_off, gs, rows) in enumerate(groups):
-                ksum = sum(k for _, _, k in gs)
-                s_ = min(KSLICE_MAX_SLICES, -(-ksum // int(T)), max(1, ksum // KSLICE_MIN_K))
-                if s_ > 1:
-                    sl[gi] = s_
-            if sl:
-                cands.append(sl)
-        per = max(1, slots // 8)
-        single_tile_groups = all(rows <= GEMM_BM for _, _, rows in groups)
-        for s_ in (2, 3, 4, 6, 8, 12, 16):  # the tiles of each XCD's last, partly filled round
-            sl = {}
-            for share in shares_of(order):
-                tail_blocks = (len(share) * ct) % per
-                if tail_blocks == 0 or tail_blocks * s_ > per + per // 4:
-                    continue
-                for t in share[len(share) - (-(-tail_blocks // ct)):]:
-                    if t[3] // s_ >= KSLICE_MIN_K:
-                        sl[t[2]] = s_
-            if sl and single_tile_groups:  # (a group = one tile record there: slicing a group slices exactly that tile)
-                cands.append(sl)
-        best, best_t = None, base
-        for sl in cands:
-            t = evaluate(sl)
-            if t < best_t:
-                best, best_t = sl, t
-        if best is None or best_t > base * (1.0 - KSLICE_MIN_GAIN):
-            return None
-        return best
-
-    @staticmethod
-    def _group_per_tile(tables, lda, ldc):
-        """The same launch with one group per 128-row tile record (A not transposed: rows of A = rows of C)."""
-        out = GemmTables()
-        for gi, (c_off, gs, rows) in enumerate(tables.groups):
-            for m0 in range(0, rows, GEMM_BM):
-                key = tables.keys[gi] if tables.keys[gi] is not None else m0 // GEMM_BM
-                out.add_group(c_off + m0 * int(ldc), [(a + m0 * int(lda), b, k) for (a, b, k) in gs], min(GEMM_BM, rows - m0),
-                              key=key, subkey=tables.subkeys[gi])
-        return out
-
-    @staticmethod
-    def _cut_segments(gs, s_, a_ks, b_ks, grain=16):
-        """Cut a segment list into s_ slices of (nearly) equal reduction length, at multiples of `grain` columns of the
-        whole list (16: the split kernels' k-tile; GEMM_BK: the fp32 kernels'); a_ks / b_ks = element distance of one
-        reduction column in A / B."""
-        ktot = sum(k for _, _, k in gs)
-        cuts = [min(ktot, (ktot * i // s_ + grain - 1) // grain * grain) for i in range(s_)] + [ktot]
-        parts = [[] for _ in range(s_)]
-        base = 0
-        for (a_off, b_off, k) in gs:
-            for i in range(s_):
-                lo, hi = max(cuts[i], base), min(cuts[i + 1], base + k)
-                if hi > lo:
-                    parts[i].append((a_off + (lo - base) * a_ks, b_off + (lo - base) * b_ks, hi - lo))
-            base += k
-        return parts
-
-    def _emit_gemm(self, lst, tables, n, a_ref, lda, ta, b_ref, ldb, tb, c_ref, ldc, bias_ref, accumulate, tag,
-                   allow_split=True, res=None, stats=None, pair=False, hint=None, flags=0, kslice=False, sp6=None):
+    def _emit_gemm(self, lst, tables, shape, a_ref, b_ref, c_ref, bias_ref, accumulate, tag, allow_split=True, res=None,
+                   stats=None, pair=False, hint=None, flags=0, kslice=False, sp6=None):
         """res = (ref, ld, start_ref or None): fold a shortcut gradient into the epilogue (hypel_seg_gemm_res_f32).
         stats = floats of the per-tile statistics scratch: hypel_seg_gemm_stats_f32 (single group, no accumulate).
         kslice: the launch may be balanced with K-slice records (dense output, ldc = n).
         sp6: the kernel family, when the caller already chose it (_split6) to shape the tables."""
-        split = self._split_k(tables, n, lda, ta, ldb, tb, ldc) if allow_split and res is None else None
+        n, lda, ta, ldb, tb, ldc = shape
+        split = gemm_policy.split_k(tables, shape) if allow_split and res is None else None
         if split is not None:
             stab, S, c_min, count = split
             pos = len(lst)
-            self._emit_gemm(lst, stab, n, a_ref, lda, ta, b_ref, ldb, tb, c_ref, ldc, None, 0, tag + "/splitk",
-                            allow_split=False)
+            self._emit_gemm(lst, stab, shape, a_ref, b_ref, c_ref, None, 0, tag + "/splitk", allow_split=False)
             self._scratch(lst[pos], "c", "scratch_wgrad", S * count)
             l2 = Launch("reduce_splits_f32", (None, count, S, c_ref + c_min, count, int(accumulate), bias_ref, int(n), 0),
                         nbytes=4 * count * (S + 1), tag="splitk-reduce")
@@ -564,12 +303,11 @@ class TowerPlan:
             return
         pair = bool(pair and not ta and tb and n > 16 and stats is None)
         if hint is None:
-            hint = self._tile_hint(tables, n, ta, tb, res is not None)
-        if HINT_OVERRIDE and tag in HINT_OVERRIDE:  # per-launch A/B: HYPEL_HINT_OVERRIDE="fwd:conv_enc_2=1,dgrad:fc_0=2"
-            hint = HINT_OVERRIDE[tag]
+            hint = gemm_policy.tile_hint(tables, shape, res is not None)
+        hint = gemm_policy.HINT_OVERRIDE.get(tag, hint)
         single_seg = bool(not ta and all(len(segs) == 1 for _, segs, _ in tables.groups))
         if sp6 is None:
-            sp6 = self._split6(tag, tables, n, ta, tb, flags,
+            sp6 = self._split6(tag, tables, shape, flags,
                                pair and any(k <= 16 for _, gs, _ in tables.groups for _, _, k in gs))
         if sp6:
             pair, hint, single_seg = False, sp6, False
@@ -577,20 +315,19 @@ class TowerPlan:
         if (sp6 and kslice and stats is None and not flags and int(ldc) == int(n) and not (ta and tb)
                 and tables.groups and not any(tables.ns)):
             # (one group per 128-row tile record first: a 1x1 convolution's data gradient is ONE group of 50 176 rows)
-            per_tile = tables if ta or all(rows <= GEMM_BM for _, _, rows in tables.groups) else self._group_per_tile(tables, lda, ldc)
-            slices = self._kslice(per_tile, n, ta, tb, lda, ldb, sp6)
+            per_tile = tables if ta or all(rows <= GEMM_BM for _, _, rows in tables.groups) else T.group_per_tile(tables, lda, ldc)
+            slices = gemm_policy.kslice(per_tile, shape, sp6)
             if slices:
-                tables, reduce_after = self._apply_kslices(per_tile, slices, n, lda, ta, ldb, tb, c_ref, ldc, tag)
+                tables, reduce_after = self._apply_kslices(per_tile, slices, shape, c_ref, tag)
         garr, sarr, tarr, macs = tables.finalize(n, pair=pair)
         if len(tarr) == 0:
             return
-        g_t, s_t, t_t = self.be.upload(garr), self.be.upload(sarr), self.be.upload(tarr)
-        self.tables += [g_t, s_t, t_t]
+        g_r, s_r, t_r = (self._upload(a) for a in (garr, sarr, tarr))
         # the launch's `accumulate` word (include/hypel.h): bit 0, the tile-width hint in bits 8-9, the flag bits
         word = (int(accumulate) | hint << 8 | int(flags) | (GEMM_SPLIT6 if sp6 else 0)
                 | (GEMM_PAIRED_SEGS if pair and tables.paired else 0) | (GEMM_SINGLE_SEG if single_seg and not flags else 0))
-        args = (a_ref, int(lda), int(ta), b_ref, int(ldb), int(tb), c_ref, int(ldc), int(n), Ref(g_t), Ref(s_t),
-                Ref(t_t), int(len(tarr)), bias_ref, word)
+        args = (a_ref, int(lda), int(ta), b_ref, int(ldb), int(tb), c_ref, int(ldc), int(n), g_r, s_r, t_r,
+                int(len(tarr)), bias_ref, word)
         name = "seg_gemm_f32"
         if res is not None:
             name = "seg_gemm_res_f32"
@@ -599,7 +336,7 @@ class TowerPlan:
             assert len(tables.groups) == 1 and not (word & 1) and int(ldc) == int(n)
             name = "seg_gemm_stats_f32"
             args = args + (None,)
-        l = Launch(name, args, flops=2 * macs, nbytes=tables.compulsory_bytes(n, lda, ta, ldb, tb), tag=tag)
+        l = Launch(name, args, flops=2 * macs, nbytes=tables.compulsory_bytes(shape), tag=tag)
         if stats is not None:
             self._scratch(l, "stats_partial", "scratch_partial", stats)
         lst.append(l)
@@ -607,36 +344,16 @@ class TowerPlan:
             l.meta["kslices"] = reduce_after.meta["kslices"]
             lst.append(reduce_after)
 
-    def _apply_kslices(self, tables, slices, n, lda, ta, ldb, tb, c_ref, ldc, tag):
+    def _apply_kslices(self, tables, slices, shape, c_ref, tag):
         """The tables with the chosen groups cut into K-slices + the launch that adds the partials to the output."""
-        from .backend import TILE_PLAIN
-        a_ks = int(lda) if ta else 1
-        b_ks = 1 if tb else int(ldb)
-        kid = self._kslice_bufs
+        sname = f"kslice:{self._kslice_bufs}"
         self._kslice_bufs += 1
-        need = sum((s_ - 1) * tables.groups[gi][2] * int(ldc) for gi, s_ in slices.items())
-        sname = f"kslice:{kid}"
-        self._alloc(sname, need)
-        c_rel = self._param_rel(c_ref)
-        scratch_from_c = self._param_rel(self._ref(sname)) - c_rel
-        out = GemmTables()
-        entries, spos = [], 0
-        for gi, (c_off, gs, rows) in enumerate(tables.groups):
-            s_ = slices.get(gi, 1)
-            if s_ == 1:
-                out.add_group(c_off, gs, rows, key=tables.keys[gi], subkey=tables.subkeys[gi])
-                continue
-            parts = self._cut_segments(gs, s_, a_ks, b_ks)
-            region = rows * int(ldc)
-            out.add_group(c_off, parts[0], rows, key=tables.keys[gi], subkey=tables.subkeys[gi], tail=True)
-            for i in range(1, s_):
-                out.add_group(scratch_from_c + spos + (i - 1) * region, parts[i], rows, flags=TILE_PLAIN, tail=True)
-            entries.append((self._param_rel(self._ref(sname, spos)), c_rel + c_off, region, region, s_ - 1, 1))
-            spos += (s_ - 1) * region
-        earr = np.array(entries, REDUCE_ENTRY_DTYPE)
-        e_t = self.be.upload(earr)
-        self.tables.append(e_t)
-        red = Launch("reduce_splits_multi_sized_f32", (Ref(self.sess.params), Ref(e_t), int(len(earr)),
+        self._alloc(sname, sum((s_ - 1) * tables.groups[gi][2] * int(shape.ldc) for gi, s_ in slices.items()))
+        parts = {gi: gemm_policy.cut_segments(tables.groups[gi][1], s_, int(shape.a_ks), int(shape.b_ks))
+                 for gi, s_ in slices.items()}
+        out, entries = T.kslice_tables(tables, parts, shape.ldc, self._param_rel(c_ref), self._param_rel(self._ref(sname)))
+        e_r = self._upload(np.array(entries, REDUCE_ENTRY_DTYPE))
+        red = Launch("reduce_splits_multi_sized_f32", (Ref(self.sess.params), e_r, len(entries),
                                                        int(max(e[3] for e in entries))),
                      nbytes=4 * sum(cnt * (S + 2) for (_, _, _, cnt, S, _) in entries), tag="kslice-reduce")
         red.meta = {"kslices": {"tiles": len(entries), "slices": int(sum(slices.values())), "of": tag}}
@@ -851,11 +568,11 @@ class TowerPlan:
         """The level's packed layout if pass `what` ("fwd" / "dgrad" / "wgrad") uses the merged form, else None."""
         lay = self._level_layout(idx, node)
         cap = MERGE_PASS_MAX_COUT[what]
-        if what == "fwd" and GEMM_SPLIT == 6:
+        if what == "fwd" and gemm_policy.GEMM_SPLIT == 6:
             cap = max(cap, MERGE_FWD_MAX_COUT_SPLIT)
         if lay is None or what not in MERGE_LEVELS or lay["co"] > cap or (what == "fwd" and lay["has_bias"]):
             return None
-        if what == "wgrad" and not (GEMM_SPLIT == 6 and MERGE_WGRAD and MERGE_WGRAD_MIN_COUT <= lay["co"] <= MERGE_WGRAD_MAX_COUT):
+        if what == "wgrad" and not (gemm_policy.GEMM_SPLIT == 6 and MERGE_WGRAD and MERGE_WGRAD_MIN_COUT <= lay["co"] <= MERGE_WGRAD_MAX_COUT):
             return None  # (on the fp32 kernels it moved work between the width classes without shortening their sum, NOTES 4.A)
         return lay
 
@@ -875,9 +592,8 @@ class TowerPlan:
                      for dy, dx, w_, col, _ in self._taps(self._columns(node), cin)]
         if not ents:
             return
-        t = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
-        self.tables.append(t)
-        self.fwd.insert(pos, Launch("copy_blocks_f32", (base, Ref(t), len(ents), max(e[2] * e[3] for e in ents)),
+        self.fwd.insert(pos, Launch("copy_blocks_f32", (base, self._upload(np.array(ents, COPY_BLOCK_DTYPE)), len(ents),
+                                                        max(e[2] * e[3] for e in ents)),
                                     nbytes=8 * sum(e[2] * e[3] for e in ents), tag="level-pack"))
 
     # ------------------------------------------------------------------ convolution taps
@@ -964,7 +680,8 @@ class TowerPlan:
                 whole.add_group(p * nb * c + ring[0][3], self._fwd_segs(ring, s_st, h, w, p), nb, n=ring[0][4])
         flags = GEMM_VAR_N | (GEMM_MFMA16X4 if lay["co"] <= 16 and C <= 64 else 0)
         tag = f"fwd:{node.branches[0].scope}/merged"
-        sp6 = self._split6(tag, whole, C, 0, 0, flags, False)
+        shape = GemmShape(n=C, lda=s_st.ld, ta=0, ldb=C, tb=0, ldc=c)
+        sp6 = self._split6(tag, whole, shape, flags, False)
         max_taps = MERGE_MAX_TAPS or (MERGE_SPLIT_MAX_TAPS if sp6 else MAX_TAPS_PER_TILE)
         S_r = [max(1, -(-len(ring) // max_taps)) for ring in rings]
         kp_n = self._channel_parts(lay["cin"], h, w) if not sp6 or MERGE_SPLIT_KPARTS else 1
@@ -977,9 +694,9 @@ class TowerPlan:
             for kp, si, chunk in self._partial_copies(segs, S_r[r], kp_n, C):
                 tb.add_group(((chunk0[r] + si) * kp_n + kp) * rows_all * c + c_off, chunk, nb, subkey=kp, n=whole.ns[gi])
         pos = len(self.fwd)
-        self._emit_gemm(self.fwd, tb, C, self._ref(s_st.buf), s_st.ld, 0, self._ref(lay["buf"]), C, 0, self._ref(ybuf), c,
-                        None, 0, tag, allow_split=False, hint=MERGE_FWD_HINT, flags=flags,
-                        sp6=sp6)  # (a split-operand launch takes its own width, _split6_width)
+        self._emit_gemm(self.fwd, tb, shape, self._ref(s_st.buf), self._ref(lay["buf"]), self._ref(ybuf), None, 0, tag,
+                        allow_split=False, hint=MERGE_FWD_HINT, flags=flags,
+                        sp6=sp6)  # (a split-operand launch takes its own width, gemm_policy.split6_width)
         if len(self.fwd) > pos:
             self.fwd[pos].kparts = kp_n
         for b, col in self._columns(node):  # the copies that hold columns of branch b: 0 .. chunk0[ring of b + 1] * kp_n - 1
@@ -1036,8 +753,8 @@ class TowerPlan:
                         tb.add_group((kp * S_tap + si) * rows_all * c + p * nb * c + col, chunk, nb, subkey=kp)
             # the kernel indexes bias by (c_off % ldc) + column, so merged branches share one launch
             pos = len(self.fwd)
-            self._emit_gemm(self.fwd, tb, cout, self._ref(s_st.buf), s_st.ld, 0, Ref(self.sess.params), cout, 0,
-                            self._ref(ybuf), c, None if split_launch else bias_ref, 0,
+            self._emit_gemm(self.fwd, tb, GemmShape(n=cout, lda=s_st.ld, ta=0, ldb=cout, tb=0, ldc=c), self._ref(s_st.buf),
+                            Ref(self.sess.params), self._ref(ybuf), None if split_launch else bias_ref, 0,
                             f"fwd:{items[0][0].scope}" + ("/split" if split_launch else ""), allow_split=False,
                             stats=((rows_all + GEMM_BM - 1) // GEMM_BM) * 2 * c if fuse_stats else None)
             if len(self.fwd) > pos:
@@ -1078,9 +795,9 @@ class TowerPlan:
                 tb.add_group(pi * cout, [(s_st.pix_off(0) + off, node.branches[pi].w.offset, width)], nb)
             act_flag = self._act_in_gemm(node, cout)
             aux["act_in_gemm"] = bool(act_flag)
-            self._emit_gemm(self.fwd, tb, cout, self._ref(s_st.buf), s_st.ld, 0, Ref(self.sess.params), cout, 0,
-                            self._ref(ybuf), c, bias_ref, 0, f"fwd:{node.branches[0].scope}+{len(node.branches) - 1}",
-                            allow_split=False, flags=act_flag)
+            self._emit_gemm(self.fwd, tb, GemmShape(n=cout, lda=s_st.ld, ta=0, ldb=cout, tb=0, ldc=c), self._ref(s_st.buf),
+                            Ref(self.sess.params), self._ref(ybuf), bias_ref, 0,
+                            f"fwd:{node.branches[0].scope}+{len(node.branches) - 1}", allow_split=False, flags=act_flag)
         else:  # dense
             b = node.branches[0]
             rowbase = 0
@@ -1089,14 +806,13 @@ class TowerPlan:
                 tb = GemmTables()
                 segs = [(s_st.pix_off(p), b.w.offset + (rowbase + p * src.c) * c, src.c) for p in range(src.npix)]
                 tb.add_group(0, segs, nb)
+                shape = GemmShape(n=c, lda=s_st.ld, ta=0, ldb=c, tb=0, ldc=c)
                 act_flag = 0
-                if len(node.sources) == 1 and self._split_k(tb, c, s_st.ld, 0, c, 0, c) is None:
+                if len(node.sources) == 1 and gemm_policy.split_k(tb, shape) is None:
                     act_flag = self._act_in_gemm(node, c)
                 aux["act_in_gemm"] = bool(act_flag)
-                self._emit_gemm(self.fwd, tb, c, self._ref(s_st.buf), s_st.ld, 0, Ref(self.sess.params), c, 0,
-                                self._ref(ybuf), c, bias_ref if si == 0 else None, 1 if si > 0 else 0,
-                                f"fwd:{b.scope}",
-                                flags=act_flag)
+                self._emit_gemm(self.fwd, tb, shape, self._ref(s_st.buf), Ref(self.sess.params), self._ref(ybuf),
+                                bias_ref if si == 0 else None, 1 if si > 0 else 0, f"fwd:{b.scope}", flags=act_flag)
                 rowbase += src.npix * src.c
 
         rows = out.npix * nb
@@ -1203,9 +919,7 @@ class TowerPlan:
                 raise NotImplementedError("residual source must cover the same pixels")
             iref = None
             if ridx is not None:
-                t = self.be.upload(np.asarray(ridx, np.int32))
-                self.tables.append(t)
-                iref = Ref(t)
+                iref = self._upload(np.asarray(ridx, np.int32))
             out.append((self._ref(st.buf, st.ch_off), st.ld, iref))
         while len(out) < 2:
             out.append((None, 0, None))
@@ -1350,9 +1064,7 @@ class TowerPlan:
             gst, acc = self._grad_target(src)
             sref = None
             if ridx is not None:
-                t = self.be.upload(self._chanmap_start(ridx, src.c))
-                self.tables.append(t)
-                sref = Ref(t)
+                sref = self._upload(self._chanmap_start(ridx, src.c))
             self.bwd.append(Launch("chanmap_bwd", (dz_ref, lddz, rows, c, self._ref(gst.buf, gst.ch_off), gst.ld,
                                                    src.c, sref, acc), nbytes=4 * rows * (c + 2 * src.c),
                                    tag="res-bwd"))
@@ -1379,9 +1091,7 @@ class TowerPlan:
             ridx = node.residuals[fold][1]
             sref = None
             if ridx is not None:
-                t = self.be.upload(self._chanmap_start(ridx, node.sources[0].c))
-                self.tables.append(t)
-                sref = Ref(t)
+                sref = self._upload(self._chanmap_start(ridx, node.sources[0].c))
             fold_res = (dz, c, sref)
             if node.has_bn or (node.act and node.act.code != 0) or aux.get("mask") is not None:
                 self._alloc("dy:" + z_st.buf, rows * c)
@@ -1409,6 +1119,7 @@ class TowerPlan:
                     w_ref, w_ld, mtag = self._ref(lay["buf"]), lay["C"], "/merged"
                 for cout, items in by_cout.items():
                     taps = self._taps(items, src.c, lay)
+                    shape = GemmShape(n=src.c, lda=c, ta=0, ldb=w_ld or cout, tb=1, ldc=gst.ld)
                     tb = GemmTables()
                     per_pixel = []
                     if len(taps) == 1 and gst.contiguous:  # a lone 1x1 branch: ONE group over all pixels
@@ -1440,8 +1151,7 @@ class TowerPlan:
                             for _, si, chunk in self._partial_copies(segs, S):
                                 tb.add_group(si * copy + gst.pix_off(pin), chunk, nb, subkey=si)
                         pos = len(self.bwd)
-                        self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, w_ref, w_ld or cout, 1,
-                                        self._ref(gst.buf), gst.ld, None, 0,
+                        self._emit_gemm(self.bwd, tb, shape, dy, w_ref, self._ref(gst.buf), None, 0,
                                         f"dgrad:{items[0][0].scope}/split{mtag}")
                         self._scratch(self.bwd[pos], "c", "scratch_dgrad", S * copy)
                         l2 = Launch("reduce_splits_f32", (None, copy, S, self._ref(gst.buf), h * w * nb * src.c,
@@ -1453,9 +1163,8 @@ class TowerPlan:
                         continue
                     for pin, segs in enumerate(per_pixel):
                         tb.add_group(gst.pix_off(pin), segs, nb)
-                    self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, w_ref, w_ld or cout, 1,
-                                    self._ref(gst.buf), gst.ld, None, acc, f"dgrad:{items[0][0].scope}{mtag}",
-                                    res=fold_res, pair=cout <= 16, kslice=True)
+                    self._emit_gemm(self.bwd, tb, shape, dy, w_ref, self._ref(gst.buf), None, acc,
+                                    f"dgrad:{items[0][0].scope}{mtag}", res=fold_res, pair=cout <= 16, kslice=True)
                     fold_res = None
                     acc = 1
             # ---- filter gradient ----
@@ -1474,8 +1183,9 @@ class TowerPlan:
                     tb = GemmTables()
                     for pi, off in items:
                         tb.add_group(gst.pix_off(0) + off, [(pi * cout, node.branches[pi].w.offset, cout)], nb)
-                    self._emit_gemm(self.bwd, tb, width, dy, c, 0, Ref(self.sess.params), cout, 1, self._ref(gst.buf),
-                                    gst.ld, None, acc, f"dgrad:{node.branches[0].scope}+", allow_split=False)
+                    self._emit_gemm(self.bwd, tb, GemmShape(n=width, lda=c, ta=0, ldb=cout, tb=1, ldc=gst.ld), dy,
+                                    Ref(self.sess.params), self._ref(gst.buf), None, acc,
+                                    f"dgrad:{node.branches[0].scope}+", allow_split=False)
             if trains:
                 self._wgrad_blockdense(node, s_st, dy, c, cout)
         else:
@@ -1488,8 +1198,8 @@ class TowerPlan:
                     tb = GemmTables()
                     for p in range(src.npix):
                         tb.add_group(gst.pix_off(p), [(0, b.w.offset + (rowbase + p * src.c) * c, c)], nb)
-                    self._emit_gemm(self.bwd, tb, src.c, dy, c, 0, Ref(self.sess.params), c, 1, self._ref(gst.buf),
-                                    gst.ld, None, acc, f"dgrad:{b.scope}")
+                    self._emit_gemm(self.bwd, tb, GemmShape(n=src.c, lda=c, ta=0, ldb=c, tb=1, ldc=gst.ld), dy,
+                                    Ref(self.sess.params), self._ref(gst.buf), None, acc, f"dgrad:{b.scope}")
                 rowbase += src.npix * src.c
             if trains:
                 self._wgrad_dense(node, dy, c)
@@ -1576,51 +1286,17 @@ class TowerPlan:
                 self._scratch(l3, "sums", "sums", 2 * c)
             self.bwd.append(l3)
 
-    def _wgrad_splits(self, base_blocks, n_pairs):
-        """Filter-gradient reduction = S_pix x S_row splits: the pixel-pair list is cut into S_pix contiguous chunks
-        and the batch rows into S_row ranges (the SAME ranges for every tap).  Tiles are ordered split-major, so each
-        XCD streams its own rows of X and dY through its L2 once while all taps consume them (the per-tap
-        formulation re-fetched them 10-20x).  Multi-tap levels use row ranges only; single-tap layers also cut the
-        pixel list, otherwise the launch would have too few blocks."""
-        want = max(1, min(WGRAD_MAX_SPLITS, (TARGET_BLOCKS + base_blocks - 1) // max(base_blocks, 1)))
-        max_row = max(1, self.nb // 64)
-        # 64-row ranges also when the unsplit launch already fills the device: with split-major tile order an XCD then streams one
-        # row range of X and dY for all taps instead of whole pixel blocks per tap (DUALCNN levels, 165 taps x 10 x 8
-        # blocks unsplit: 82 -> 117 TFLOP/s with 8 row ranges)
-        if WGRAD_MIN_SPLITS > 0:
-            want = max(want, min(WGRAD_MAX_SPLITS, WGRAD_MIN_SPLITS))
-        elif base_blocks >= TARGET_BLOCKS:
-            want = max(want, min(WGRAD_MAX_SPLITS, max_row))
-        s_row = min(want, max_row)
-        if s_row >= 5:  # a multiple of 8 row ranges maps whole ranges onto the 8 XCDs
-            s_row = min(max(8, max_row // 8 * 8), (s_row + 7) // 8 * 8)
-        s_pix = max(1, min(n_pairs, want // s_row))
-        return s_pix, s_row
-
     def _emit_wgrad(self, groups, slab, w0_offset, n, a_ref, lda, b_ref, ldb, tag, acc=0, unpack=None):
         """Filter-gradient product: groups = [(c_off in the slab, [(a_off, b_off)] pixel pairs, rows, n or 0 = the launch's
-        n)], each the sum over its pixel pairs and the batch rows; split s of the reduction (_wgrad_splits) writes its slab
-        at s * slab.
+        n)], each the sum over its pixel pairs and the batch rows; split s of the reduction (gemm_policy.wgrad_splits)
+        writes its slab at s * slab.
         unpack (merged levels): dict(buf, entries) -- the product's output is a packed image in buffer `buf`, scattered into
         the gradient slots by block copies after the reduction."""
-        nb = self.nb
-        n_pairs = max(len(prs) for _, prs, _, _ in groups)
-        s_pix, s_row = self._wgrad_splits(sum((rows + GEMM_BM - 1) // GEMM_BM * (((gn or n) + 63) // 64)
-                                              for _, _, rows, gn in groups), n_pairs)
+        s_pix, s_row = gemm_policy.wgrad_splits(sum((rows + GEMM_BM - 1) // GEMM_BM * (((gn or n) + 63) // 64)
+                                                    for _, _, rows, gn in groups),
+                                                max(len(prs) for _, prs, _, _ in groups), self.nb)
         S = s_pix * s_row
-        # split = (row range, pixel-pair chunk), row range major (the XCD-locality key); a group with fewer pixel pairs
-        # than the widest one gets proportionally cut chunks
-        rcuts = [min(nb, (nb * s // s_row + 31) // 32 * 32) for s in range(s_row)] + [nb]
-        tb = GemmTables()
-        for sr in range(s_row):
-            r0, r1 = rcuts[sr], rcuts[sr + 1]
-            for sp in range(s_pix):
-                p0, p1 = n_pairs * sp // s_pix, n_pairs * (sp + 1) // s_pix
-                si = sr * s_pix + sp
-                for c_off, prs, rows, gn in groups:
-                    q0, q1 = len(prs) * p0 // n_pairs, len(prs) * p1 // n_pairs
-                    segs = [(a + r0 * lda, b + r0 * ldb, r1 - r0) for a, b in prs[q0:q1]] if r1 > r0 else []
-                    tb.add_group(si * slab + c_off, segs, rows, key=si, n=gn)
+        tb = T.wgrad_split_tables(groups, self.nb, lda, ldb, slab, s_pix, s_row)
         if MERGE_WGRAD:
             if (acc or (unpack and any(e[6] for e in unpack["entries"]))) and self._pending_wgrads:
                 # a second application of shared weights adds to what an earlier pending product writes: keep the order
@@ -1629,13 +1305,11 @@ class TowerPlan:
                                              lda=int(lda), b_ref=b_ref, ldb=int(ldb), tag=tag, acc=int(acc), unpack=unpack))
             return
         assert unpack is None, "merged-level filter gradients need the merged launch (MERGE_WGRAD)"
-        if S == 1:
-            self._emit_gemm(self.bwd, tb, n, a_ref, lda, 1, b_ref, ldb, 0, Ref(self.sess.grads, w0_offset), n, None,
-                            acc, tag, allow_split=False)
-            return
         launch_pos = len(self.bwd)
-        self._emit_gemm(self.bwd, tb, n, a_ref, lda, 1, b_ref, ldb, 0, Ref(self.sess.grads), n, None, 0, tag,
-                        allow_split=False)
+        self._emit_gemm(self.bwd, tb, GemmShape(n=n, lda=lda, ta=1, ldb=ldb, tb=0, ldc=n), a_ref, b_ref,
+                        Ref(self.sess.grads, w0_offset if S == 1 else 0), None, acc if S == 1 else 0, tag, allow_split=False)
+        if S == 1:
+            return
         l = self.bwd[launch_pos]
         self._scratch(l, "c", "scratch_wgrad", S * slab)
         l2 = Launch("reduce_splits_f32", (None, slab, S, Ref(self.sess.grads, w0_offset), slab, acc, None, 0, 0),
@@ -1645,130 +1319,53 @@ class TowerPlan:
 
     def _flush_wgrads(self):
         """Emit the collected filter gradients: one hypel_seg_gemm_multi_f32 per tile width over the blocks of every
-        pending product, then one hypel_reduce_splits_multi_f32 that sums the split slabs into the gradient buffer.
-
-        Block order: the blocks of one (product, split) pair -- all taps and column tiles that read the same batch-row
-        range of X and dY -- form a locality group; groups are dealt to the 8 XCDs heaviest first onto the least
-        loaded XCD (each XCD's L2 then streams a row range once for all its taps, and the XCDs finish together), and
-        the record array is laid out so that the kernel's XCD remap (block b runs on XCD b % 8 and takes record
-        (b % 8) * L + b / 8) hands XCD x exactly its list; short lists are padded with empty records."""
+        pending product (gemm_tables.merged_wgrad_tables: the XCD-laid record arrays), then one
+        hypel_reduce_splits_multi_f32 that sums the split slabs into the gradient buffer and, for merged levels, the block
+        copies that scatter the packed gradient images into the variables' gradient slots."""
         pend, self._pending_wgrads = self._pending_wgrads, []
         if not pend:
             return
         base = Ref(self.sess.params)
         rel = self._param_rel
         # scratch for the split slabs of this flush
-        need = sum(e["S"] * e["slab"] for e in pend if e["S"] > 1)
-        fid = self._wgrad_flushes
+        sname = f"wgrad_partials:{self._wgrad_flushes}"
         self._wgrad_flushes += 1
-        sname = f"wgrad_partials:{fid}"
-        self._alloc(sname, max(need, 1))
-        spos = 0
+        self._alloc(sname, max(sum(e["S"] * e["slab"] for e in pend if e["S"] > 1), 1))
         grads0 = rel(Ref(self.sess.grads))
-        entries = []
-        unpacks = []  # block copies packed gradient image -> TF-layout gradient slots (merged levels)
-
-        def col_tiles(n, split6=0):
-            """[(n0, tile width)] of a product with n output columns: one width per product.  split6 = tile-width hint of
-            the split-operand kernel (widths | GEMM_MULTI_SPLIT6: their own launches)."""
-            if split6:
-                wdt = SPLIT6_BN[split6]
-                return [(n0, wdt | GEMM_MULTI_SPLIT6) for n0 in range(0, n, wdt)]
-            wdt = 16 if n <= 16 else (32 if n <= 32 else 64)
-            return [(n0, wdt) for n0 in range(0, n, wdt)]
-
-        per_width = {}  # width -> dict(segs, lists, macs, nbytes, tags)
         for e in pend:
-            n = e["n"]
-            up = e.get("unpack")
+            n, tb, up = e["n"], e["tb"], e["unpack"]
             if up is not None:
                 # the reduction target is the level's packed gradient image (dense per-offset blocks), scattered into the
                 # variables' gradient slots afterwards
                 self._alloc(up["buf"], e["slab"])
-                out_base = rel(self._ref(up["buf"]))
-                unpacks += [(out_base + so, grads0 + do, rows, cols, sld, dld, acc, 0)
-                            for (so, do, rows, cols, sld, dld, acc) in up["entries"]]
+                e.update(out_base=rel(self._ref(up["buf"])), unpack=up["entries"])
             else:
-                out_base = grads0 + e["w0"]
-            if e["S"] > 1:
-                c_base = rel(self._ref(sname, spos))
-                entries.append((c_base, out_base, e["slab"], e["slab"], e["S"], 0 if up is not None else e["acc"]))
-                spos += e["S"] * e["slab"]
-                flags = 0
-            else:
-                c_base = out_base
-                flags = 0 if up is not None else e["acc"]
-            a0, b0 = rel(e["a_ref"]), rel(e["b_ref"])
-            tb = e["tb"]
-            sp6 = self._split6(e["tag"], tb, n, 1, 0, 0, False, in_multi=True)
-            first_width = None
-            loc_groups = {}  # (width, locality key) -> [work, [(work, record)]]
-            for gi, (c_off, gs, rows) in enumerate(tb.groups):
-                gn = tb.n_of(gi, n)
-                # a merged level's per-offset products differ in their column count: each takes the width class of ITS n
-                sp_g = sp6 if gn == n else (self._split6_width(gn) if sp6 and gn > GEMM_SPLIT_MIN_N else 0)
-                tiles = col_tiles(gn, sp_g)
-                ksum = sum(k for _, _, k in gs)
-                key = tb.keys[gi] if tb.keys[gi] is not None else 0
-                seg_begin = {}
-                for wdt in sorted({wd for _, wd in tiles}, reverse=True):
-                    pw = per_width.setdefault(wdt, dict(segs=[], lists=[], macs=0, nbytes=0, tags=[]))
-                    if first_width is None:
-                        first_width = wdt
-                    if e["tag"] not in pw["tags"]:
-                        pw["tags"].append(e["tag"])
-                    # (a split with no reduction rows still owns its slab: the reduce reads it, so it must be zero)
-                    seg_begin[wdt] = len(pw["segs"])
-                    pw["segs"] += [(a0 + int(a_off), b0 + int(b_off), int(k), 0) for (a_off, b_off, k) in gs]
-                first = (a0 + int(gs[0][0]), b0 + int(gs[0][1]), int(gs[0][2])) if gs else (0, 0, 0)
-                for m0 in range(0, rows, GEMM_BM):
-                    work = ksum * min(GEMM_BM, rows - m0)
-                    for n0, wdt in tiles:
-                        per_width[wdt]["macs"] += min(GEMM_BM, rows - m0) * ksum * min(wdt & 0xff, gn - n0)
-                        recs = loc_groups.setdefault((wdt, key), [0, []])
-                        recs[1].append((work, (c_base + int(c_off), first[0], first[1], m0, rows, n0, gn,
-                                               seg_begin[wdt], len(gs), first[2], flags, e["lda"], e["ldb"], gn, 0)))
-                        recs[0] += work
-            if first_width is not None:
-                per_width[first_width]["nbytes"] += tb.compulsory_bytes(n, e["lda"], 1, e["ldb"], 0)
-            for (wdt, _), (wk, r) in loc_groups.items():  # inside a locality group: heavy blocks first
-                r.sort(key=lambda t: -t[0])
-                per_width[wdt]["lists"].append((wk, [rec for _, rec in r]))
-        for width in sorted(per_width, reverse=True):
-            pw = per_width[width]
-            segs, lists = pw["segs"], pw["lists"]
-            lists.sort(key=lambda t: -t[0])
-            xcd_work, xcd_recs = [0] * 8, [[] for _ in range(8)]
-            for w, r in lists:
-                x = min(range(8), key=lambda i: (xcd_work[i], i))
-                xcd_work[x] += w
-                xcd_recs[x] += r
-            L = max(len(r) for r in xcd_recs)
-            arr = np.zeros(8 * L, MTILE_DTYPE)  # zero record = empty block (rows 0, no segments)
-            for x in range(8):
-                if xcd_recs[x]:
-                    arr[x * L:x * L + len(xcd_recs[x])] = np.array(xcd_recs[x], MTILE_DTYPE)
-            sarr = np.array(segs + [(0, 0, 0, 0)], SEG_DTYPE)  # + the zero sentinel record (GemmTables.finalize)
-            s_t, r_t = self.be.upload(sarr), self.be.upload(arr)
-            self.tables += [s_t, r_t]
-            l = Launch("seg_gemm_multi_f32", (base, 1, 0, width, Ref(s_t), Ref(r_t), int(len(arr))),
-                       flops=2 * pw["macs"], nbytes=pw["nbytes"],
+                e["out_base"] = grads0 + e["w0"]
+            e.update(a0=rel(e["a_ref"]), b0=rel(e["b_ref"]))
+            sp6 = self._split6(e["tag"], tb, GemmShape(n=n, lda=e["lda"], ta=1, ldb=e["ldb"], tb=0, ldc=n), 0, False,
+                               in_multi=True)
+            # a merged level's per-offset products differ in their column count: each takes the width class of ITS n
+            e["col_tiles"] = [gemm_policy.col_tiles(gn, sp6 if gn == n else gemm_policy.split6_width(gn)
+                                                    if sp6 and gn > gemm_policy.GEMM_SPLIT_MIN_N else 0)
+                              for gn in (tb.n_of(gi, n) for gi in range(len(tb.groups)))]
+        launches, entries, unpacks = T.merged_wgrad_tables(pend, grads0, rel(self._ref(sname)))
+        for m in launches:
+            width = m["width"]
+            s_r, r_r = self._upload(m["segs"]), self._upload(m["records"])
+            l = Launch("seg_gemm_multi_f32", (base, 1, 0, width, s_r, r_r, int(len(m["records"]))),
+                       flops=2 * m["macs"], nbytes=m["nbytes"],
                        tag=f"wgrad-merged/{'s' if width & GEMM_MULTI_SPLIT6 else ''}{width & 0xff}")
-            l.meta = {"products": pw["tags"], "blocks": int(sum(len(r) for r in xcd_recs)),
-                      "xcd_work": [int(w) for w in xcd_work]}
+            l.meta = {"products": m["tags"], "blocks": m["blocks"], "xcd_work": m["xcd_work"]}
             self.bwd.append(l)
         if entries:
-            earr = np.array([(p, o, st, cnt, S, acc) for (p, o, st, cnt, S, acc) in entries], REDUCE_ENTRY_DTYPE)
-            e_t = self.be.upload(earr)
-            self.tables.append(e_t)
-            l = Launch("reduce_splits_multi_f32", (base, Ref(e_t), int(len(earr))),
+            e_r = self._upload(np.array(entries, REDUCE_ENTRY_DTYPE))
+            l = Launch("reduce_splits_multi_f32", (base, e_r, len(entries)),
                        nbytes=4 * sum(cnt * (S + 1) for (_, _, _, cnt, S, _) in entries), tag="wgrad-reduce")
             l.meta = {"splits": [int(S) for (_, _, _, _, S, _) in entries]}
             self.bwd.append(l)
         if unpacks:
-            u_t = self.be.upload(np.array(unpacks, COPY_BLOCK_DTYPE))
-            self.tables.append(u_t)
-            self.bwd.append(Launch("copy_blocks_f32", (base, Ref(u_t), len(unpacks), max(u[2] * u[3] for u in unpacks)),
+            u_r = self._upload(np.array(unpacks, COPY_BLOCK_DTYPE))
+            self.bwd.append(Launch("copy_blocks_f32", (base, u_r, len(unpacks), max(u[2] * u[3] for u in unpacks)),
                                    nbytes=8 * sum(u[2] * u[3] for u in unpacks), tag="level-unpack"))
 
     def _wgrad_conv(self, idx, node, s_st, dy_ref, c):
@@ -1904,9 +1501,7 @@ class TowerPlan:
         s_st = self.storage_of(src)
         self._assert_contiguous(node.weights)
         self._assert_contiguous(node.biases)
-        t = self.be.upload(np.asarray([s_st.pix_off(p) for p in range(src.npix)], np.int64))
-        self.tables.append(t)
-        aux = {"pix": Ref(t), "x": s_st}
+        aux = {"x": s_st, "pix": self._upload(np.asarray([s_st.pix_off(p) for p in range(src.npix)], np.int64))}
         self.node_aux[idx] = aux
         self._alloc(f"uhat:{idx}", nb * I * jd)
         self._alloc(f"capc:{idx}", (2 * R - 1) * I * J)
@@ -1974,9 +1569,7 @@ class TowerPlan:
             gst, acc_x = self._grad_target(src)
             dx, lddx = self._ref(gst.buf), gst.ld
             if [gst.pix_off(p) for p in range(src.npix)] != [s_st.pix_off(p) for p in range(src.npix)]:
-                t = self.be.upload(np.asarray([gst.pix_off(p) for p in range(src.npix)], np.int64))
-                self.tables.append(t)
-                dpix = Ref(t)
+                dpix = self._upload(np.asarray([gst.pix_off(p) for p in range(src.npix)], np.int64))
         self.bwd.append(Launch("caps_uhat_bwd", (self._ref(s_st.buf), aux["pix"], s_st.ld, M, self._p(node.weights[0]), nb,
                                                  I, J, D, 2 * R - 1, cc, vec, dw, db_, acc_w, dx, dpix, lddx, acc_x),
                                nbytes=4 * I * (D + 1) * jd * (2 if trains else 1), tag="caps-uhat-bwd"))

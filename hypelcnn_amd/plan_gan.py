@@ -5,7 +5,7 @@ encoder tap, loss slots, and ONE slab reduction + ONE optimiser launch per train
 emission is inherited from plan.TowerPlan."""
 import numpy as np
 
-from . import graph as G
+from . import gemm_policy, graph as G
 from .backend import COPY_BLOCK_DTYPE, LOSS_NONE, LOSS_TERM_DTYPE, REDUCE_ENTRY_DTYPE, Ref
 from .gemm_tables import GemmTables, Launch
 from .plan import Storage, TowerPlan, stat_chunk_rows
@@ -30,8 +30,7 @@ class PhasePlan(TowerPlan):
     _defer_bias_sums = True  # bias-gradient chunk sums wait for the slab-reduction launch of the train op
 
     def nominal_batch(self):
-        from . import plan as _P
-        return _P.SPLIT_NOMINAL_BATCH_GAN
+        return gemm_policy.SPLIT_NOMINAL_BATCH_GAN
 
     def __init__(self, tower, nb, session, terms=(), train_groups=(), outputs=(), seed=1234):
         self.terms = list(terms)
@@ -358,9 +357,8 @@ class PhasePlan(TowerPlan):
         rel = self._param_rel
         ents = [(rel(self._ref(st.buf, st.ch_off)), rel(self._ref(name, g * nb * c)), nb, c, st.ld, c, 0, 0)
                 for g, st in enumerate(sts)]
-        t = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
-        self.tables.append(t)
-        self.fwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), Ref(t), len(ents), nb * c),
+        table = self._upload(np.array(ents, COPY_BLOCK_DTYPE))
+        self.fwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), table, len(ents), nb * c),
                                nbytes=8 * len(srcs) * nb * c, tag="batch-gather"))
         return Storage(name, nb * len(srcs), c, None, 0, c, 1), True
 
@@ -489,9 +487,8 @@ class PhasePlan(TowerPlan):
                     gst, acc = self._grad_target(t)
                     ents.append((rel(self._ref(scatter, g * nb0 * c)), rel(self._ref(gst.buf, gst.ch_off)), nb0, c, c,
                                  gst.ld, acc, 0))
-                tbl = self.be.upload(np.array(ents, COPY_BLOCK_DTYPE))
-                self.tables.append(tbl)
-                self.bwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), Ref(tbl), len(ents), nb0 * c),
+                table = self._upload(np.array(ents, COPY_BLOCK_DTYPE))
+                self.bwd.append(Launch("copy_blocks_f32", (Ref(self.sess.params), table, len(ents), nb0 * c),
                                        nbytes=8 * len(ents) * nb0 * c, tag="batch-scatter"))
 
     # ---- per-block gradient slabs of the fused kernels: reduced once per train op ----
@@ -555,9 +552,8 @@ class PhasePlan(TowerPlan):
                 launch.set("pw_stride", (first[1][0].ptr() - first[0][0].ptr()) // 4)
                 launch.set("pb_stride", (first[1][1].ptr() - first[0][1].ptr()) // 4)
         for rnd in [ents] + later:
-            e_t = self.be.upload(np.array(rnd, REDUCE_ENTRY_DTYPE))
-            self.tables.append(e_t)
-            self.bwd.append(Launch("reduce_splits_wave_multi_f32", (base, Ref(e_t), len(rnd), sum(e[3] for e in rnd)),
+            table = self._upload(np.array(rnd, REDUCE_ENTRY_DTYPE))
+            self.bwd.append(Launch("reduce_splits_wave_multi_f32", (base, table, len(rnd), sum(e[3] for e in rnd)),
                                    tag="slab-reduce"))
 
     @staticmethod
@@ -846,9 +842,8 @@ class PhasePlan(TowerPlan):
         arr = np.array([(rel(t["a"]), rel(t["b"]), rel(t["da"]), rel(t["db"]), t["lda"], t["ldb"], t["ldda"], t["lddb"],
                          t["rows"], t["mode"], t["c"], t["acc_da"], t["acc_db"], t["target"], t["gcoef"], t["pscale"],
                          first + k) for k, t in enumerate(batch)], LOSS_TERM_DTYPE)
-        e_t = self.be.upload(arr)
-        self.tables.append(e_t)
-        l = Launch("loss_terms_slots", (Ref(self.sess.params), Ref(e_t), len(batch), None), tag=f"loss-terms/{len(batch)}")
+        l = Launch("loss_terms_slots", (Ref(self.sess.params), self._upload(arr), len(batch), None),
+                   tag=f"loss-terms/{len(batch)}")
         self._loss_slot(l, "slots")
         self._term_list.append(l)
 

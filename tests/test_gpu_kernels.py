@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from hypelcnn_amd.backend import GROUP_DTYPE, SEG_DTYPE, TILE_DTYPE, Ref
-from hypelcnn_amd.plan import GemmTables, TowerPlan
+from hypelcnn_amd.gemm_policy import cut_segments
+from hypelcnn_amd.plan import GemmTables
 from tests import emu_backend
 from tests.emu_backend import EmuBackend
 from tests.parity_util import Both
@@ -1614,7 +1615,7 @@ def test_seg_gemm_kslice_plain_records(hip, split, hint, with_res, acc):
         if s_ == 1:
             tb.add_group(c_off, gs, r)
             continue
-        parts = TowerPlan._cut_segments(gs, s_, 1, 1)
+        parts = cut_segments(gs, s_, 1, 1)
         tb.add_group(c_off, parts[0], r, tail=True)
         for i in range(1, s_):
             tb.add_group(scratch0 + spos + (i - 1) * region, parts[i], r, flags=1, tail=True)

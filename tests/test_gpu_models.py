@@ -154,13 +154,13 @@ def test_grss2013_hypelcnn_batch1024_split6_vs_fp32_kernels(hip, monkeypatch):
     """The benchmarked configuration with every eligible product on the split-operand kernels (HYPEL_GEMM_SPLIT=6) against
     the same plan on the fp32 MFMA kernels, same weights / inputs: logits and gradients equal to fp32 rounding (two
     fp32-grade evaluations of the same sums), labels identical, run-to-run bit-exact."""
-    from hypelcnn_amd import plan
+    from hypelcnn_amd import gemm_policy
     alg = _alg("alg_param_hypelcnn.json")
-    monkeypatch.setattr(plan, "GEMM_SPLIT", 0)
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT", 0)
     built0, sess0, params, x, onehot, masks = _case(hip, "HYPELCNNModel", 7, 145, 15, alg, 1024, 99)
     ct0 = U.run_train_step(built0, x, onehot, masks)
     g0, l0 = sess0.grads.clone(), ct0.value(built0.y_conv).clone()
-    monkeypatch.setattr(plan, "GEMM_SPLIT", 6)
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT", 6)
     built1, sess1, _, _, _, _ = _case(hip, "HYPELCNNModel", 7, 145, 15, alg, 1024, 99)
     ct1 = U.run_train_step(built1, x, onehot, masks)
     launches = ct1.plan.fwd + ct1.plan.bwd
@@ -286,7 +286,7 @@ def test_grss2018_dualcnn_large_batches_equal_oracle_checked_chunks(hip, dual_fu
     gradients -- up to fp32 summation order.  The comparison needs the SAME arithmetic per sample at every batch size (a
     forward value that differs by one rounding can take the other leaky-ReLU branch): since round 6 the planner chooses
     between the fp32 MFMA and the split-operand kernels per LAYER (a launch is priced at a nominal batch,
-    plan.SPLIT_NOMINAL_BATCH), so the default plan is used as it is at 64, 128 and 512 (round 5 had to take the
+    gemm_policy.SPLIT_NOMINAL_BATCH), so the default plan is used as it is at 64, 128 and 512 (round 5 had to take the
     batch-dependent FLOP threshold out here)."""
     alg = dual_full[0]
     built, sess, params, x, onehot, masks = _case(hip, "DUALCNNModel", 11, 49, 20, alg, 512, 2018)

@@ -132,9 +132,9 @@ def test_split6_plan_matches_oracle(monkeypatch):
     """HYPEL_GEMM_SPLIT=6 (include/hypel.h HYPEL_GEMM_SPLIT6): with the size threshold forced down the planner marks the
     eligible forward, data-gradient and merged filter-gradient launches of a toy HYPELCNN; the emulation checks the
     eligibility rules of the flag, and the whole step still equals the oracle."""
-    from hypelcnn_amd import plan
-    monkeypatch.setattr(plan, "GEMM_SPLIT", 6)
-    monkeypatch.setattr(plan, "GEMM_SPLIT_MIN_FLOPS", 0.0)
+    from hypelcnn_amd import gemm_policy
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT", 6)
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT_MIN_FLOPS", 0.0)
     alg = dict(ALG_H, filter_count=96)
     built, sess, params, x, onehot, masks = _case("HYPELCNNModel", 5, 40, 4, alg, 70, 29)
     ct = U.run_train_step(built, x, onehot, masks)
@@ -182,8 +182,8 @@ def test_wgrad_row_ranges_of_device_filling_launch_match_oracle(monkeypatch, mod
     """Filter gradients of a launch that already fills the device are still cut into 64-row batch ranges
     (split-major tile order); forced by declaring one block 'device filling' at batch 192 (3 ranges, the last
     boundary not a multiple of the 128-row tile)."""
-    from hypelcnn_amd import plan
-    monkeypatch.setattr(plan, "TARGET_BLOCKS", 1)
+    from hypelcnn_amd import gemm_policy
+    monkeypatch.setattr(gemm_policy, "TARGET_BLOCKS", 1)
     built, sess, params, x, onehot, masks = _case(model_name, patch, ch, classes, alg, 192, 41)
     ct = U.run_train_step(built, x, onehot, masks)
     assert "wgrad-reduce" in _tags(ct)
@@ -194,11 +194,11 @@ def test_wgrad_row_ranges_of_device_filling_launch_match_oracle(monkeypatch, mod
 
 def test_all_large_batch_branches_together_match_oracle(monkeypatch):
     """Every split policy at once, at the batch size where production enables them (nb = 64) on a small DUALCNN."""
-    from hypelcnn_amd import plan
+    from hypelcnn_amd import gemm_policy, plan
     monkeypatch.setattr(plan, "MAX_TAPS_PER_TILE", 4)
     monkeypatch.setattr(plan, "DGRAD_MAX_SEGS", 5)
     monkeypatch.setattr(plan, "L2_CHUNK_BYTES", 1 << 16)
-    monkeypatch.setattr(plan, "TARGET_BLOCKS", 4)
+    monkeypatch.setattr(gemm_policy, "TARGET_BLOCKS", 4)
     built, sess, params, x, onehot, masks = _case("DUALCNNModel", 5, 7, 3, ALG_D, 64, 43)
     ct = U.run_train_step(built, x, onehot, masks)
     tags = _tags(ct)
@@ -291,13 +291,13 @@ def test_merged_forward_with_split_forced_off_uses_fp32_chunking(monkeypatch):
     """A merged level forward is cut for the kernel family that actually runs: with the split-operand kernels forced off by
     HYPEL_SPLIT_OVERRIDE for a level they would take (24 filters per branch), its tiles hold at most MAX_TAPS_PER_TILE taps
     and the reduction is cut into channel parts, as on the fp32 kernels; the step still equals the oracle."""
-    from hypelcnn_amd import plan
+    from hypelcnn_amd import gemm_policy, plan
     from hypelcnn_amd.backend import GROUP_DTYPE
     tag = "fwd:connector_0_conv1x1/merged"
     monkeypatch.setattr(plan, "TAP_SPLIT_MIN_BATCH", 1)
     monkeypatch.setattr(plan, "MAX_TAPS_PER_TILE", 5)
     monkeypatch.setattr(plan, "L2_CHUNK_BYTES", 4096)
-    monkeypatch.setattr(plan, "SPLIT_OVERRIDE", {tag: 0})
+    monkeypatch.setattr(gemm_policy, "SPLIT_OVERRIDE", {tag: 0})
     alg = dict(ALG_H, filter_count=192)
     built, sess, params, x, onehot, masks = _case("HYPELCNNModel", 7, 9, 4, alg, 5, 47)
     ct = U.run_train_step(built, x, onehot, masks)
@@ -315,15 +315,15 @@ def test_kslice_records_match_oracle(monkeypatch, frac_min):
     multi-kernel levels cut into slices and the tail tiles of the 1x1 stack's launches, slice 0 with the folded shortcut
     gather / accumulate bit, the others as plain partials in scratch, one reduce launch adding them in slice order; the
     whole step still equals the oracle."""
-    from hypelcnn_amd import plan
-    monkeypatch.setattr(plan, "GEMM_SPLIT", 6)
-    monkeypatch.setattr(plan, "GEMM_SPLIT_MIN_FLOPS", 0.0)
-    monkeypatch.setattr(plan, "KSLICE_MIN_GAIN", -10.0)   # take the best candidate whatever it is worth here
-    monkeypatch.setattr(plan, "KSLICE_MIN_K", 4)
-    monkeypatch.setattr(plan, "KSLICE_OVERHEAD_K", 1)
-    monkeypatch.setattr(plan, "KSLICE_REDUCE_COST_K", 0)
-    monkeypatch.setattr(plan, "KSLICE_FRAC_MIN", frac_min)
-    monkeypatch.setattr(plan, "KSLICE_SLOTS", {1: 8, 2: 8, 3: 8})
+    from hypelcnn_amd import gemm_policy
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT", 6)
+    monkeypatch.setattr(gemm_policy, "GEMM_SPLIT_MIN_FLOPS", 0.0)
+    monkeypatch.setattr(gemm_policy, "KSLICE_MIN_GAIN", -10.0)   # take the best candidate whatever it is worth here
+    monkeypatch.setattr(gemm_policy, "KSLICE_MIN_K", 4)
+    monkeypatch.setattr(gemm_policy, "KSLICE_OVERHEAD_K", 1)
+    monkeypatch.setattr(gemm_policy, "KSLICE_REDUCE_COST_K", 0)
+    monkeypatch.setattr(gemm_policy, "KSLICE_FRAC_MIN", frac_min)
+    monkeypatch.setattr(gemm_policy, "KSLICE_SLOTS", {1: 8, 2: 8, 3: 8})
     alg = dict(ALG_H, filter_count=400)
     built, sess, params, x, onehot, masks = _case("HYPELCNNModel", 5, 40, 4, alg, 150, 31)
     ct = U.run_train_step(built, x, onehot, masks)
