@@ -21,9 +21,14 @@ def _k_svm_kernel_planes_f32(self, g, ld, rows, cols, kind, gammas, n_gamma, row
     rn, cn = _arr(row_norms, np.float64)[:rows], _arr(col_norms, np.float64)[:cols]
     gam = _arr(gammas, np.float64)[:n_gamma]
     o = _arr(out)
+    # a plane is what hypel_svm_kernel_apply_f32 leaves in place: where rows are walked in groups of four columns (ld and
+    # plane_stride multiples of 4) the pad columns of a row's last group hold g's own values, any further one is not written
+    last = (cols + 3) // 4 * 4 if ld % 4 == 0 and plane_stride % 4 == 0 else cols
+    pads = _mat(g, ld, rows, last)[:, cols:].copy()
     for p in range(n_gamma):
-        plane = np.lib.stride_tricks.as_strided(o[p * plane_stride:], (rows, cols), (ld * 4, 4))
-        plane[...] = kernel_values(before, RBF, float(gam[p]), 0.0, 0, rn, cn).astype(np.float32)
+        plane = np.lib.stride_tricks.as_strided(o[p * plane_stride:], (rows, last), (ld * 4, 4))
+        plane[:, :cols] = kernel_values(before, RBF, float(gam[p]), 0.0, 0, rn, cn).astype(np.float32)
+        plane[:, cols:] = pads
     assert np.array_equal(m, before), "out of place: g is left intact"
 
 
