@@ -11,6 +11,11 @@ level's candidate table (in active-node order, without replacement per node).  N
 reproduced.  On purpose, unlike scikit-learn: thresholds lie on bin edges, candidates are not redrawn when all of a node's
 are invalid, growth is level-wise (node numbers are breadth-first per tree).
 
+ExtraTreesForest (reference classify/classic_ml_trainer.py:50, `ExtraTreesClassifier`) grows through the same level loop
+with another split search: no quantisation, one random cut per node and candidate column on the raw float32 values
+(hypel_forest_columns_f32, hypel_forest_split_random, hypel_forest_split_apply_thr); fit() calls the two hooks
+_prepare_columns and _split_level for what differs.
+
 predict: hypel_forest_predict_rows walks every tree per row and averages the leaf rows in fp64.  predict_scene walks the
 trees straight on the padded scene (hypel_forest_predict_scene) where the data set has one resolution, else it cuts
 patches chunk by chunk and uses the row kernel.  There is no CPU fallback: the `backend` argument exists so that the
@@ -112,6 +117,29 @@ class ForestClassifier:
                              f"{FOREST_MAX_CLASSES} classes (HYPEL_FOREST_MAX_CLASSES)")
 
     # ---- fit ---------------------------------------------------------------------------------------------------
+    _name = "ForestClassifier"
+
+    def _prepare_columns(self, be, rng, x, n, f, ldn):
+        """Once per fit, after the bootstrap draw: the feature-major form of the rows that the split search reads.
+        Here: the row permutation of the edge subsample is drawn, then edges and bins."""
+        perm = rng.permutation(n).astype(np.int32)
+        edges, n_edges = be.empty(f * FOREST_MAX_EDGES), be.zeros(f, torch.int32)
+        perm_d = be.upload(perm[:min(n, FOREST_EDGE_ROWS)])
+        be.call("forest_bin_edges_f32", Ref(x), f, n, f, Ref(perm_d), self.n_bins, Ref(edges), Ref(n_edges))
+        bins = be.zeros(f * ldn, torch.uint8)
+        be.call("forest_bin_u8", Ref(x), f, n, f, Ref(edges), Ref(n_edges), Ref(bins), ldn)
+        self._edges, self._n_edges, self._bins, self._ldn = edges, n_edges, bins, ldn
+
+    def _split_level(self, be, rng, rows, src, dst, slots, mf, f, score, valid, grown):
+        """One level: the split search and its application.  rows = (ldn, y, weight, n, n_classes), slots = (active,
+        n_active, cand), grown = the arguments of hypel_forest_split_apply from `level` on.  Returns the level's cut
+        table (what _level_done receives beside score and valid)."""
+        best_bin = be.zeros(slots[1] * mf, torch.int32)
+        be.call("forest_split_hist", Ref(self._bins), *rows, src, *slots, mf, f, score, Ref(best_bin), valid)
+        be.call("forest_split_apply", Ref(self._bins), *rows, src, dst, *slots, mf, f, score, Ref(best_bin), valid,
+                Ref(self._edges), *grown)
+        return best_bin
+
     def fit(self, X, y):
         be = self._backend()
         y = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y).reshape(-1)
@@ -128,17 +156,9 @@ class ForestClassifier:
             weight = np.stack([np.bincount(rng.integers(0, n, n), minlength=n) for _ in range(n_trees)]).astype(np.int32)
         else:
             weight = np.ones((n_trees, n), np.int32)
-        perm = rng.permutation(n).astype(np.int32)
         self.bootstrap_counts_ = weight
-
-        # edges and bins
-        edges, n_edges = be.empty(f * FOREST_MAX_EDGES), be.zeros(f, torch.int32)
-        perm_d = be.upload(perm[:min(n, FOREST_EDGE_ROWS)])
-        be.call("forest_bin_edges_f32", Ref(x), f, n, f, Ref(perm_d), self.n_bins, Ref(edges), Ref(n_edges))
         ldn = _round_up(n, 4)
-        bins = be.zeros(f * ldn, torch.uint8)
-        be.call("forest_bin_u8", Ref(x), f, n, f, Ref(edges), Ref(n_edges), Ref(bins), ldn)
-        self._edges, self._n_edges, self._bins, self._ldn = edges, n_edges, bins, ldn
+        self._prepare_columns(be, rng, x, n, f, ldn)
 
         # the order array: tree after tree, the tree's unique in-bag rows in ascending order
         in_bag = [np.flatnonzero(weight[t] > 0).astype(np.int32) for t in range(n_trees)]
@@ -159,22 +179,20 @@ class ForestClassifier:
             else:
                 cand = np.stack([rng.choice(f, mf, replace=False) for _ in range(n_active)]).astype(np.int32)
             cand_d = be.upload(cand)
-            score = be.zeros(n_active * mf, torch.float64)
-            best_bin, valid = be.zeros(n_active * mf, torch.int32), be.zeros(n_active * mf, torch.int32)
+            score, valid = be.zeros(n_active * mf, torch.float64), be.zeros(n_active * mf, torch.int32)
             split_ws, nxt, counter = (be.zeros(n_active, torch.int32), be.zeros(8 * n_active, torch.int32),
                                       be.zeros(1, torch.int32))
             src, dst = order[level % 2], order[(level + 1) % 2]
-            be.call("forest_split_hist", Ref(bins), ldn, Ref(y_d), Ref(w_d), n, n_cls, Ref(src), Ref(active), n_active,
-                    Ref(cand_d), mf, f, Ref(score), Ref(best_bin), Ref(valid))
-            be.call("forest_split_apply", Ref(bins), ldn, Ref(y_d), Ref(w_d), n, n_cls, Ref(src), Ref(dst), Ref(active),
-                    n_active, Ref(cand_d), mf, f, Ref(score), Ref(best_bin), Ref(valid), Ref(edges), level, cap, n_nodes,
-                    capacity, Ref(i32["feature"]), Ref(i32["thr_bin"]), Ref(threshold), Ref(i32["left"]),
-                    Ref(i32["right"]), Ref(i32["node_tree"]), Ref(i32["node_count"]), Ref(i32["node_weight"]), Ref(value),
-                    Ref(split_ws), Ref(nxt), Ref(counter))
+            rows = (ldn, Ref(y_d), Ref(w_d), n, n_cls)
+            slots = (Ref(active), n_active, Ref(cand_d))
+            grown = (level, cap, n_nodes, capacity, Ref(i32["feature"]), Ref(i32["thr_bin"]), Ref(threshold),
+                     Ref(i32["left"]), Ref(i32["right"]), Ref(i32["node_tree"]), Ref(i32["node_count"]),
+                     Ref(i32["node_weight"]), Ref(value), Ref(split_ws), Ref(nxt), Ref(counter))
+            cut = self._split_level(be, rng, rows, Ref(src), Ref(dst), slots, mf, f, Ref(score), Ref(valid), grown)
             n_next = int(counter.cpu()[0])  # (the one small read per level; it also orders the buffers' lifetimes)
             if n_next < 0:
-                raise RuntimeError("ForestClassifier.fit: node arrays too small (hypel_forest_split_apply)")
-            self._level_done(level, active, n_active, cand, score, best_bin, valid)
+                raise RuntimeError(f"{self._name}.fit: node arrays too small (hypel_forest_split_apply)")
+            self._level_done(level, active, n_active, cand, score, cut, valid)
             active, n_active, n_nodes, level = nxt, n_next, n_nodes + n_next, level + 1
         self.n_levels_ = level
 
@@ -335,3 +353,46 @@ class ForestClassifier:
             be.call("forest_predict_rows", Ref(patches.reshape(-1)), f, r1 - r0, f, *self._model_args(self._dev["nodes"]),
                     Ref(self._labels_u8), Ref(pts.reshape(-1)), Ref(raster), int(raster_w), None)
             be.synchronize()  # the patches die here
+
+
+class ExtraTreesForest(ForestClassifier):
+    """The subset of sklearn.ensemble.ExtraTreesClassifier the reference names (classify/classic_ml_trainer.py:50), on
+    the device: per node and candidate column ONE cut, drawn uniformly inside the range of the node's raw float32
+    values (hypel_forest_split_random), the best-scoring candidate taken (hypel_forest_split_apply_thr).  No column is
+    quantised, so there is no n_bins and threshold_bin_ is all -1; every other fitted attribute, from_arrays, arrays()
+    and the three serving calls are ForestClassifier's.
+
+    Random stream, numpy.random.Generator(PCG64(seed)) on the host, in this order: with bootstrap=True the bootstrap
+    counts, tree after tree, as ForestClassifier draws them (bootstrap=False, the default as in scikit-learn: weights
+    all one and no draw); then per level the candidate table exactly as ForestClassifier draws it (max_features == the
+    column count: no draw; else one rng.choice(f, max_features, replace=False) per active node, in active-node order)
+    followed by u = rng.random((n_active, max_features), dtype=float32).  There is no edge permutation.
+
+    On purpose, unlike scikit-learn: its random stream is not reproduced; candidates are not redrawn when all of a
+    node's are constant (the node becomes an impure leaf); growth is level-wise; a node at the depth cap (max_depth, at
+    most HYPEL_FOREST_MAX_DEPTH) is an impure leaf -- n_levels_ (the number of levels grown) shows when the cap was
+    reached."""
+    _name = "ExtraTreesForest"
+
+    def __init__(self, n_estimators=50, max_features=24, bootstrap=False, max_depth=None, seed=0, backend=None,
+                 chunk_rows=None):
+        super().__init__(n_estimators=n_estimators, max_features=max_features, bootstrap=bootstrap, max_depth=max_depth,
+                         seed=seed, backend=backend, chunk_rows=chunk_rows)
+
+    def get_params(self):
+        p = super().get_params()
+        del p["n_bins"]
+        return p
+
+    def _prepare_columns(self, be, rng, x, n, f, ldn):
+        xt = be.zeros(f * ldn)
+        be.call("forest_columns_f32", Ref(x), f, n, f, Ref(xt), ldn)
+        self._xt, self._ldn = xt, ldn
+
+    def _split_level(self, be, rng, rows, src, dst, slots, mf, f, score, valid, grown):
+        n_active = slots[1]
+        u = be.upload(rng.random((n_active, mf), dtype=np.float32))
+        thr = be.zeros(n_active * mf)
+        be.call("forest_split_random", Ref(self._xt), *rows, src, *slots, Ref(u), mf, f, score, Ref(thr), valid)
+        be.call("forest_split_apply_thr", Ref(self._xt), *rows, src, dst, *slots, mf, f, score, Ref(thr), valid, *grown)
+        return thr

@@ -1,4 +1,4 @@
-"""Classic-ML baseline (reference classify/classic_ml_trainer.py:20-157): a kernel SVC or a random forest on flattened
+"""Classic-ML baseline (reference classify/classic_ml_trainer.py:20-157): a kernel SVC, a random forest or an extra-trees forest on flattened
 patches, trained and served on the device by hypelcnn_amd.classic.svc.SVC / hypelcnn_amd.classic.forest.ForestClassifier,
 with the reference's flow, flag names and output files --
 `confusion_matrix_<loader>_run<i>.csv`, `metrics_<loader>_run<i>.txt` (OA,AA,KAPPA) and `params_<loader>_run<i>.json`
@@ -13,6 +13,10 @@ Differences from the reference, all on purpose:
    thresholds on bin edges, no candidate redraw and level-wise growth.  scikit-learn's estimator itself,
    asked for by name (RandomForestClassifier, random_forest, rf, ExtraTreesClassifier), stays refused: its result is
    its random stream's, which this project does not reproduce;
+ - the reference's commented line :50 (ExtraTreesClassifier) is --estimator extra_trees: random-threshold trees on the
+   raw float32 values (hypelcnn_amd.classic.forest.ExtraTreesForest), under the same three flags --forest_trees,
+   --forest_max_features and --forest_seed (--forest_bins is ignored: nothing is quantised); no bootstrap, as in
+   scikit-learn;
  - the reference's search (:126-136, GridSearchCV(SVC(), C x gamma) over StratifiedShuffleSplit(2, 0.1, 42)) runs on
    the device under a NEW flag, --svc_grid (hypelcnn_amd.classic.model_selection): after the baseline fit and its three
    files it searches the flattened training data, prints the reference's line and writes svc_grid_<loader>_run<i>.json;
@@ -38,7 +42,7 @@ from hypelcnn_amd.common.common_nn_ops import SceneArrays, create_colored_image,
 from hypelcnn_amd.common.tiff_io import imwrite
 from hypelcnn_amd.importer.InMemoryImporter import InMemoryImporter
 
-ESTIMATORS = ("svc_rbf", "svc_poly", "forest")
+ESTIMATORS = ("svc_rbf", "svc_poly", "forest", "extra_trees")
 
 
 def add_parse_cmds_for_app(parser):
@@ -48,14 +52,15 @@ def add_parse_cmds_for_app(parser):
                         help="If true, performs full scene classification.")
     parser.add_argument("--split_count", nargs="?", type=int, default=1, help="Split count")
     parser.add_argument("--estimator", nargs="?", type=str, default="svc_rbf",
-                        help="svc_rbf (reference :49), svc_poly (reference :48) or forest (reference :46)")
+                        help="svc_rbf (reference :49), svc_poly (reference :48), forest (reference :46) or extra_trees "
+                             "(reference :50)")
     parser.add_argument("--svc_gamma", nargs="?", type=float, default=1e-09, help="RBF gamma (svc_rbf)")
     parser.add_argument("--svc_c", nargs="?", type=float, default=None, help="C (default: 10000 svc_rbf, 1 svc_poly)")
     parser.add_argument("--svc_tol", nargs="?", type=float, default=1e-3, help="Stopping tolerance of the solver")
-    parser.add_argument("--forest_trees", nargs="?", type=int, default=50, help="Trees of the forest (forest)")
+    parser.add_argument("--forest_trees", nargs="?", type=int, default=50, help="Trees of the forest (forest, extra_trees)")
     parser.add_argument("--forest_max_features", nargs="?", type=int, default=24,
-                        help="Candidate features per node (forest; the reference's int(2 * sqrt(144)))")
-    parser.add_argument("--forest_bins", nargs="?", type=int, default=256, help="Bins per feature, 2..256 (forest)")
+                        help="Candidate features per node (forest, extra_trees; the reference's int(2 * sqrt(144)))")
+    parser.add_argument("--forest_bins", nargs="?", type=int, default=256, help="Bins per feature, 2..256 (forest; ignored by extra_trees, which quantises nothing)")
     parser.add_argument("--forest_seed", nargs="?", type=int, default=0,
                         help="Seed of the forest's random stream; episode i of --split_count uses seed + i")
     parser.add_argument("--svc_grid", nargs="?", const=True, type=type_ensure_strtobool, default=False,
@@ -75,11 +80,16 @@ def create_estimator(flags, backend=None, run_index=0):
         raise NotImplementedError(
             f"--estimator {name}: scikit-learn's RandomForestClassifier (reference classic_ml_trainer.py:46) is not built: "
             f"its result is that of scikit-learn's random stream, which is not reproduced here; --estimator forest grows "
-            f"the same kind of forest on the device with a seeded stream of its own; use one of {ESTIMATORS}")
+            f"the same kind of forest on the device with a seeded stream of its own (--estimator extra_trees: the "
+            f"random-threshold kind of ExtraTreesClassifier); use one of {ESTIMATORS}")
     if name == "forest":
         from hypelcnn_amd.classic.forest import ForestClassifier
         return ForestClassifier(n_estimators=flags.forest_trees, max_features=flags.forest_max_features,
                                 n_bins=flags.forest_bins, seed=flags.forest_seed + run_index, backend=backend)
+    if name == "extra_trees":
+        from hypelcnn_amd.classic.forest import ExtraTreesForest
+        return ExtraTreesForest(n_estimators=flags.forest_trees, max_features=flags.forest_max_features,
+                                seed=flags.forest_seed + run_index, backend=backend)
     if name == "svc_rbf":
         return SVC(kernel="rbf", gamma=flags.svc_gamma, C=10000.0 if flags.svc_c is None else flags.svc_c,
                    tol=flags.svc_tol, backend=backend)
@@ -224,8 +234,8 @@ def main(argv=None, backend=None):
             "--hyperparamopt (reference classic_ml_trainer.py:126-136) is not built: its contract is scikit-learn's own "
             "GridSearchCV object; the same search, with the same grid and splits, runs on the device under --svc_grid "
             "(--svc_grid_c / --svc_grid_gamma / --svc_grid_refit)")
-    if flags.svc_grid and flags.estimator == "forest":
-        raise ValueError("--svc_grid searches the SVC's C x gamma: not with --estimator forest")
+    if flags.svc_grid and flags.estimator in ("forest", "extra_trees"):
+        raise ValueError(f"--svc_grid searches the SVC's C x gamma: not with --estimator {flags.estimator}")
     results = []
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)

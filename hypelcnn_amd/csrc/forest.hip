@@ -8,6 +8,11 @@
 //                          atomics, a prefix sum over the bins per class, one score per bin boundary, the best boundary.
 //   * split_apply_kernel : one workgroup per active node: the best slot, the node record, the stable partition of the
 //                          node's segment of the order array (from one buffer into the other).
+//   * columns_kernel     : the feature-major float32 copy of the rows (x + 0.0f), 64 x 64 tiles through LDS.
+//   * split_random_kernel: extra-trees: one WAVEFRONT per (active node, candidate slot): the range of the node's raw
+//                          values, one cut inside it, the class weights on either side (a per-wave LDS table, integer
+//                          atomics), one score.  No block barrier: late levels are thousands of records of 2-20 rows.
+//   * split_apply_kernel is one body for both searches; the side test (bin <= thr_bin, or xt <= threshold) is a functor.
 //   * level_compact_kernel: one workgroup: a prefix sum over the nodes that split gives the children their node numbers
 //                          and their places in the next level's active list, in active-node order.
 //   * predict_kernel     : one row (or one scene pixel) per lane, one wavefront per block: the walk diverges per lane,
@@ -198,23 +203,153 @@ __global__ __launch_bounds__(THREADS) void split_hist_kernel(const uint8_t* __re
     }
 }
 
+constexpr int TILE = 64;
+
+// xt[c][i] = x[i][c] + 0.0f: a 64 x 64 tile read along the rows' columns and written along the columns' rows, the
+// LDS tile padded by one word so that neither side meets a bank twice
+__global__ __launch_bounds__(THREADS) void columns_kernel(const float* __restrict__ x, int64_t ld, int64_t n, int f,
+                                                          int64_t col_tiles, float* __restrict__ xt, int64_t ldn) {
+    __shared__ float tile[TILE][TILE + 1];
+    const int64_t rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
+    const int64_t i0 = rt * TILE, c0 = ct * TILE;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < TILE; r += WAVES)
+        if (i0 + r < n && c0 + lane < f) tile[r][lane] = x[(i0 + r) * ld + c0 + lane] + 0.0f;
+    __syncthreads();
+    for (int c = wave; c < TILE; c += WAVES)
+        if (c0 + c < f && i0 + lane < n) xt[(c0 + c) * ldn + i0 + lane] = tile[lane][c];
+}
+
+struct WaveMin {
+    __device__ __forceinline__ float operator()(float a, float b) const { return b < a ? b : a; }
+};
+struct WaveMax {
+    __device__ __forceinline__ float operator()(float a, float b) const { return b > a ? b : a; }
+};
+
+// lo + u * (hi - lo) in float32, one rounding per operation; a cut that is not below hi (u close to 1, or hi - lo = inf)
+// falls back to lo
+__device__ __forceinline__ float random_cut(float lo, float hi, float u) {
+#pragma clang fp contract(off)
+    const float d = hi - lo;
+    const float m = u * d;
+    float t = lo + m;
+    if (!(t < hi)) t = lo;
+    return t;
+}
+
+// One wavefront per record; the block's WAVES wavefronts share nothing but the launch.  side[0 .. C) is the class
+// weight left of the cut, side[MAXC .. MAXC + C) the node's: integer LDS atomics of this wavefront alone, ordered
+// against its own reads by wave barriers.
+__global__ __launch_bounds__(THREADS) void split_random_kernel(const float* __restrict__ xt, int64_t ldn,
+                                                               const int32_t* __restrict__ y,
+                                                               const int32_t* __restrict__ weight, int64_t n, int C,
+                                                               const int32_t* __restrict__ order,
+                                                               const int32_t* __restrict__ active,
+                                                               const int32_t* __restrict__ cand,
+                                                               const float* __restrict__ u, int mf, int64_t n_records,
+                                                               double* __restrict__ score, float* __restrict__ thr,
+                                                               int32_t* __restrict__ valid) {
+    __shared__ int side_s[WAVES][2 * MAXC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t rec = (int64_t)blockIdx.x * WAVES + wave;
+    if (rec >= n_records) return;  // (no block barrier below)
+    const int64_t a = rec / mf;
+    const int tree = active[4 * a], start = active[4 * a + 1], count = active[4 * a + 2];
+    const float* col = xt + (int64_t)cand[rec] * ldn;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = lane; i < count; i += 64) {
+        const float v = col[order[start + i]];
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+    lo = wave_reduce_all(lo, WaveMin());
+    hi = wave_reduce_all(hi, WaveMax());
+    if (count < 2 || !(lo < hi)) {  // (uniform over the wavefront)
+        if (lane == 0) {
+            score[rec] = 0.0;
+            thr[rec] = 0.0f;
+            valid[rec] = 0;
+        }
+        return;
+    }
+    const float t = random_cut(lo, hi, u[rec]);
+    int* side = side_s[wave];
+    side[lane] = 0;  // 2 * MAXC == 64
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int32_t* wt = weight + (int64_t)tree * n;
+    for (int i = lane; i < count; i += 64) {
+        const int s = order[start + i];
+        const int w = wt[s], k = y[s];
+        atomicAdd(&side[MAXC + k], w);
+        if (col[s] <= t) atomicAdd(&side[k], w);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int l = lane < C ? side[lane] : 0, r = lane < C ? side[MAXC + lane] - l : 0;
+    const int nl = wave_sum(l), nr = wave_sum(r);
+    const long long sl = wave_sum((long long)l * l), sr = wave_sum((long long)r * r);
+    if (lane == 0) {
+        score[rec] = boundary_score(sl, nl, sr, nr);
+        thr[rec] = t;
+        valid[rec] = 1;
+    }
+}
+static_assert(2 * MAXC == 64, "split_random_kernel zeroes its table with one store per lane");
+
 struct NodeOut {
     int32_t *feature, *thr_bin, *left, *right, *node_tree, *node_count, *node_weight;
     float* threshold;
     double* value;
 };
 
-__global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __restrict__ bins, int64_t ldn,
-                                                              const int32_t* __restrict__ y,
+// Which rows of a split node go left.  slot_aux(record) is the Pick's third key (the bin; the slot where the cut is a
+// float: a node's columns are distinct, so it never decides); choose(pick) binds the winning slot before threshold(),
+// thr_bin() and left(row) are asked.
+struct BinSide {
+    const uint8_t* bins;
+    int64_t ldn;
+    const int32_t* best_bin;
+    const float* edges;
+    const uint8_t* col;
+    int feature, bin;
+    __device__ __forceinline__ int slot_aux(int64_t at, int) const { return best_bin[at]; }
+    __device__ __forceinline__ void choose(const Pick& p, int64_t) {
+        col = bins + (int64_t)p.feature * ldn;
+        feature = p.feature;
+        bin = p.bin;
+    }
+    __device__ __forceinline__ float threshold() const { return edges[(int64_t)feature * MAXE + bin]; }
+    __device__ __forceinline__ int thr_bin() const { return bin; }
+    __device__ __forceinline__ bool left(int row) const { return (int)col[row] <= bin; }
+};
+
+struct ThrSide {
+    const float* xt;
+    int64_t ldn;
+    const float* thr;
+    const float* col;
+    float t;
+    __device__ __forceinline__ int slot_aux(int64_t, int slot) const { return slot; }
+    __device__ __forceinline__ void choose(const Pick& p, int64_t first) {
+        col = xt + (int64_t)p.feature * ldn;
+        t = thr[first + p.bin];
+    }
+    __device__ __forceinline__ float threshold() const { return t; }
+    __device__ __forceinline__ int thr_bin() const { return -1; }
+    __device__ __forceinline__ bool left(int row) const { return col[row] <= t; }  // the serving walk's compare
+};
+
+template <class Side>
+__global__ __launch_bounds__(THREADS) void split_apply_kernel(Side side, const int32_t* __restrict__ y,
                                                               const int32_t* __restrict__ weight, int64_t n, int C,
                                                               const int32_t* __restrict__ order_in,
                                                               int32_t* __restrict__ order_out,
                                                               const int32_t* __restrict__ active,
                                                               const int32_t* __restrict__ cand, int mf,
                                                               const double* __restrict__ score,
-                                                              const int32_t* __restrict__ best_bin,
-                                                              const int32_t* __restrict__ valid,
-                                                              const float* __restrict__ edges, int at_cap, NodeOut o,
+                                                              const int32_t* __restrict__ valid, int at_cap, NodeOut o,
                                                               int32_t* __restrict__ split_ws) {
     __shared__ int cls[MAXC];
     __shared__ Pick red[THREADS];
@@ -234,7 +369,7 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
     Pick p = {0.0, INT_MAX, INT_MAX, 0};
     for (int s = tid; s < mf; s += THREADS) {
         const int64_t at = a * mf + s;
-        const Pick q = {score[at], cand[at], best_bin[at], valid[at]};
+        const Pick q = {score[at], cand[at], side.slot_aux(at, s), valid[at]};
         if (q.valid && better(q, p)) p = q;
     }
     p = block_best(p, red);  // (its barriers also publish cls)
@@ -244,13 +379,14 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
         classes_present += cls[k] > 0;
     }
     const bool leaf = count < 2 || classes_present < 2 || !p.valid || at_cap;
+    if (!leaf) side.choose(p, a * mf);
     if (tid == 0) {
         o.node_tree[node] = tree;
         o.node_count[node] = count;
         o.node_weight[node] = nw;
         o.feature[node] = leaf ? -1 : p.feature;
-        o.thr_bin[node] = leaf ? -1 : p.bin;
-        o.threshold[node] = leaf ? 0.0f : edges[(int64_t)p.feature * MAXE + p.bin];
+        o.thr_bin[node] = leaf ? -1 : side.thr_bin();
+        o.threshold[node] = leaf ? 0.0f : side.threshold();
         o.left[node] = -1;
         o.right[node] = -1;
     }
@@ -259,10 +395,9 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
         if (tid == 0) split_ws[a] = 0;
         return;
     }
-    // stable partition of order_in[start .. start + count) by bin <= p.bin into order_out at the same place
-    const uint8_t* bf = bins + (int64_t)p.feature * ldn;
+    // stable partition of order_in[start .. start + count) by the side test into order_out at the same place
     int mine = 0;
-    for (int i = tid; i < count; i += THREADS) mine += (int)bf[order_in[start + i]] <= p.bin;
+    for (int i = tid; i < count; i += THREADS) mine += side.left(order_in[start + i]);
     mine = wave_sum(mine);
     if (lane == 0 && mine) atomicAdd(&n_left_s, mine);
     __syncthreads();
@@ -272,7 +407,7 @@ __global__ __launch_bounds__(THREADS) void split_apply_kernel(const uint8_t* __r
         const int i = base + tid;
         const bool live = i < count;
         const int s = live ? order_in[start + i] : 0;
-        const bool go_left = live && (int)bf[s] <= p.bin;
+        const bool go_left = live && side.left(s);
         const unsigned long long bl = __ballot(go_left), br = __ballot(live && !go_left);
         if (lane == 0) {
             wcount[wave] = __popcll(bl);
@@ -474,12 +609,73 @@ extern "C" int hypel_forest_split_apply(const uint8_t* bins, int64_t ldn, const 
     HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, "hypel_forest_split_apply");
     HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, "hypel_forest_split_apply");
     const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
-    hipLaunchKernelGGL(split_apply_kernel, dim3(n_active), dim3(THREADS), 0, ST, bins, ldn, y, weight, n, n_classes,
-                       order_in, order_out, active, cand, max_features, score, best_bin, valid, edges,
-                       (int)(level >= max_depth), o, split_ws);
+    const BinSide side = {bins, ldn, best_bin, edges, nullptr, 0, 0};
+    hipLaunchKernelGGL(split_apply_kernel<BinSide>, dim3(n_active), dim3(THREADS), 0, ST, side, y, weight, n, n_classes,
+                       order_in, order_out, active, cand, max_features, score, valid, (int)(level >= max_depth), o,
+                       split_ws);
     hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
                        node_capacity, left, right, next_active, counter);
     HYPEL_CHECK_LAUNCH("hypel_forest_split_apply");
+    return 0;
+}
+
+extern "C" int hypel_forest_columns_f32(const float* x, int64_t ld, int64_t n, int32_t f, float* xt, int64_t ldn,
+                                        hypel_stream_t stream) {
+    HYPEL_REQUIRE(x && xt, "hypel_forest_columns_f32");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && ldn >= n, "hypel_forest_columns_f32");
+    const int64_t row_tiles = (n + TILE - 1) / TILE, col_tiles = (f + TILE - 1) / TILE;
+    HYPEL_REQUIRE(row_tiles * col_tiles < ((int64_t)1 << 31), "hypel_forest_columns_f32");
+    hipLaunchKernelGGL(columns_kernel, dim3((unsigned)(row_tiles * col_tiles)), dim3(THREADS), 0, ST, x, ld, n, f,
+                       col_tiles, xt, ldn);
+    HYPEL_CHECK_LAUNCH("hypel_forest_columns_f32");
+    return 0;
+}
+
+extern "C" int hypel_forest_split_random(const float* xt, int64_t ldn, const int32_t* y, const int32_t* weight,
+                                         int64_t n, int32_t n_classes, const int32_t* order, const int32_t* active,
+                                         int32_t n_active, const int32_t* cand, const float* u, int32_t max_features,
+                                         int32_t f, double* score, float* thr, int32_t* valid, hypel_stream_t stream) {
+    HYPEL_REQUIRE(xt && y && weight && order && active && cand && u && score && thr && valid,
+                  "hypel_forest_split_random");
+    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_random");
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_random");
+    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_random");
+    const int64_t n_records = (int64_t)n_active * max_features;
+    HYPEL_REQUIRE(n_records < ((int64_t)1 << 31), "hypel_forest_split_random");
+    hipLaunchKernelGGL(split_random_kernel, dim3((unsigned)((n_records + WAVES - 1) / WAVES)), dim3(THREADS), 0, ST, xt,
+                       ldn, y, weight, n, n_classes, order, active, cand, u, max_features, n_records, score, thr, valid);
+    HYPEL_CHECK_LAUNCH("hypel_forest_split_random");
+    return 0;
+}
+
+extern "C" int hypel_forest_split_apply_thr(const float* xt, int64_t ldn, const int32_t* y, const int32_t* weight,
+                                            int64_t n, int32_t n_classes, const int32_t* order_in, int32_t* order_out,
+                                            const int32_t* active, int32_t n_active, const int32_t* cand,
+                                            int32_t max_features, int32_t f, const double* score, const float* thr,
+                                            const int32_t* valid, int32_t level, int32_t max_depth, int32_t node_base,
+                                            int32_t node_capacity, int32_t* feature, int32_t* thr_bin, float* threshold,
+                                            int32_t* left, int32_t* right, int32_t* node_tree, int32_t* node_count,
+                                            int32_t* node_weight, double* value, int32_t* split_ws, int32_t* next_active,
+                                            int32_t* counter, hypel_stream_t stream) {
+    HYPEL_REQUIRE(xt && y && weight && order_in && order_out && order_in != order_out && active && cand,
+                  "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(score && thr && valid && feature && thr_bin && threshold && left && right,
+                  "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(node_tree && node_count && node_weight && value && split_ws && next_active && counter,
+                  "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, "hypel_forest_split_apply_thr");
+    HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, "hypel_forest_split_apply_thr");
+    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    const ThrSide side = {xt, ldn, thr, nullptr, 0.0f};
+    hipLaunchKernelGGL(split_apply_kernel<ThrSide>, dim3(n_active), dim3(THREADS), 0, ST, side, y, weight, n, n_classes,
+                       order_in, order_out, active, cand, max_features, score, valid, (int)(level >= max_depth), o,
+                       split_ws);
+    hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
+                       node_capacity, left, right, next_active, counter);
+    HYPEL_CHECK_LAUNCH("hypel_forest_split_apply_thr");
     return 0;
 }
 

@@ -954,6 +954,30 @@ int hypel_tensor_summary_f32(const float* base, const int64_t* table, int32_t n_
  *   the nodes that split before it keep theirs).  split_ws: int32 [n_active], left holding nL of a node that split
  *   and 0 of a leaf.  No node array is touched outside the records of the active nodes, no record of score, best_bin,
  *   valid or next_active outside the ones named here.
+ * Extra-trees (reference classify/classic_ml_trainer.py:50, ExtraTreesClassifier): the same level-wise growth over the
+ *   same operands -- y, weight, order, active, cand, the node arrays, split_ws, next_active and counter mean what they
+ *   mean above -- but the split search reads the raw float32 values and never the bins: per record one random cut inside
+ *   the node's range.
+ * hypel_forest_columns_f32: xt[c * ldn + i] = x[i * ld + c] + 0.0f for i < n, c < f, ldn >= n: the feature-major float32
+ *   copy with the sign of zero removed (so that a range does not depend on the order in which equal zeros are met).
+ *   Elements i >= n of a row of xt are not written.
+ * hypel_forest_split_random: one record per (active node a, slot s), at a * max_features + s, column c = cand[a][s];
+ *   u float32 [n_active][max_features] in [0, 1) (drawn on the host).  Over the node's rows r = order[start .. start +
+ *   count): lo = min xt[c][r], hi = max xt[c][r].  The record is valid when count >= 2 and lo < hi.  The cut is formed in
+ *   float32, one rounding each, no contraction: d = hi - lo; m = u * d; t = lo + m; if (!(t < hi)) t = lo  (scikit-learn's
+ *   own guard; it also catches d = inf of a column that spans more than the float32 range).  Hence lo <= t < hi and both
+ *   sides hold a row, and weight: every row of a segment has weight >= 1 (order holds in-bag rows).  L_k = the weight
+ *   of class k over the rows with xt[c][r] <= t, R_k the rest; score = (double)sum_k
+ *   L_k^2 / (double)nL + (double)sum_k R_k^2 / (double)nR as in hypel_forest_split_hist: the sums of squares exact in
+ *   int64, two divisions and one addition, each rounded once, no contraction.  Written: score, thr = t, valid = 1; or
+ *   (0.0, 0.0f, 0).  No record of score, thr or valid outside n_active * max_features is touched.
+ * hypel_forest_split_apply_thr: hypel_forest_split_apply with xt, ldn for bins, ldn and thr (float32, the table above) for
+ *   best_bin and edges.  The best valid slot is the one with the largest score, then the lower column index (a node's
+ *   columns are distinct: a total order).  Leaf reasons, node record, value, the compaction into next_active, counter
+ *   (-1 at node_capacity included) and split_ws are exactly those of hypel_forest_split_apply, with two differences:
+ *   threshold[node] = thr of the chosen slot (0 for a leaf) and thr_bin[node] = -1 always.  The stable partition goes by
+ *   xt[feature][r] <= threshold, the float32 compare of the serving walk: every training row reaches the leaf it was
+ *   counted in.  Integer atomics only, as above: two runs write identical bytes.
  * Serving: a model is one array of hypel_forest_node_t over all trees, 16-byte aligned (a record is one load; another
  *   alignment is refused) -- tree t's root is node tree_off[t] (int32 [n_trees]).  A node with left < 0 is a leaf and
  *   ends the walk at row -1 - left of leaf_value (fp64 [n_leaves][n_classes]); otherwise the walk goes to node `left` when x[feature] <= threshold (float32 compare) and to
@@ -992,6 +1016,20 @@ int hypel_forest_split_apply(const uint8_t* bins, int64_t ldn, const int32_t* y,
                              int32_t* thr_bin, float* threshold, int32_t* left, int32_t* right, int32_t* node_tree,
                              int32_t* node_count, int32_t* node_weight, double* value, int32_t* split_ws,
                              int32_t* next_active, int32_t* counter, hypel_stream_t stream);
+int hypel_forest_columns_f32(const float* x, int64_t ld, int64_t n, int32_t f, float* xt, int64_t ldn,
+                             hypel_stream_t stream);
+int hypel_forest_split_random(const float* xt, int64_t ldn, const int32_t* y, const int32_t* weight, int64_t n,
+                              int32_t n_classes, const int32_t* order, const int32_t* active, int32_t n_active,
+                              const int32_t* cand, const float* u, int32_t max_features, int32_t f, double* score,
+                              float* thr, int32_t* valid, hypel_stream_t stream);
+int hypel_forest_split_apply_thr(const float* xt, int64_t ldn, const int32_t* y, const int32_t* weight, int64_t n,
+                                 int32_t n_classes, const int32_t* order_in, int32_t* order_out, const int32_t* active,
+                                 int32_t n_active, const int32_t* cand, int32_t max_features, int32_t f,
+                                 const double* score, const float* thr, const int32_t* valid, int32_t level,
+                                 int32_t max_depth, int32_t node_base, int32_t node_capacity, int32_t* feature,
+                                 int32_t* thr_bin, float* threshold, int32_t* left, int32_t* right, int32_t* node_tree,
+                                 int32_t* node_count, int32_t* node_weight, double* value, int32_t* split_ws,
+                                 int32_t* next_active, int32_t* counter, hypel_stream_t stream);
 int hypel_forest_predict_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off, int32_t n_trees,
                               const hypel_forest_node_t* nodes, int32_t n_nodes, const double* leaf_value,
                               int32_t n_leaves, int32_t n_classes, const uint8_t* class_labels, const int32_t* points,

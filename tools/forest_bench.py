@@ -6,7 +6,13 @@ hypel_forest_predict_rows it replaces (floor: every patch written once and read 
 scikit-learn is importable, RandomForestClassifier(n_jobs=16) on the CPU for scale: its fit, and its prediction of
 --sklearn_rows scene rows.
 
-    python tools/forest_bench.py [--path grss2013] [--trees 50] [--max_features 24] [--scene_h 349] [--scene_w 1905]"""
+--estimator extra_trees measures hypelcnn_amd.classic.forest.ExtraTreesForest the same way (scikit-learn's
+ExtraTreesClassifier for scale) and adds `fit_levels`: per level the event times of hypel_forest_split_random and
+hypel_forest_split_apply_thr beside the records, the rows they cover and the byte floor of the search -- per record its
+rows of one xt column twice (the range, then the counts) plus order, y and weight once, 20 bytes a row, at 6.2 TB/s.
+
+    python tools/forest_bench.py [--estimator forest] [--path grss2013] [--trees 50] [--max_features 24]
+                                 [--scene_h 349] [--scene_w 1905]"""
 import argparse
 import json
 import os
@@ -19,7 +25,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from hypelcnn_amd.backend import HipBackend  # noqa: E402
-from hypelcnn_amd.classic.forest import ForestClassifier  # noqa: E402
+from hypelcnn_amd.classic.forest import ExtraTreesForest, ForestClassifier  # noqa: E402
 from hypelcnn_amd.common.common_nn_ops import SceneArrays, get_loader_from_name  # noqa: E402
 from hypelcnn_amd.importer.InMemoryImporter import InMemoryImporter  # noqa: E402
 
@@ -54,6 +60,19 @@ def table(log):
     return {k: {kk: (round(vv, 1) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in rows.items()}
 
 
+def level_table(log, level_rows, max_features):
+    """extra_trees: one row per level from the launch log (one search and one apply launch a level, in order)"""
+    search = [us for name, us in log if name == "forest_split_random"]
+    apply = [us for name, us in log if name == "forest_split_apply_thr"]
+    out = []
+    for level, (nodes, rows) in enumerate(level_rows):
+        floor_us = 20.0 * rows * max_features / STREAM_BYTES_PER_S * 1e6
+        out.append({"level": level, "nodes": nodes, "records": nodes * max_features, "node_rows": rows,
+                    "split_random_us": round(search[level], 1), "split_random_floor_us": round(floor_us, 2),
+                    "split_apply_thr_us": round(apply[level], 1)})
+    return out
+
+
 def timed(fn, repeats=3):
     """best wall time of `repeats` synchronised calls, after one warm-up"""
     fn()
@@ -69,12 +88,16 @@ def timed(fn, repeats=3):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--estimator", default="forest", choices=("forest", "extra_trees"))
     ap.add_argument("--path", default="grss2013")
     ap.add_argument("--trees", type=int, default=50)
     ap.add_argument("--max_features", type=int, default=24)
     ap.add_argument("--neighborhood", type=int, default=2)
     ap.add_argument("--scene_h", type=int, default=349)
     ap.add_argument("--scene_w", type=int, default=1905)
+    ap.add_argument("--fit_repeats", type=int, default=2,
+                    help="timed fits after one warm-up; 0: fit_s is the wall time of the one event-timed fit "
+                         "(its per-launch synchronisation included), for tree counts whose host draws take minutes")
     ap.add_argument("--sklearn", type=int, default=1)
     ap.add_argument("--sklearn_rows", type=int, default=20000)
     args = ap.parse_args()
@@ -84,16 +107,32 @@ def main():
     Xv, yv = va.data.reshape(len(va.data), -1), va.labels
     hip = HipBackend()
     kw = dict(n_estimators=args.trees, max_features=args.max_features)
-    result = {"tool": "forest_bench", "config": {"path": args.path, **kw}, "train_rows": int(len(X)),
-              "features": int(X.shape[1])}
+    result = {"tool": "forest_bench", "config": {"estimator": args.estimator, "path": args.path, **kw},
+              "train_rows": int(len(X)), "features": int(X.shape[1])}
+    extra = args.estimator == "extra_trees"
+    level_rows = []
 
-    fit_s = timed(lambda: ForestClassifier(backend=hip, **kw).fit(X, y), repeats=2)
-    model = ForestClassifier(backend=hip, **kw).fit(X, y)
+    class Estimator(ExtraTreesForest if extra else ForestClassifier):
+        def _level_done(self, level, active, n_active, *tables):
+            if self.count_levels:
+                level_rows.append((n_active, int(active[:4 * n_active].view(n_active, 4)[:, 2].sum())))
+    Estimator.count_levels = False
+
+    if args.fit_repeats:
+        fit_s = timed(lambda: Estimator(backend=hip, **kw).fit(X, y), repeats=args.fit_repeats)
+    log = TimedBackend(hip)
+    Estimator.count_levels = True
+    t0 = time.perf_counter()
+    model = Estimator(backend=log, **kw).fit(X, y)
+    if not args.fit_repeats:
+        fit_s = time.perf_counter() - t0
+    Estimator.count_levels = False
+    model._be = hip
     result.update(fit_s=round(fit_s, 4), nodes=int(len(model.feature_)), levels=int(model.n_levels_),
                   validation_oa=float((model.predict(Xv) == yv).mean()))
-    log = TimedBackend(hip)
-    ForestClassifier(backend=log, **kw).fit(X, y)
     result["fit_launches"] = table(log.log)
+    if extra:
+        result["fit_levels"] = level_table(log.log, level_rows, model._resolve_max_features(X.shape[1]))
     result["fit_launch_sum_s"] = round(sum(us for _, us in log.log) * 1e-6, 4)
 
     # whole-scene serving on a scene of the real size (the model's features are the same window of the same bands)
@@ -118,7 +157,9 @@ def main():
                        "gather_over_direct": round(gather_s / direct_s, 2), "same_raster": same}
     if args.sklearn:
         try:
-            from sklearn.ensemble import RandomForestClassifier
+            from sklearn.ensemble import ExtraTreesClassifier, RandomForestClassifier
+            if extra:
+                RandomForestClassifier = ExtraTreesClassifier
         except ImportError:
             RandomForestClassifier = None
         if RandomForestClassifier is not None:
