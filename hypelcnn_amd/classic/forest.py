@@ -18,8 +18,18 @@ _prepare_columns and _split_level for what differs.
 
 predict: hypel_forest_predict_rows walks every tree per row and averages the leaf rows in fp64.  predict_scene walks the
 trees straight on the padded scene (hypel_forest_predict_scene) where the data set has one resolution, else it cuts
-patches chunk by chunk and uses the row kernel.  There is no CPU fallback: the `backend` argument exists so that the
-tests can run this file on their numpy emulation of the same entry points."""
+patches chunk by chunk and uses the row kernel.
+
+Diagnostics, methods of both classes and of a model loaded with from_arrays (what scikit-learn's forests carry as
+attributes; none is a constructor argument, get_params() does not change): out_of_bag (hypel_forest_oob_rows: the vote
+of the trees whose bootstrap left a training row out -- oob_decision_function_, oob_votes_, oob_score_),
+feature_importances (hypel_forest_importances_f64: mean decrease in impurity from node_weight_ and Gini of value_, every
+sum in an order the header states) and permutation_importance (hypel_forest_permuted_hits: the columns of a group,
+c % group_mod, read from a partner row inside the walk; group_mod = the channel count of flattened patches asks which
+band, at every window position together, carries the decision).
+
+There is no CPU fallback: the `backend` argument exists so that the tests can run this file on their numpy emulation
+of the same entry points."""
 import numpy as np
 import torch
 
@@ -58,7 +68,8 @@ class ForestClassifier:
     tree_offsets_[t] .. tree_offsets_[t + 1]; feature_ (-1: leaf), threshold_ (float32), left_ / right_ (tree-local
     child numbers like scikit-learn's children_left / children_right, -1: leaf), leaf_ (row of leaf_value_, -1: inner
     node), value_ [n_nodes, n_classes] (class weight fractions), leaf_value_ = value_ of the leaves; after fit also
-    threshold_bin_, node_count_ (unique rows) and node_weight_."""
+    threshold_bin_, node_count_ (unique rows), node_weight_ and bootstrap_counts_ [n_trees, n].  After out_of_bag():
+    oob_decision_function_, oob_votes_, oob_score_; after feature_importances(): importances_n_used_."""
 
     def __init__(self, n_estimators=50, max_features=24, bootstrap=True, max_depth=None, n_bins=256, seed=0,
                  backend=None, chunk_rows=None):
@@ -207,6 +218,7 @@ class ForestClassifier:
         child = lambda a: np.where(a[by_tree] >= 0, new_id[np.maximum(a[by_tree], 0)] - first, -1).astype(np.int32)  # noqa: E731
         self.threshold_bin_ = got["thr_bin"][by_tree]
         self.node_count_, self.node_weight_ = got["node_count"][by_tree], got["node_weight"][by_tree]
+        self.__dict__.pop("impurity_", None)  # (of an earlier from_arrays: a grown forest's impurity is Gini from value_)
         self._set_model(f, got["feature"][by_tree], threshold.cpu().numpy()[:n_nodes][by_tree], child(got["left"]),
                         child(got["right"]), offsets,
                         value.cpu().numpy()[:n_nodes * n_cls].reshape(n_nodes, n_cls)[by_tree])
@@ -214,15 +226,24 @@ class ForestClassifier:
 
     # ---- the served model ----------------------------------------------------------------------------------------
     @classmethod
-    def from_arrays(cls, classes, n_features, feature, threshold, left, right, tree_offsets, value, backend=None):
+    def from_arrays(cls, classes, n_features, feature, threshold, left, right, tree_offsets, value, backend=None,
+                    node_weight=None, impurity=None):
         """A served model from flat node arrays (see the class docstring; scikit-learn's tree_.feature, .threshold,
         .children_left, .children_right and .value[:, 0, :] of every estimator, concatenated).  float64 thresholds are
-        rounded DOWN to float32."""
+        rounded DOWN to float32.  node_weight and impurity (optional; tree_.weighted_n_node_samples and tree_.impurity)
+        are what feature_importances() needs: without impurity it is Gini from `value`."""
         self = cls(n_estimators=len(tree_offsets) - 1, backend=backend)
         self.classes_ = np.asarray(classes)
         self._check_classes(self.classes_)
         self._set_model(int(n_features), np.asarray(feature), np.asarray(threshold), np.asarray(left), np.asarray(right),
                         np.asarray(tree_offsets), np.asarray(value, np.float64))
+        for name, a in (("node_weight_", node_weight), ("impurity_", impurity)):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64).reshape(-1)
+                if len(a) != len(self.feature_):
+                    raise ValueError(f"ForestClassifier.from_arrays: {name[:-1]} has {len(a)} entries, the model "
+                                     f"{len(self.feature_)} nodes")
+                setattr(self, name, a)
         return self
 
     def _set_model(self, n_features, feature, threshold, left, right, tree_offsets, value):
@@ -312,6 +333,121 @@ class ForestClassifier:
 
     def predict_proba(self, X):
         return self._run(X, True)[1]
+
+    # ---- diagnostics -------------------------------------------------------------------------------------------
+    def _class_index(self, y, n, where):
+        """labels -> int32 indices into classes_ (-1: a label the model does not know; it never counts as a hit)"""
+        y = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y).reshape(-1)
+        if len(y) != n:
+            raise ValueError(f"{self._name}.{where}: {n} rows, {len(y)} labels")
+        at = np.minimum(np.searchsorted(self.classes_, y), len(self.classes_) - 1)
+        return y, np.where(self.classes_[at] == y, at, -1).astype(np.int32)
+
+    def out_of_bag(self, X, y, in_bag_counts=None):
+        """scikit-learn's oob_score=True on the device (hypel_forest_oob_rows): every row of the training matrix X is
+        voted on by the trees whose bootstrap left it out.  Sets oob_decision_function_ [n, n_classes] (the mean leaf
+        row of the voting trees; zeros where no tree votes), oob_votes_ [n] and oob_score_ (the accuracy of the
+        first-maximum labels, computed on the host) and returns the score.  in_bag_counts [n_trees, n] defaults to the
+        bootstrap_counts_ of fit(); a model from from_arrays passes its own (scikit-learn: the bincount of
+        _generate_sample_indices per estimator)."""
+        be = self._backend()
+        self._fitted()
+        counts = getattr(self, "bootstrap_counts_", None) if in_bag_counts is None else np.asarray(in_bag_counts)
+        if in_bag_counts is None and not self.bootstrap:
+            raise ValueError("Out of bag estimation only available if bootstrap=True")
+        if counts is None:
+            raise ValueError(f"{self._name}.out_of_bag: a model from from_arrays has no bootstrap_counts_: pass "
+                             f"in_bag_counts [n_trees, n]")
+        n, n_cls, n_trees = X.shape[0], len(self.classes_), self.n_estimators
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"{self._name}.out_of_bag: X has {X.shape[1]} features, the model was fitted on "
+                             f"{self.n_features_in_}")
+        if counts.shape != (n_trees, n):
+            raise ValueError(f"{self._name}.out_of_bag: in-bag counts of shape {counts.shape}, X has {n} rows and the "
+                             f"forest {n_trees} trees: out-of-bag rows are rows of the training matrix")
+        y, _ = self._class_index(y, n, "out_of_bag")
+        w_d = be.upload(np.ascontiguousarray(counts, np.int32))
+        idx, votes = be.zeros(_round_up(n, 4), torch.uint8), be.zeros(n, torch.int32)
+        proba = be.zeros(n * n_cls, torch.float64)
+        step = self._chunk(n)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            x, m, f = self._rows(X[r0:r1])
+            be.call("forest_oob_rows", Ref(x), f, m, f, *self._model_args(self._dev["nodes"]), None, Ref(w_d, r0), n,
+                    Ref(idx, r0), Ref(proba, r0 * n_cls), Ref(votes, r0))
+            be.synchronize()  # x dies here
+        self.oob_decision_function_ = proba.cpu().numpy().reshape(n, n_cls)
+        self.oob_votes_ = votes.cpu().numpy()
+        self.oob_score_ = float(np.mean(self.classes_[idx.cpu().numpy()[:n]] == y))
+        if (self.oob_votes_ == 0).any():
+            import warnings
+            warnings.warn(f"{self._name}.out_of_bag: {int((self.oob_votes_ == 0).sum())} of {n} rows are in every tree's "
+                          f"bag (too few trees): their row of oob_decision_function_ is zeros and counts as class "
+                          f"{self.classes_[0]!r}")
+        return self.oob_score_
+
+    def feature_importances(self, per_tree=False):
+        """scikit-learn's feature_importances_ (mean decrease in impurity) on the device
+        (hypel_forest_importances_f64): node_weight_ of the fit and Gini from value_, or the node_weight / impurity
+        given to from_arrays.  Returns [n_features] (sum 1, or all zeros where no tree has a split), with
+        per_tree=True the pair (that, [n_trees, n_features] normalised per tree); importances_n_used_ = the trees with
+        more than one node."""
+        be = self._backend()
+        self._fitted()
+        weight = getattr(self, "node_weight_", None)
+        if weight is None:
+            raise ValueError(f"{self._name}.feature_importances: the model was loaded without node_weight "
+                             f"(from_arrays(..., node_weight=tree_.weighted_n_node_samples))")
+        impurity = getattr(self, "impurity_", None)
+        f, n_trees, n_nodes = self.n_features_in_, self.n_estimators, len(self.feature_)
+        rows, imp, used = be.zeros(n_trees * f, torch.float64), be.zeros(f, torch.float64), be.zeros(1, torch.int32)
+        w_d = be.upload(np.ascontiguousarray(weight, np.float64))
+        v_d = be.upload(np.ascontiguousarray(self.value_, np.float64))
+        i_d = None if impurity is None else be.upload(impurity)
+        be.call("forest_importances_f64", Ref(self._dev["nodes"]), n_nodes, Ref(self._dev["tree_off"]), n_trees, Ref(v_d),
+                len(self.classes_), Ref(w_d), None if i_d is None else Ref(i_d), f, Ref(rows), Ref(imp), Ref(used))
+        be.synchronize()
+        self.importances_n_used_ = int(used.cpu()[0])
+        out = imp.cpu().numpy()
+        return (out, rows.cpu().numpy().reshape(n_trees, f)) if per_tree else out
+
+    def permutation_importance(self, X, y, n_repeats=5, group_mod=None, seed=0, groups_per_launch=None):
+        """Grouped permutation importance on the device (hypel_forest_permuted_hits): column c belongs to group
+        c % group_mod (None: every column its own group; the channel count of flattened patches: one band at every
+        window position).  Per repeat ONE permutation of the rows is drawn, numpy.random.Generator(PCG64(seed)),
+        rng.permutation(n), and shared by all groups; a group's columns are read from the partner row, the others from
+        the row itself, inside the walk -- no permuted copy of X is made, but all of X is on the device at once.
+        Returns a dict: baseline (accuracy of predict), hits int64 [groups, repeats] (rows still classified as y),
+        importances = baseline - hits / n, importances_mean and importances_std (over the repeats, ddof 0).  This is
+        not sklearn.inspection.permutation_importance's random stream (it redraws per column)."""
+        be = self._backend()
+        self._fitted()
+        x, n, f = self._rows(X)
+        if f != self.n_features_in_:
+            raise ValueError(f"{self._name}.permutation_importance: X has {f} features, the model was fitted on "
+                             f"{self.n_features_in_}")
+        group_mod = f if group_mod is None else int(group_mod)
+        n_repeats = int(n_repeats)
+        if group_mod < 1 or n_repeats < 1:
+            raise ValueError(f"{self._name}.permutation_importance: group_mod={group_mod}, n_repeats={n_repeats}: both >= 1")
+        y, yi = self._class_index(y, n, "permutation_importance")
+        baseline = float(np.mean(self.predict(X) == y))
+        rng = np.random.Generator(np.random.PCG64(seed))
+        partner = be.upload(np.stack([rng.permutation(n) for _ in range(n_repeats)]).astype(np.int32))
+        y_d = be.upload(yi)
+        row_blocks = (n + 63) // 64
+        # groups per launch: the grid below 2^24 blocks (far inside the entry point's 2^31 - 1), the hit table with it
+        step = groups_per_launch or max(1, (1 << 24) // (row_blocks * n_repeats))
+        hits = np.zeros((group_mod, n_repeats), np.int64)
+        for g0 in range(0, group_mod, step):
+            g = min(step, group_mod - g0)
+            part = be.zeros(g * n_repeats, torch.int32)
+            be.call("forest_permuted_hits", Ref(x), f, n, f, *self._model_args(self._dev["nodes"]), Ref(y_d),
+                    Ref(partner), n_repeats, group_mod, g0, g, Ref(part))
+            hits[g0:g0 + g] = part.cpu().numpy().reshape(g, n_repeats)
+        imp = baseline - hits / float(n)
+        return {"baseline": baseline, "hits": hits, "importances": imp, "importances_mean": imp.mean(1),
+                "importances_std": imp.std(1)}
 
     def predict_scene(self, arrays, raster, raster_w, direct=None):
         """Whole-scene path: `arrays` is a common_nn_ops.SceneArrays fed with the padded scene and the (x, y) targets,

@@ -17,6 +17,12 @@ Differences from the reference, all on purpose:
    raw float32 values (hypelcnn_amd.classic.forest.ExtraTreesForest), under the same three flags --forest_trees,
    --forest_max_features and --forest_seed (--forest_bins is ignored: nothing is quantised); no bootstrap, as in
    scikit-learn;
+ - what scikit-learn's forests carry as attributes is asked for by NEW flags, valid with forest and extra_trees only and
+   computed on the device: --forest_oob (oob_score_ on the training rows; extra_trees, built without
+   bootstrap, answers with scikit-learn's ValueError), --forest_importances (feature_importances_) and
+   --forest_permutation_repeats N (a permutation importance per band on the validation rows, one band at every window
+   position permuted together).  They write forest_diagnostics_<loader>_run<i>.json, band_importance_<loader>_run<i>.csv
+   and feature_importance_<loader>_run<i>.npy after the reference's three files, which do not change;
  - the reference's search (:126-136, GridSearchCV(SVC(), C x gamma) over StratifiedShuffleSplit(2, 0.1, 42)) runs on
    the device under a NEW flag, --svc_grid (hypelcnn_amd.classic.model_selection): after the baseline fit and its three
    files it searches the flattened training data, prints the reference's line and writes svc_grid_<loader>_run<i>.json;
@@ -63,6 +69,14 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--forest_bins", nargs="?", type=int, default=256, help="Bins per feature, 2..256 (forest; ignored by extra_trees, which quantises nothing)")
     parser.add_argument("--forest_seed", nargs="?", type=int, default=0,
                         help="Seed of the forest's random stream; episode i of --split_count uses seed + i")
+    parser.add_argument("--forest_oob", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, scores the forest out of bag on the training rows (forest; extra_trees is built "
+                             "without bootstrap and refuses).")
+    parser.add_argument("--forest_importances", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, writes the impurity importances per feature and per band (forest, extra_trees).")
+    parser.add_argument("--forest_permutation_repeats", nargs="?", type=int, default=0,
+                        help="Repeats of the per-band permutation importance on the validation rows; 0: off (forest, "
+                             "extra_trees)")
     parser.add_argument("--svc_grid", nargs="?", const=True, type=type_ensure_strtobool, default=False,
                         help="If true, searches C x gamma on the device after the baseline fit (reference :126-136).")
     # (a decade range such as -2:10:13 starts with '-' and is no number, so argparse would take it for an option:
@@ -164,6 +178,47 @@ def perform_full_scene_classification(data_path, loader_name, neighborhood, esti
     return scene_as_image
 
 
+def forest_diagnostics_asked(flags):
+    return [name for name, on in (("--forest_oob", flags.forest_oob), ("--forest_importances", flags.forest_importances),
+                                  ("--forest_permutation_repeats", flags.forest_permutation_repeats > 0)) if on]
+
+
+def perform_forest_diagnostics(flags, estimator, training, validation, run_index):
+    """The forest's own diagnostics, after the reference's three files: forest_diagnostics_<loader>_run<i>.json (the
+    out-of-bag score, the rows without a vote, the trees the importances used), band_importance_<loader>_run<i>.csv
+    (per band: the impurity importance summed over the window, the permutation mean and standard deviation; nan for
+    what was not asked) and feature_importance_<loader>_run<i>.npy ([p, p, channels], with --forest_importances)."""
+    p, channels = training.data.shape[1], training.data.shape[3]
+    file_id = f"{flags.loader_name}_run{run_index}"
+    report = {"estimator": flags.estimator, "oob_score": None, "oob_rows_without_vote": None, "n_used": None,
+              "permutation_repeats": flags.forest_permutation_repeats, "permutation_baseline": None}
+    per_band = numpy.full((channels, 3), numpy.nan)
+    os.makedirs(flags.base_log_path, exist_ok=True)
+    if flags.forest_oob:
+        report["oob_score"] = estimator.out_of_bag(flatten_data(training.data), training.labels)
+        report["oob_rows_without_vote"] = int((estimator.oob_votes_ == 0).sum())
+        print("OOB:%5.5f" % report["oob_score"])
+    if flags.forest_importances:
+        importances = estimator.feature_importances().reshape(p, p, channels)
+        report["n_used"] = estimator.importances_n_used_
+        per_band[:, 0] = importances.sum((0, 1))
+        numpy.save(os.path.join(flags.base_log_path, f"feature_importance_{file_id}.npy"), importances)
+    if flags.forest_permutation_repeats > 0:
+        result = estimator.permutation_importance(flatten_data(validation.data), validation.labels,
+                                                  n_repeats=flags.forest_permutation_repeats, group_mod=channels,
+                                                  seed=flags.forest_seed + run_index)
+        report["permutation_baseline"] = result["baseline"]
+        per_band[:, 1], per_band[:, 2] = result["importances_mean"], result["importances_std"]
+    if flags.forest_importances or flags.forest_permutation_repeats > 0:
+        with open(os.path.join(flags.base_log_path, f"band_importance_{file_id}.csv"), "w") as band_file:
+            print("band,impurity_importance,permutation_mean,permutation_std", file=band_file)
+            for band, row in enumerate(per_band):
+                print("%d,%.17g,%.17g,%.17g" % (band, *row), file=band_file)
+    with open(os.path.join(flags.base_log_path, f"forest_diagnostics_{file_id}.json"), "w") as report_file:
+        json.dump(report, report_file)
+    return report
+
+
 def parse_decades(text, flag):
     """'lo:hi:n' -> numpy.logspace(lo, hi, n), the form of the reference's two ranges (:127-128)"""
     try:
@@ -236,6 +291,9 @@ def main(argv=None, backend=None):
             "(--svc_grid_c / --svc_grid_gamma / --svc_grid_refit)")
     if flags.svc_grid and flags.estimator in ("forest", "extra_trees"):
         raise ValueError(f"--svc_grid searches the SVC's C x gamma: not with --estimator {flags.estimator}")
+    if forest_diagnostics_asked(flags) and flags.estimator not in ("forest", "extra_trees"):
+        raise ValueError(f"{', '.join(forest_diagnostics_asked(flags))}: diagnostics of a forest (--estimator forest or "
+                         f"extra_trees), not of --estimator {flags.estimator}")
     results = []
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)
@@ -251,6 +309,8 @@ def main(argv=None, backend=None):
         overall_accuracy, average_accuracy, kappa = scores(conf_matrix)
         print_output(estimator.get_params(), average_accuracy, conf_matrix, kappa, overall_accuracy, run_index,
                      flags.loader_name, flags.base_log_path)
+        if forest_diagnostics_asked(flags):
+            estimator.diagnostics_ = perform_forest_diagnostics(flags, estimator, training, validation, run_index)
         if flags.svc_grid:
             grid = perform_grid_search(flags, flatten_data(training.data), training.labels, run_index, backend)
             if flags.svc_grid_refit:

@@ -19,7 +19,16 @@
 //                          so a block holds no second wavefront that would wait on the slowest; a node is one
 //                          16-byte record, so a step is two dependent loads (the node, the value); the class sums
 //                          are fp64 in LDS, one column per lane, sized by n_classes so that LDS does not cap the
-//                          wavefronts per CU that hide those loads.
+//                          wavefronts per CU that hide those loads.  Which trees vote is a functor of the one
+//                          walk_and_vote: all of them when serving.
+//   * oob_rows_kernel    : the same walk and vote by the trees whose bootstrap left the row out; the number of votes
+//                          and the means are written beside the label.
+//   * permuted_hits_kernel: the same walk per (group of columns, repeat, row) with the group's columns read from a
+//                          partner row; the rows still classified as y are counted by a wave sum and one integer
+//                          atomic per block.
+//   * importance_raw_kernel: one workgroup per (tree, window of columns): per-column fp64 sums of the nodes' impurity
+//                          decreases in LDS, in node order by claiming columns (integer atomicMin), no fp atomic;
+//                          normalise_rows_kernel and importance_mean_kernel finish scikit-learn's arithmetic.
 // Integer atomics only (sums of int32 weights are exact and commute); every choice among equals is a total order
 // (score, then feature index, then bin) and every list is built by a prefix sum, so two runs write identical bytes.
 #include <limits.h>
@@ -493,13 +502,26 @@ struct SceneReader {  // feature = 2 * (element offset from the window origin's 
 
 constexpr int PRED_LANES = 64;
 
-template <class Reader>
-__device__ __forceinline__ void walk_and_vote(const Model& m, const Reader& read, double* acc, int lane,
-                                              const uint8_t* __restrict__ class_labels, uint8_t* __restrict__ out,
-                                              double* __restrict__ proba) {
+// Which trees vote for a row: every tree when serving; out of bag, the trees whose bootstrap left the row out.
+struct AllTrees {
+    __device__ __forceinline__ bool skip(int) const { return false; }
+};
+struct OutOfBag {
+    const int32_t* in_bag;  // the row's column of the count table: tree t's count at in_bag[t * ldw]
+    int64_t ldw;
+    __device__ __forceinline__ bool skip(int t) const { return in_bag[(int64_t)t * ldw] > 0; }
+};
+
+// The winner's class index; n_votes = the trees that voted (a row without a vote has means 0 and winner 0).
+template <class Reader, class Trees>
+__device__ __forceinline__ int walk_and_vote(const Model& m, const Reader& read, const Trees& trees, double* acc,
+                                             int lane, double* __restrict__ proba, int& n_votes) {
     const int C = m.n_classes;
     for (int k = 0; k < C; ++k) acc[k * PRED_LANES + lane] = 0.0;
+    int votes = 0;
     for (int t = 0; t < m.n_trees; ++t) {
+        if (trees.skip(t)) continue;
+        ++votes;
         int4 rec = m.nodes[m.tree_off[t]];  // (feature, threshold bits, left, right); left < 0: leaf row -1 - left
         for (int step = 0; rec.z >= 0 && step < m.n_nodes; ++step)  // (bounded: a child's index exceeds its parent's)
             rec = m.nodes[read(rec.x) <= __int_as_float(rec.y) ? rec.z : rec.w];
@@ -508,17 +530,18 @@ __device__ __forceinline__ void walk_and_vote(const Model& m, const Reader& read
             for (int k = 0; k < C; ++k) acc[k * PRED_LANES + lane] += row[k];
         }
     }
+    n_votes = votes;
     int best = 0;
     double bv = -1.0;
     for (int k = 0; k < C; ++k) {
-        const double v = acc[k * PRED_LANES + lane] / (double)m.n_trees;
+        const double v = votes > 0 ? acc[k * PRED_LANES + lane] / (double)votes : 0.0;
         if (proba) proba[k] = v;
         if (v > bv) {  // the first maximum
             bv = v;
             best = k;
         }
     }
-    *out = class_labels ? class_labels[best] : (uint8_t)best;
+    return best;
 }
 
 __global__ __launch_bounds__(PRED_LANES) void predict_rows_kernel(const float* __restrict__ x, int64_t ld, int64_t n,
@@ -531,7 +554,9 @@ __global__ __launch_bounds__(PRED_LANES) void predict_rows_kernel(const float* _
     if (i >= n) return;
     const RowReader read = {x + i * ld};
     uint8_t* o = points ? out + (int64_t)points[2 * i + 1] * raster_w + points[2 * i] : out + i;
-    walk_and_vote(m, read, acc, threadIdx.x, class_labels, o, proba ? proba + i * m.n_classes : nullptr);
+    int votes;
+    const int best = walk_and_vote(m, read, AllTrees(), acc, threadIdx.x, proba ? proba + i * m.n_classes : nullptr, votes);
+    *o = class_labels ? class_labels[best] : (uint8_t)best;
 }
 
 __global__ __launch_bounds__(PRED_LANES) void predict_scene_kernel(const float* __restrict__ casi,
@@ -545,7 +570,186 @@ __global__ __launch_bounds__(PRED_LANES) void predict_scene_kernel(const float* 
     const int64_t px = points[2 * i], py = points[2 * i + 1];
     const int64_t origin = py * wp + px;
     const SceneReader read = {casi + origin * cc, lidar ? lidar + origin * cl : nullptr};
-    walk_and_vote(m, read, acc, threadIdx.x, class_labels, out + py * raster_w + px, nullptr);
+    int votes;
+    const int best = walk_and_vote(m, read, AllTrees(), acc, threadIdx.x, nullptr, votes);
+    out[py * raster_w + px] = class_labels ? class_labels[best] : (uint8_t)best;
+}
+
+// ---- diagnostics: out-of-bag vote, grouped permutation hits, mean decrease in impurity ----------------------------------
+__global__ __launch_bounds__(PRED_LANES) void oob_rows_kernel(const float* __restrict__ x, int64_t ld, int64_t n, Model m,
+                                                              const uint8_t* __restrict__ class_labels,
+                                                              const int32_t* __restrict__ weight, int64_t ldw,
+                                                              uint8_t* __restrict__ out, double* __restrict__ proba,
+                                                              int32_t* __restrict__ votes) {
+    extern __shared__ double acc[];  // [n_classes][PRED_LANES]
+    const int64_t i = (int64_t)blockIdx.x * PRED_LANES + threadIdx.x;
+    if (i >= n) return;
+    const RowReader read = {x + i * ld};
+    const OutOfBag trees = {weight + i, ldw};
+    int nv;
+    const int best = walk_and_vote(m, read, trees, acc, threadIdx.x, proba + i * m.n_classes, nv);
+    votes[i] = nv;
+    out[i] = class_labels ? class_labels[best] : (uint8_t)best;
+}
+
+struct PermutedReader {  // the columns of group g come from the partner row
+    const float *row, *other;
+    int group_mod, g;
+    __device__ __forceinline__ float operator()(int feature) const {
+        return (feature % group_mod == g ? other : row)[feature];
+    }
+};
+
+// One block per (group, repeat, 64 rows); no lane leaves before the wave sum.
+__global__ __launch_bounds__(PRED_LANES) void permuted_hits_kernel(const float* __restrict__ x, int64_t ld, int64_t n,
+                                                                   int64_t row_blocks, Model m,
+                                                                   const int32_t* __restrict__ y,
+                                                                   const int32_t* __restrict__ partner, int n_repeats,
+                                                                   int group_mod, int g0, int32_t* __restrict__ hits) {
+    extern __shared__ double acc[];  // [n_classes][PRED_LANES]
+    const int64_t rec = blockIdx.x / row_blocks, rb = blockIdx.x - rec * row_blocks;
+    const int gi = (int)(rec / n_repeats), r = (int)(rec - (int64_t)gi * n_repeats);
+    const int64_t i = rb * PRED_LANES + threadIdx.x;
+    int hit = 0;
+    if (i < n) {
+        int64_t p = partner[(int64_t)r * n + i];
+        if (p < 0 || p >= n) p = i;  // (a permutation of the rows by contract; never read outside x)
+        const PermutedReader read = {x + i * ld, x + p * ld, group_mod, g0 + gi};
+        int votes;
+        hit = walk_and_vote(m, read, AllTrees(), acc, threadIdx.x, nullptr, votes) == y[i];
+    }
+    hit = wave_sum(hit);
+    if (threadIdx.x == 0 && hit) atomicAdd(&hits[(int64_t)gi * n_repeats + r], hit);
+}
+
+constexpr int IMP_WINDOW = HYPEL_FOREST_IMPORTANCE_WINDOW;
+
+__device__ __forceinline__ double node_impurity(const double* __restrict__ impurity, const double* __restrict__ value,
+                                                int C, int node) {
+#pragma clang fp contract(off)
+    if (impurity) return impurity[node];
+    const double* v = value + (int64_t)node * C;
+    double s = 0.0;
+    for (int k = 0; k < C; ++k) {
+        const double q = v[k] * v[k];
+        s = s + q;
+    }
+    return 1.0 - s;
+}
+
+__device__ __forceinline__ double impurity_decrease(double w, double i, double wl, double il, double wr, double ir) {
+#pragma clang fp contract(off)
+    const double a = w * i;
+    const double b = wl * il;
+    const double c = wr * ir;
+    const double d = a - b;
+    return d - c;
+}
+
+// One workgroup per (tree, window of IMP_WINDOW columns): tab[c] sums the decreases of the tree's inner nodes on column
+// c in ascending node order.  The nodes come in chunks of the block, thread k holding node base + k.  Within a chunk
+// the lowest thread that still holds a decrease for a column claims it (LDS atomicMin), adds, gives the column back
+// and retires; the others try again -- per column the additions happen in thread = node order, in at most THREADS
+// rounds per chunk (all of them on one column).  No floating-point atomic anywhere.
+__global__ __launch_bounds__(THREADS) void importance_raw_kernel(const int4* __restrict__ nodes, int n_nodes,
+                                                                 const int32_t* __restrict__ tree_off, int n_trees,
+                                                                 const double* __restrict__ value, int C,
+                                                                 const double* __restrict__ node_weight,
+                                                                 const double* __restrict__ impurity, int f, int windows,
+                                                                 double* __restrict__ per_tree) {
+#pragma clang fp contract(off)
+    __shared__ double tab[IMP_WINDOW];
+    __shared__ int claim[IMP_WINDOW];
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x / windows, c0 = (blockIdx.x - t * windows) * IMP_WINDOW;
+    const int width = min(IMP_WINDOW, f - c0);
+    const int first = min(max(tree_off[t], 0), n_nodes - 1);
+    const int end = t + 1 < n_trees ? min(max(tree_off[t + 1], first + 1), n_nodes) : n_nodes;
+    for (int c = tid; c < width; c += THREADS) {
+        tab[c] = 0.0;
+        claim[c] = INT_MAX;
+    }
+    __syncthreads();
+    for (int base = first; base < end; base += THREADS) {
+        const int j = base + tid;
+        int pending = 0, c = 0;
+        double d = 0.0;
+        if (j < end) {
+            const int4 rec = nodes[j];
+            // (children inside the node array by contract; a record that breaks it is passed over, never followed)
+            if (rec.z >= 0 && rec.w >= 0 && rec.z < n_nodes && rec.w < n_nodes && rec.x >= c0 && rec.x < c0 + width) {
+                pending = 1;
+                c = rec.x - c0;
+                d = impurity_decrease(node_weight[j], node_impurity(impurity, value, C, j), node_weight[rec.z],
+                                      node_impurity(impurity, value, C, rec.z), node_weight[rec.w],
+                                      node_impurity(impurity, value, C, rec.w));
+            }
+        }
+        do {
+            if (pending) atomicMin(&claim[c], tid);
+            __syncthreads();
+            const bool mine = pending && claim[c] == tid;
+            __syncthreads();  // every claim is read before its holder gives it back
+            if (mine) {
+                tab[c] = tab[c] + d;
+                claim[c] = INT_MAX;
+                pending = 0;
+            }
+        } while (__syncthreads_or(pending));
+    }
+    const double w0 = node_weight[first];
+    for (int c = tid; c < width; c += THREADS) per_tree[(int64_t)t * f + c0 + c] = tab[c] / w0;
+}
+
+// rows[r][0 .. f) divided by its sum where that is > 0; the sum runs over the columns in ascending order from 0.0: the
+// block stages THREADS values at a time, thread 0 adds them one after the other
+__global__ __launch_bounds__(THREADS) void normalise_rows_kernel(double* __restrict__ rows, int f) {
+#pragma clang fp contract(off)
+    __shared__ double stage[THREADS];
+    __shared__ double total;
+    const int tid = threadIdx.x;
+    double* row = rows + (int64_t)blockIdx.x * f;
+    double s = 0.0;
+    for (int base = 0; base < f; base += THREADS) {
+        if (base + tid < f) stage[tid] = row[base + tid];
+        __syncthreads();
+        if (tid == 0) {
+            const int m = min(THREADS, f - base);
+            for (int k = 0; k < m; ++k) s = s + stage[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) total = s;
+    __syncthreads();
+    const double all = total;
+    if (all > 0.0)
+        for (int c = tid; c < f; c += THREADS) row[c] = row[c] / all;
+}
+
+// importances[c] = (the rows of the trees with more than one node, added in tree order from 0.0) / their number
+__global__ __launch_bounds__(THREADS) void importance_mean_kernel(const double* __restrict__ per_tree,
+                                                                  const int32_t* __restrict__ tree_off, int n_trees,
+                                                                  int n_nodes, int f, double* __restrict__ importances,
+                                                                  int32_t* __restrict__ n_used) {
+#pragma clang fp contract(off)
+    __shared__ int wcount[WAVES];
+    const int tid = threadIdx.x;
+    auto size = [&](int t) { return (t + 1 < n_trees ? tree_off[t + 1] : n_nodes) - tree_off[t]; };
+    int mine = 0;
+    for (int t = tid; t < n_trees; t += THREADS) mine += size(t) > 1;
+    mine = wave_sum(mine);
+    if ((tid & 63) == 0) wcount[tid >> 6] = mine;
+    __syncthreads();
+    int used = 0;
+    for (int k = 0; k < WAVES; ++k) used += wcount[k];
+    const int c = blockIdx.x * THREADS + tid;
+    if (c < f) {
+        double s = 0.0;
+        for (int t = 0; t < n_trees; ++t)
+            if (size(t) > 1) s = s + per_tree[(int64_t)t * f + c];
+        importances[c] = used > 0 ? s / (double)used : 0.0;
+    }
+    if (blockIdx.x == 0 && tid == 0) n_used[0] = used;
 }
 
 }  // namespace
@@ -732,5 +936,71 @@ extern "C" int hypel_forest_predict_scene(const float* casi, const float* lidar,
                        (size_t)n_classes * PRED_LANES * sizeof(double), ST, casi, cl ? lidar : nullptr,
                        wp, cc, cl, points, n, m, class_labels, out, raster_w);
     HYPEL_CHECK_LAUNCH("hypel_forest_predict_scene");
+    return 0;
+}
+
+extern "C" int hypel_forest_oob_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off,
+                                     int32_t n_trees, const hypel_forest_node_t* nodes, int32_t n_nodes,
+                                     const double* leaf_value, int32_t n_leaves, int32_t n_classes,
+                                     const uint8_t* class_labels, const int32_t* weight, int64_t ldw, uint8_t* out,
+                                     double* proba, int32_t* votes, hypel_stream_t stream) {
+    Model m;
+    if (forest_model("hypel_forest_oob_rows", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes))
+        return -1;
+    HYPEL_REQUIRE(x && weight && out && proba && votes, "hypel_forest_oob_rows");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && ldw >= n, "hypel_forest_oob_rows");
+    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
+    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_oob_rows");
+    hipLaunchKernelGGL(oob_rows_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
+                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, m, class_labels, weight, ldw, out,
+                       proba, votes);
+    HYPEL_CHECK_LAUNCH("hypel_forest_oob_rows");
+    return 0;
+}
+
+extern "C" int hypel_forest_permuted_hits(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off,
+                                          int32_t n_trees, const hypel_forest_node_t* nodes, int32_t n_nodes,
+                                          const double* leaf_value, int32_t n_leaves, int32_t n_classes,
+                                          const int32_t* y, const int32_t* partner, int32_t n_repeats,
+                                          int32_t group_mod, int32_t g0, int32_t n_groups, int32_t* hits,
+                                          hypel_stream_t stream) {
+    Model m;
+    if (forest_model("hypel_forest_permuted_hits", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves,
+                     n_classes))
+        return -1;
+    HYPEL_REQUIRE(x && y && partner && hits, "hypel_forest_permuted_hits");
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && n_repeats >= 1, "hypel_forest_permuted_hits");
+    HYPEL_REQUIRE(group_mod >= 1 && g0 >= 0 && n_groups >= 1 && (int64_t)g0 + n_groups <= group_mod,
+                  "hypel_forest_permuted_hits");
+    const int64_t row_blocks = (n + PRED_LANES - 1) / PRED_LANES;
+    // (three factors below 2^31 each: the product of the first two fits, the division never overflows)
+    HYPEL_REQUIRE((int64_t)n_groups * n_repeats <= (((int64_t)1 << 31) - 1) / row_blocks,
+                  "hypel_forest_permuted_hits: more than 2^31 - 1 blocks, launch fewer groups at a time");
+    hipLaunchKernelGGL(permuted_hits_kernel, dim3((unsigned)((int64_t)n_groups * n_repeats * row_blocks)),
+                       dim3(PRED_LANES), (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, row_blocks, m, y,
+                       partner, n_repeats, group_mod, g0, hits);
+    HYPEL_CHECK_LAUNCH("hypel_forest_permuted_hits");
+    return 0;
+}
+
+extern "C" int hypel_forest_importances_f64(const hypel_forest_node_t* nodes, int32_t n_nodes, const int32_t* tree_off,
+                                            int32_t n_trees, const double* value, int32_t n_classes,
+                                            const double* node_weight, const double* impurity, int32_t f,
+                                            double* per_tree, double* importances, int32_t* n_used,
+                                            hypel_stream_t stream) {
+    HYPEL_REQUIRE(nodes && tree_off && node_weight && per_tree && importances && n_used, "hypel_forest_importances_f64");
+    HYPEL_REQUIRE(((uintptr_t)nodes & (sizeof(int4) - 1)) == 0, "hypel_forest_importances_f64");
+    HYPEL_REQUIRE(n_trees > 0 && n_nodes >= n_trees && f > 0, "hypel_forest_importances_f64");
+    HYPEL_REQUIRE(impurity || (value && n_classes >= 1 && n_classes <= MAXC), "hypel_forest_importances_f64");
+    const int windows = (f + IMP_WINDOW - 1) / IMP_WINDOW;
+    HYPEL_REQUIRE((int64_t)n_trees * windows < ((int64_t)1 << 31), "hypel_forest_importances_f64");
+    hipLaunchKernelGGL(importance_raw_kernel, dim3((unsigned)((int64_t)n_trees * windows)), dim3(THREADS), 0, ST,
+                       reinterpret_cast<const int4*>(nodes), n_nodes, tree_off, n_trees, value, n_classes, node_weight,
+                       impurity, f, windows, per_tree);
+    hipLaunchKernelGGL(normalise_rows_kernel, dim3(n_trees), dim3(THREADS), 0, ST, per_tree, f);
+    hipLaunchKernelGGL(importance_mean_kernel, dim3((f + THREADS - 1) / THREADS), dim3(THREADS), 0, ST, per_tree, tree_off,
+                       n_trees, n_nodes, f, importances, n_used);
+    hipLaunchKernelGGL(normalise_rows_kernel, dim3(1), dim3(THREADS), 0, ST, importances, f);
+    HYPEL_CHECK_LAUNCH("hypel_forest_importances_f64");
     return 0;
 }

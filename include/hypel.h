@@ -994,8 +994,42 @@ int hypel_tensor_summary_f32(const float* base, const int64_t* table, int32_t n_
  *   patch: the feature field of scene_nodes[node] is 2 * e + a where a = 1 reads lidar and 0 casi, and e is the
  *   element offset from the window origin's pixel in that array -- (py * wp + px) * cc + ch for patch feature (py * p + px) * (cc + cl) + ch,
  *   ch < cc; (py * wp + px) * cl + ch - cc otherwise -- translated once when the model is uploaded.  The label goes
- *   to out[y * raster_w + x]. */
+ *   to out[y * raster_w + x].
+ * Diagnostics of a served model (scikit-learn's oob_decision_function_ / oob_score_, feature_importances_ and a grouped
+ *   permutation importance).  The model arguments, the walk, the fp64 sum in tree order and the first maximum are those
+ *   of hypel_forest_predict_rows; nothing below uses a floating-point atomic, so two runs write identical bytes.
+ * hypel_forest_oob_rows: weight is an int32 table [n_trees][ldw] of bootstrap counts, ldw >= n.  Tree t does NOT vote
+ *   for row i where weight[t * ldw + i] > 0.  votes[i] = the number of trees that vote; the leaf rows of the voting
+ *   trees are summed in tree order in fp64 from 0.0 and each sum is divided once by (double)votes[i] into proba
+ *   [n][n_classes]; out[i] = class_labels[first maximum] (NULL: the index).  A row no tree votes for has votes 0, a
+ *   proba row of zeros and class index 0.  out, proba and votes are all required.  Rows are served in chunks by
+ *   offsetting x, weight, proba, votes and out by the chunk's first row; ldw stays the table's row length.
+ * hypel_forest_permuted_hits: column c belongs to group c % group_mod (group_mod >= 1; group_mod = f: every column its
+ *   own group).  For every group g of [g0, g0 + n_groups) (inside [0, group_mod)), every repeat r < n_repeats and every
+ *   row i, the walk reads x[partner[r * n + i]][c] for the columns c of group g and x[i][c] for the others; partner is
+ *   int32 [n_repeats][n], each row a permutation of 0 .. n - 1.  Where the winner's class INDEX equals y[i] (int32 [n]),
+ *   hits[(g - g0) * n_repeats + r] is incremented (integer atomics): the caller zeroes hits [n_groups][n_repeats], the
+ *   launch adds to what it holds.  The grid is n_groups * n_repeats * ceil(n / 64) blocks; more than 2^31 - 1 are refused
+ *   with a message that says so (launch fewer groups at a time).
+ * hypel_forest_importances_f64: mean decrease in impurity.  nodes as for serving (children absolute, left < 0: a leaf),
+ *   tree t owning the nodes tree_off[t] .. tree_off[t + 1] (n_nodes for the last tree), its root first; node_weight fp64
+ *   [n_nodes] (the root's > 0); impurity fp64 [n_nodes], or NULL for Gini from value fp64 [n_nodes][n_classes] (every
+ *   node's class fractions, not the leaf table): s = 0.0, s = s + v_k * v_k for k = 0 .. n_classes - 1 (product and
+ *   addition rounded once each), impurity = 1.0 - s.  value and n_classes are read only when impurity is NULL.
+ *   For an inner node j with children l, r: d = ((w_j * imp_j) - (w_l * imp_l)) - (w_r * imp_r), the three products and
+ *   the two subtractions rounded once each, in this order.  raw[t][c] = the d of tree t's inner nodes with feature c,
+ *   added one by one in ascending node order from 0.0.  Then, every step one rounding per element: raw[t][c] /= the
+ *   weight of t's root; S_t = the sum of raw[t][0 .. f) in ascending column order from 0.0, and where S_t > 0,
+ *   raw[t][c] /= S_t: that is per_tree [n_trees][f] (a lone root's row is zeros).  n_used[0] = the number of trees with
+ *   more than one node.  importances[c] = (per_tree[t][c] of those trees, added in tree order from 0.0) / (double)n_used,
+ *   then S = the sum of importances[0 .. f) in ascending column order from 0.0 and, where S > 0, importances[c] /= S.
+ *   n_used = 0: importances is zeros.  (scikit-learn's arithmetic but for the two normalising sums, which numpy adds
+ *   pairwise.)  The per-column sum runs in one workgroup per (tree, window of HYPEL_FOREST_IMPORTANCE_WINDOW columns)
+ *   with an fp64 table and an int32 claim table in LDS: of a chunk of nodes, the lowest thread = node holding a decrease
+ *   for a column claims the column, adds and retires, the others try again.  Like the serving kernels it does not
+ *   validate the model. */
 #define HYPEL_FOREST_EDGE_ROWS 16384
+#define HYPEL_FOREST_IMPORTANCE_WINDOW 4096
 #define HYPEL_FOREST_MAX_EDGES 255
 #define HYPEL_FOREST_MAX_CLASSES 32
 #define HYPEL_FOREST_MAX_DEPTH 64
@@ -1039,6 +1073,19 @@ int hypel_forest_predict_scene(const float* casi, const float* lidar, int64_t hp
                                const hypel_forest_node_t* scene_nodes, int32_t n_nodes, const double* leaf_value,
                                int32_t n_leaves, int32_t n_classes, const uint8_t* class_labels, uint8_t* out,
                                int64_t raster_w, hypel_stream_t stream);
+int hypel_forest_oob_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off, int32_t n_trees,
+                          const hypel_forest_node_t* nodes, int32_t n_nodes, const double* leaf_value, int32_t n_leaves,
+                          int32_t n_classes, const uint8_t* class_labels, const int32_t* weight, int64_t ldw,
+                          uint8_t* out, double* proba, int32_t* votes, hypel_stream_t stream);
+int hypel_forest_permuted_hits(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off,
+                               int32_t n_trees, const hypel_forest_node_t* nodes, int32_t n_nodes,
+                               const double* leaf_value, int32_t n_leaves, int32_t n_classes, const int32_t* y,
+                               const int32_t* partner, int32_t n_repeats, int32_t group_mod, int32_t g0,
+                               int32_t n_groups, int32_t* hits, hypel_stream_t stream);
+int hypel_forest_importances_f64(const hypel_forest_node_t* nodes, int32_t n_nodes, const int32_t* tree_off,
+                                 int32_t n_trees, const double* value, int32_t n_classes, const double* node_weight,
+                                 const double* impurity, int32_t f, double* per_tree, double* importances,
+                                 int32_t* n_used, hypel_stream_t stream);
 
 /* ---- template matching (utilities/lidar_matcher.py: cv2.resize INTER_AREA by an integer factor, cv2.matchTemplate
  * TM_CCORR_NORMED, cv2.minMaxLoc's max_loc; csrc/match.hip) ------------------------------------------------------------

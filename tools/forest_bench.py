@@ -11,8 +11,13 @@ ExtraTreesClassifier for scale) and adds `fit_levels`: per level the event times
 hypel_forest_split_apply_thr beside the records, the rows they cover and the byte floor of the search -- per record its
 rows of one xt column twice (the range, then the counts) plus order, y and weight once, 20 bytes a row, at 6.2 TB/s.
 
+--diagnostics R replaces the scene part by the forest diagnostics on the same problem: the per-launch event times of
+hypel_forest_oob_rows, hypel_forest_importances_f64 and hypel_forest_permuted_hits (one group per band, R repeats), the
+wall times of the three methods, and scikit-learn's oob_score=True and sklearn.inspection.permutation_importance at
+n_jobs=16 for orientation.
+
     python tools/forest_bench.py [--estimator forest] [--path grss2013] [--trees 50] [--max_features 24]
-                                 [--scene_h 349] [--scene_w 1905]"""
+                                 [--scene_h 349] [--scene_w 1905] [--diagnostics 5]"""
 import argparse
 import json
 import os
@@ -86,8 +91,56 @@ def timed(fn, repeats=3):
     return best
 
 
+def diagnostics(args, model, log, hip, train, validation, channels, result):
+    """--diagnostics R: per-launch event times of hypel_forest_oob_rows (training rows), hypel_forest_importances_f64 and
+    hypel_forest_permuted_hits (validation rows, one group per band, R repeats); for orientation only, scikit-learn's
+    extra cost of oob_score=True at fit and sklearn.inspection.permutation_importance (per COLUMN, its own stream) at
+    n_jobs=16."""
+    (X, y), (Xv, yv) = train, validation
+    del log.log[:]
+    model._be = log
+    oob = model.out_of_bag(X, y)
+    model.feature_importances()
+    model.permutation_importance(Xv, yv, n_repeats=args.diagnostics, group_mod=channels, seed=0)
+    model._be = hip
+    wall = {"out_of_bag_s": timed(lambda: model.out_of_bag(X, y)), "feature_importances_s": timed(model.feature_importances),
+            "permutation_importance_s": timed(lambda: model.permutation_importance(
+                Xv, yv, n_repeats=args.diagnostics, group_mod=channels, seed=0), repeats=1)}
+    result["diagnostics"] = {"launches": table(log.log), "wall": {k: round(v, 5) for k, v in wall.items()},
+                             "oob_score": oob, "oob_rows_without_vote": int((model.oob_votes_ == 0).sum()),
+                             "n_used": model.importances_n_used_, "train_rows": int(len(X)),
+                             "validation_rows": int(len(Xv)), "groups": int(channels), "repeats": args.diagnostics}
+    if not args.sklearn:
+        return
+    try:
+        from sklearn.ensemble import ExtraTreesClassifier, RandomForestClassifier
+        from sklearn.inspection import permutation_importance
+    except ImportError:
+        return
+    cls = ExtraTreesClassifier if args.estimator == "extra_trees" else RandomForestClassifier
+    fits = {}
+    for oob_score in (False, True):
+        t0 = time.perf_counter()
+        sk = cls(args.trees, max_features=min(args.max_features, X.shape[1]), n_jobs=16, bootstrap=True,
+                 oob_score=oob_score, random_state=0).fit(X, y)
+        fits[oob_score] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sk.feature_importances_
+    t1 = time.perf_counter()
+    sk.set_params(n_jobs=1)  # (the columns are the parallel axis below)
+    permutation_importance(sk, Xv, yv, n_repeats=args.diagnostics, n_jobs=16, random_state=0)
+    t2 = time.perf_counter()
+    result["diagnostics"]["sklearn_cpu"] = {"fit_s": round(fits[False], 3), "fit_oob_score_s": round(fits[True], 3),
+                                            "oob_score": float(sk.oob_score_), "feature_importances_s": round(t1 - t0, 4),
+                                            "permutation_importance_s": round(t2 - t1, 2),
+                                            "permutation_columns": int(X.shape[1])}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--diagnostics", type=int, default=0,
+                    help="R > 0: instead of the scene, the forest diagnostics (out-of-bag, importances, R permutation "
+                         "repeats per band) launch by launch; extra_trees is then grown with bootstrap")
     ap.add_argument("--estimator", default="forest", choices=("forest", "extra_trees"))
     ap.add_argument("--path", default="grss2013")
     ap.add_argument("--trees", type=int, default=50)
@@ -107,6 +160,8 @@ def main():
     Xv, yv = va.data.reshape(len(va.data), -1), va.labels
     hip = HipBackend()
     kw = dict(n_estimators=args.trees, max_features=args.max_features)
+    if args.diagnostics:
+        kw["bootstrap"] = True
     result = {"tool": "forest_bench", "config": {"estimator": args.estimator, "path": args.path, **kw},
               "train_rows": int(len(X)), "features": int(X.shape[1])}
     extra = args.estimator == "extra_trees"
@@ -134,6 +189,10 @@ def main():
     if extra:
         result["fit_levels"] = level_table(log.log, level_rows, model._resolve_max_features(X.shape[1]))
     result["fit_launch_sum_s"] = round(sum(us for _, us in log.log) * 1e-6, 4)
+    if args.diagnostics:
+        diagnostics(args, model, log, hip, (X, y), (Xv, yv), tr.data.shape[3], result)
+        print(json.dumps(result))
+        return
 
     # whole-scene serving on a scene of the real size (the model's features are the same window of the same bands)
     big = f"{args.path}:h={args.scene_h}:w={args.scene_w}"
