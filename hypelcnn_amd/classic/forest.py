@@ -310,22 +310,29 @@ class ForestClassifier:
             return max(1, min(int(self.chunk_rows), n))
         return max(1, min(n, (1 << 28) // (4 * self.n_features_in_)))
 
+    def _chunks(self, n, produce):
+        """The chunked serving loop: yields (r0, x, m, f), where x, m, f = produce(r0, r1) are a chunk's rows on the
+        device, their number and their feature count; synchronises after each chunk (x dies there)."""
+        step = self._chunk(n)
+        for r0 in range(0, n, step):
+            yield (r0, *produce(r0, min(n, r0 + step)))
+            self._be.synchronize()
+
+    def _check_features(self, got, where):
+        if got != self.n_features_in_:
+            raise ValueError(f"{where}: X has {got} features, the model was fitted on {self.n_features_in_}")
+
     def _run(self, X, want_proba):
         be = self._backend()
         self._fitted()
         n = X.shape[0]
-        if X.shape[1] != self.n_features_in_:
-            raise ValueError(f"ForestClassifier: X has {X.shape[1]} features, the model was fitted on {self.n_features_in_}")
+        self._check_features(X.shape[1], "ForestClassifier")
         n_cls = len(self.classes_)
         idx = be.zeros(_round_up(n, 4), torch.uint8)
         proba = be.zeros(n * n_cls, torch.float64) if want_proba else None
-        step = self._chunk(n)
-        for r0 in range(0, n, step):
-            r1 = min(n, r0 + step)
-            x, m, f = self._rows(X[r0:r1])
+        for r0, x, m, f in self._chunks(n, lambda r0, r1: self._rows(X[r0:r1])):
             be.call("forest_predict_rows", Ref(x), f, m, f, *self._model_args(self._dev["nodes"]), None, None,
                     Ref(idx, r0), 0, None if proba is None else Ref(proba, r0 * n_cls))
-            be.synchronize()  # x dies here
         return idx.cpu().numpy()[:n], None if proba is None else proba.cpu().numpy().reshape(n, n_cls)
 
     def predict(self, X):
@@ -359,9 +366,7 @@ class ForestClassifier:
             raise ValueError(f"{self._name}.out_of_bag: a model from from_arrays has no bootstrap_counts_: pass "
                              f"in_bag_counts [n_trees, n]")
         n, n_cls, n_trees = X.shape[0], len(self.classes_), self.n_estimators
-        if X.shape[1] != self.n_features_in_:
-            raise ValueError(f"{self._name}.out_of_bag: X has {X.shape[1]} features, the model was fitted on "
-                             f"{self.n_features_in_}")
+        self._check_features(X.shape[1], f"{self._name}.out_of_bag")
         if counts.shape != (n_trees, n):
             raise ValueError(f"{self._name}.out_of_bag: in-bag counts of shape {counts.shape}, X has {n} rows and the "
                              f"forest {n_trees} trees: out-of-bag rows are rows of the training matrix")
@@ -369,13 +374,9 @@ class ForestClassifier:
         w_d = be.upload(np.ascontiguousarray(counts, np.int32))
         idx, votes = be.zeros(_round_up(n, 4), torch.uint8), be.zeros(n, torch.int32)
         proba = be.zeros(n * n_cls, torch.float64)
-        step = self._chunk(n)
-        for r0 in range(0, n, step):
-            r1 = min(n, r0 + step)
-            x, m, f = self._rows(X[r0:r1])
+        for r0, x, m, f in self._chunks(n, lambda r0, r1: self._rows(X[r0:r1])):
             be.call("forest_oob_rows", Ref(x), f, m, f, *self._model_args(self._dev["nodes"]), None, Ref(w_d, r0), n,
                     Ref(idx, r0), Ref(proba, r0 * n_cls), Ref(votes, r0))
-            be.synchronize()  # x dies here
         self.oob_decision_function_ = proba.cpu().numpy().reshape(n, n_cls)
         self.oob_votes_ = votes.cpu().numpy()
         self.oob_score_ = float(np.mean(self.classes_[idx.cpu().numpy()[:n]] == y))
@@ -423,9 +424,7 @@ class ForestClassifier:
         be = self._backend()
         self._fitted()
         x, n, f = self._rows(X)
-        if f != self.n_features_in_:
-            raise ValueError(f"{self._name}.permutation_importance: X has {f} features, the model was fitted on "
-                             f"{self.n_features_in_}")
+        self._check_features(f, f"{self._name}.permutation_importance")
         group_mod = f if group_mod is None else int(group_mod)
         n_repeats = int(n_repeats)
         if group_mod < 1 or n_repeats < 1:
@@ -481,14 +480,12 @@ class ForestClassifier:
                     Ref(raster), int(raster_w))
             be.synchronize()
             return
-        step = self._chunk(n)
-        for r0 in range(0, n, step):
-            r1 = min(n, r0 + step)
-            patches, pts = arrays.gather(torch.arange(r0, r1, device=be.device))
-            f = self.n_features_in_
-            be.call("forest_predict_rows", Ref(patches.reshape(-1)), f, r1 - r0, f, *self._model_args(self._dev["nodes"]),
+
+        def gathered(r0, r1):
+            return arrays.gather(torch.arange(r0, r1, device=be.device)), r1 - r0, self.n_features_in_
+        for _, (patches, pts), m, f in self._chunks(n, gathered):
+            be.call("forest_predict_rows", Ref(patches.reshape(-1)), f, m, f, *self._model_args(self._dev["nodes"]),
                     Ref(self._labels_u8), Ref(pts.reshape(-1)), Ref(raster), int(raster_w), None)
-            be.synchronize()  # the patches die here
 
 
 class ExtraTreesForest(ForestClassifier):

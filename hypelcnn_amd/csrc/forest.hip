@@ -776,19 +776,49 @@ extern "C" int hypel_forest_bin_u8(const float* x, int64_t ld, int64_t n, int32_
     return 0;
 }
 
+// the checks the four growth entry points share (a record is an (active node, candidate slot) pair)
+static int forest_growth_args(const char* name, int64_t n, int64_t ldn, int32_t n_active, int32_t f, int32_t n_classes,
+                              int32_t max_features) {
+    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, name);
+    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, name);
+    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, name);
+    HYPEL_REQUIRE((int64_t)n_active * max_features < ((int64_t)1 << 31), name);
+    return 0;
+}
+
 extern "C" int hypel_forest_split_hist(const uint8_t* bins, int64_t ldn, const int32_t* y, const int32_t* weight,
                                        int64_t n, int32_t n_classes, const int32_t* order, const int32_t* active,
                                        int32_t n_active, const int32_t* cand, int32_t max_features, int32_t f,
                                        double* score, int32_t* best_bin, int32_t* valid, hypel_stream_t stream) {
     HYPEL_REQUIRE(bins && y && weight && order && active && cand && score && best_bin && valid,
                   "hypel_forest_split_hist");
-    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_hist");
-    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_hist");
-    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_hist");
-    HYPEL_REQUIRE((int64_t)n_active * max_features < ((int64_t)1 << 31), "hypel_forest_split_hist");
+    if (forest_growth_args("hypel_forest_split_hist", n, ldn, n_active, f, n_classes, max_features)) return -1;
     hipLaunchKernelGGL(split_hist_kernel, dim3((unsigned)((int64_t)n_active * max_features)), dim3(THREADS), 0, ST, bins,
                        ldn, y, weight, n, n_classes, order, active, cand, max_features, score, best_bin, valid);
     HYPEL_CHECK_LAUNCH("hypel_forest_split_hist");
+    return 0;
+}
+
+// One level's apply for either search; `side` is its side test, built and checked by the caller.
+template <class Side>
+static int forest_split_apply(const char* name, const Side& side, const int32_t* y, const int32_t* weight, int64_t n,
+                              int64_t ldn, int32_t n_classes, const int32_t* order_in, int32_t* order_out,
+                              const int32_t* active, int32_t n_active, const int32_t* cand, int32_t max_features,
+                              int32_t f, const double* score, const int32_t* valid, int32_t level, int32_t max_depth,
+                              int32_t node_base, int32_t node_capacity, const NodeOut& o, int32_t* split_ws,
+                              int32_t* next_active, int32_t* counter, hypel_stream_t stream) {
+    HYPEL_REQUIRE(y && weight && order_in && order_out && order_in != order_out && active && cand && score, name);
+    HYPEL_REQUIRE(valid && o.feature && o.thr_bin && o.threshold && o.left && o.right && o.node_tree, name);
+    HYPEL_REQUIRE(o.node_count && o.node_weight && o.value && split_ws && next_active && counter, name);
+    if (forest_growth_args(name, n, ldn, n_active, f, n_classes, max_features)) return -1;
+    HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, name);
+    HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, name);
+    hipLaunchKernelGGL(split_apply_kernel<Side>, dim3(n_active), dim3(THREADS), 0, ST, side, y, weight, n, n_classes,
+                       order_in, order_out, active, cand, max_features, score, valid, (int)(level >= max_depth), o,
+                       split_ws);
+    hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
+                       node_capacity, o.left, o.right, next_active, counter);
+    HYPEL_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -801,26 +831,12 @@ extern "C" int hypel_forest_split_apply(const uint8_t* bins, int64_t ldn, const 
                                         float* threshold, int32_t* left, int32_t* right, int32_t* node_tree,
                                         int32_t* node_count, int32_t* node_weight, double* value, int32_t* split_ws,
                                         int32_t* next_active, int32_t* counter, hypel_stream_t stream) {
-    HYPEL_REQUIRE(bins && y && weight && order_in && order_out && order_in != order_out && active && cand,
-                  "hypel_forest_split_apply");
-    HYPEL_REQUIRE(score && best_bin && valid && edges && feature && thr_bin && threshold && left && right,
-                  "hypel_forest_split_apply");
-    HYPEL_REQUIRE(node_tree && node_count && node_weight && value && split_ws && next_active && counter,
-                  "hypel_forest_split_apply");
-    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_apply");
-    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_apply");
-    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_apply");
-    HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, "hypel_forest_split_apply");
-    HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, "hypel_forest_split_apply");
-    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    HYPEL_REQUIRE(bins && best_bin && edges, "hypel_forest_split_apply");
     const BinSide side = {bins, ldn, best_bin, edges, nullptr, 0, 0};
-    hipLaunchKernelGGL(split_apply_kernel<BinSide>, dim3(n_active), dim3(THREADS), 0, ST, side, y, weight, n, n_classes,
-                       order_in, order_out, active, cand, max_features, score, valid, (int)(level >= max_depth), o,
-                       split_ws);
-    hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
-                       node_capacity, left, right, next_active, counter);
-    HYPEL_CHECK_LAUNCH("hypel_forest_split_apply");
-    return 0;
+    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    return forest_split_apply("hypel_forest_split_apply", side, y, weight, n, ldn, n_classes, order_in, order_out, active,
+                              n_active, cand, max_features, f, score, valid, level, max_depth, node_base, node_capacity,
+                              o, split_ws, next_active, counter, stream);
 }
 
 extern "C" int hypel_forest_columns_f32(const float* x, int64_t ld, int64_t n, int32_t f, float* xt, int64_t ldn,
@@ -841,11 +857,8 @@ extern "C" int hypel_forest_split_random(const float* xt, int64_t ldn, const int
                                          int32_t f, double* score, float* thr, int32_t* valid, hypel_stream_t stream) {
     HYPEL_REQUIRE(xt && y && weight && order && active && cand && u && score && thr && valid,
                   "hypel_forest_split_random");
-    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_random");
-    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_random");
-    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_random");
+    if (forest_growth_args("hypel_forest_split_random", n, ldn, n_active, f, n_classes, max_features)) return -1;
     const int64_t n_records = (int64_t)n_active * max_features;
-    HYPEL_REQUIRE(n_records < ((int64_t)1 << 31), "hypel_forest_split_random");
     hipLaunchKernelGGL(split_random_kernel, dim3((unsigned)((n_records + WAVES - 1) / WAVES)), dim3(THREADS), 0, ST, xt,
                        ldn, y, weight, n, n_classes, order, active, cand, u, max_features, n_records, score, thr, valid);
     HYPEL_CHECK_LAUNCH("hypel_forest_split_random");
@@ -861,26 +874,12 @@ extern "C" int hypel_forest_split_apply_thr(const float* xt, int64_t ldn, const 
                                             int32_t* left, int32_t* right, int32_t* node_tree, int32_t* node_count,
                                             int32_t* node_weight, double* value, int32_t* split_ws, int32_t* next_active,
                                             int32_t* counter, hypel_stream_t stream) {
-    HYPEL_REQUIRE(xt && y && weight && order_in && order_out && order_in != order_out && active && cand,
-                  "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(score && thr && valid && feature && thr_bin && threshold && left && right,
-                  "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(node_tree && node_count && node_weight && value && split_ws && next_active && counter,
-                  "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(n > 0 && ldn >= n && n < ((int64_t)1 << 31) && n_active > 0 && f > 0, "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(n_classes >= 1 && n_classes <= MAXC, "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(max_features >= 1 && max_features <= f, "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(level >= 0 && max_depth >= 0 && max_depth <= HYPEL_FOREST_MAX_DEPTH, "hypel_forest_split_apply_thr");
-    HYPEL_REQUIRE(node_base >= 0 && node_capacity >= node_base, "hypel_forest_split_apply_thr");
-    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    HYPEL_REQUIRE(xt && thr, "hypel_forest_split_apply_thr");
     const ThrSide side = {xt, ldn, thr, nullptr, 0.0f};
-    hipLaunchKernelGGL(split_apply_kernel<ThrSide>, dim3(n_active), dim3(THREADS), 0, ST, side, y, weight, n, n_classes,
-                       order_in, order_out, active, cand, max_features, score, valid, (int)(level >= max_depth), o,
-                       split_ws);
-    hipLaunchKernelGGL(level_compact_kernel, dim3(1), dim3(THREADS), 0, ST, active, n_active, split_ws, node_base,
-                       node_capacity, left, right, next_active, counter);
-    HYPEL_CHECK_LAUNCH("hypel_forest_split_apply_thr");
-    return 0;
+    const NodeOut o = {feature, thr_bin, left, right, node_tree, node_count, node_weight, threshold, value};
+    return forest_split_apply("hypel_forest_split_apply_thr", side, y, weight, n, ldn, n_classes, order_in, order_out,
+                              active, n_active, cand, max_features, f, score, valid, level, max_depth, node_base,
+                              node_capacity, o, split_ws, next_active, counter, stream);
 }
 
 static int forest_model(const char* name, Model* m, const int32_t* tree_off, int32_t n_trees,
@@ -894,23 +893,36 @@ static int forest_model(const char* name, Model* m, const int32_t* tree_off, int
     return 0;
 }
 
+// A walking launch: the model (forest_model) and the grid (forest_walk_grid) of `per_row_block` blocks per 64 rows, one
+// lane a row: the block count, refused from 2^31 on (n > 0 is the caller's check), and the LDS of the class sums.
+struct Walk {
+    Model m;
+    int64_t row_blocks;
+    unsigned blocks;
+    size_t lds;
+};
+static int forest_walk_grid(const char* name, Walk* w, int64_t n, int64_t per_row_block) {
+    w->row_blocks = (n + PRED_LANES - 1) / PRED_LANES;
+    HYPEL_REQUIRE(per_row_block <= INT32_MAX / w->row_blocks && "2^31 - 1 blocks at most: launch fewer groups", name);
+    w->blocks = (unsigned)(per_row_block * w->row_blocks);
+    w->lds = (size_t)w->m.n_classes * PRED_LANES * sizeof(double);
+    return 0;
+}
+
 extern "C" int hypel_forest_predict_rows(const float* x, int64_t ld, int64_t n, int32_t f, const int32_t* tree_off,
                                          int32_t n_trees, const hypel_forest_node_t* nodes, int32_t n_nodes,
                                          const double* leaf_value, int32_t n_leaves, int32_t n_classes,
                                          const uint8_t* class_labels, const int32_t* points, uint8_t* out,
                                          int64_t raster_w, double* proba, hypel_stream_t stream) {
-    Model m;
-    if (forest_model("hypel_forest_predict_rows", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves,
-                     n_classes))
-        return -1;
-    HYPEL_REQUIRE(x && out, "hypel_forest_predict_rows");
-    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && (!points || raster_w > 0), "hypel_forest_predict_rows");
-    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
-    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_predict_rows");
-    hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
-                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, m, class_labels,
+    const char* name = "hypel_forest_predict_rows";
+    Walk w;
+    if (forest_model(name, &w.m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes)) return -1;
+    HYPEL_REQUIRE(x && out, name);
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && (!points || raster_w > 0), name);
+    if (forest_walk_grid(name, &w, n, 1)) return -1;
+    hipLaunchKernelGGL(predict_rows_kernel, dim3(w.blocks), dim3(PRED_LANES), w.lds, ST, x, ld, n, w.m, class_labels,
                        points, out, raster_w, proba);
-    HYPEL_CHECK_LAUNCH("hypel_forest_predict_rows");
+    HYPEL_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -921,21 +933,17 @@ extern "C" int hypel_forest_predict_scene(const float* casi, const float* lidar,
                                           const double* leaf_value, int32_t n_leaves, int32_t n_classes,
                                           const uint8_t* class_labels, uint8_t* out, int64_t raster_w,
                                           hypel_stream_t stream) {
-    Model m;
-    if (forest_model("hypel_forest_predict_scene", &m, tree_off, n_trees, scene_nodes, n_nodes, leaf_value, n_leaves,
-                     n_classes))
-        return -1;
-    HYPEL_REQUIRE(casi && points && out && (cl == 0 || lidar), "hypel_forest_predict_scene");
-    HYPEL_REQUIRE(n > 0 && p > 0 && hp >= p && wp >= p && cc > 0 && cl >= 0 && raster_w > 0,
-                  "hypel_forest_predict_scene");
+    const char* name = "hypel_forest_predict_scene";
+    Walk w;
+    if (forest_model(name, &w.m, tree_off, n_trees, scene_nodes, n_nodes, leaf_value, n_leaves, n_classes)) return -1;
+    HYPEL_REQUIRE(casi && points && out && (cl == 0 || lidar), name);
+    HYPEL_REQUIRE(n > 0 && p > 0 && hp >= p && wp >= p && cc > 0 && cl >= 0 && raster_w > 0, name);
     // the largest element offset a translated feature can carry must fit the int32 it is packed into
-    HYPEL_REQUIRE(((int64_t)(p - 1) * wp + p) * (cc > cl ? cc : cl) < ((int64_t)1 << 30), "hypel_forest_predict_scene");
-    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
-    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_predict_scene");
-    hipLaunchKernelGGL(predict_scene_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
-                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, casi, cl ? lidar : nullptr,
-                       wp, cc, cl, points, n, m, class_labels, out, raster_w);
-    HYPEL_CHECK_LAUNCH("hypel_forest_predict_scene");
+    HYPEL_REQUIRE(((int64_t)(p - 1) * wp + p) * (cc > cl ? cc : cl) < ((int64_t)1 << 30), name);
+    if (forest_walk_grid(name, &w, n, 1)) return -1;
+    hipLaunchKernelGGL(predict_scene_kernel, dim3(w.blocks), dim3(PRED_LANES), w.lds, ST, casi, cl ? lidar : nullptr, wp,
+                       cc, cl, points, n, w.m, class_labels, out, raster_w);
+    HYPEL_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -944,17 +952,15 @@ extern "C" int hypel_forest_oob_rows(const float* x, int64_t ld, int64_t n, int3
                                      const double* leaf_value, int32_t n_leaves, int32_t n_classes,
                                      const uint8_t* class_labels, const int32_t* weight, int64_t ldw, uint8_t* out,
                                      double* proba, int32_t* votes, hypel_stream_t stream) {
-    Model m;
-    if (forest_model("hypel_forest_oob_rows", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes))
-        return -1;
-    HYPEL_REQUIRE(x && weight && out && proba && votes, "hypel_forest_oob_rows");
-    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && ldw >= n, "hypel_forest_oob_rows");
-    const int64_t blocks = (n + PRED_LANES - 1) / PRED_LANES;
-    HYPEL_REQUIRE(blocks < ((int64_t)1 << 31), "hypel_forest_oob_rows");
-    hipLaunchKernelGGL(oob_rows_kernel, dim3((unsigned)blocks), dim3(PRED_LANES),
-                       (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, m, class_labels, weight, ldw, out,
-                       proba, votes);
-    HYPEL_CHECK_LAUNCH("hypel_forest_oob_rows");
+    const char* name = "hypel_forest_oob_rows";
+    Walk w;
+    if (forest_model(name, &w.m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes)) return -1;
+    HYPEL_REQUIRE(x && weight && out && proba && votes, name);
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && ldw >= n, name);
+    if (forest_walk_grid(name, &w, n, 1)) return -1;
+    hipLaunchKernelGGL(oob_rows_kernel, dim3(w.blocks), dim3(PRED_LANES), w.lds, ST, x, ld, n, w.m, class_labels, weight,
+                       ldw, out, proba, votes);
+    HYPEL_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -964,22 +970,16 @@ extern "C" int hypel_forest_permuted_hits(const float* x, int64_t ld, int64_t n,
                                           const int32_t* y, const int32_t* partner, int32_t n_repeats,
                                           int32_t group_mod, int32_t g0, int32_t n_groups, int32_t* hits,
                                           hypel_stream_t stream) {
-    Model m;
-    if (forest_model("hypel_forest_permuted_hits", &m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves,
-                     n_classes))
-        return -1;
-    HYPEL_REQUIRE(x && y && partner && hits, "hypel_forest_permuted_hits");
-    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && n_repeats >= 1, "hypel_forest_permuted_hits");
-    HYPEL_REQUIRE(group_mod >= 1 && g0 >= 0 && n_groups >= 1 && (int64_t)g0 + n_groups <= group_mod,
-                  "hypel_forest_permuted_hits");
-    const int64_t row_blocks = (n + PRED_LANES - 1) / PRED_LANES;
-    // (three factors below 2^31 each: the product of the first two fits, the division never overflows)
-    HYPEL_REQUIRE((int64_t)n_groups * n_repeats <= (((int64_t)1 << 31) - 1) / row_blocks,
-                  "hypel_forest_permuted_hits: more than 2^31 - 1 blocks, launch fewer groups at a time");
-    hipLaunchKernelGGL(permuted_hits_kernel, dim3((unsigned)((int64_t)n_groups * n_repeats * row_blocks)),
-                       dim3(PRED_LANES), (size_t)n_classes * PRED_LANES * sizeof(double), ST, x, ld, n, row_blocks, m, y,
+    const char* name = "hypel_forest_permuted_hits";
+    Walk w;
+    if (forest_model(name, &w.m, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes)) return -1;
+    HYPEL_REQUIRE(x && y && partner && hits, name);
+    HYPEL_REQUIRE(n > 0 && f > 0 && ld >= f && n_repeats >= 1, name);
+    HYPEL_REQUIRE(group_mod >= 1 && g0 >= 0 && n_groups >= 1 && (int64_t)g0 + n_groups <= group_mod, name);
+    if (forest_walk_grid(name, &w, n, (int64_t)n_groups * n_repeats)) return -1;
+    hipLaunchKernelGGL(permuted_hits_kernel, dim3(w.blocks), dim3(PRED_LANES), w.lds, ST, x, ld, n, w.row_blocks, w.m, y,
                        partner, n_repeats, group_mod, g0, hits);
-    HYPEL_CHECK_LAUNCH("hypel_forest_permuted_hits");
+    HYPEL_CHECK_LAUNCH(name);
     return 0;
 }
 

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE shared by tests/test_extra_trees_emu.py and tests/test_gpu_extra_trees.py: a recording
 ExtraTreesForest, the scikit-learn fixture of tests/golden/make_reference_extra_trees.py, and a brute-force fit that
 replays the draw order ExtraTreesForest documents -- node by node in plain numpy and Python ints, written from the class
-docstring and include/hypel.h, sharing no code with the class, the kernels or tests/emu_extra_trees.py."""
+docstring and include/hypel.h, sharing no code with the class, the kernels or tests/emu_forest.py."""
 import numpy as np
 
 from hypelcnn_amd.backend import FOREST_MAX_DEPTH

@@ -1,10 +1,11 @@
 """TEST INFRASTRUCTURE shared by tests/test_gpu_extra_trees_kernels.py (the HIP kernels, through the C-ABI) and
-tests/test_extra_trees_kernel_cases_emu.py (the numpy emulation, tests/emu_extra_trees.py): case tables and a brute-force
+tests/test_extra_trees_kernel_cases_emu.py (the numpy emulation, tests/emu_forest.py): case tables and a brute-force
 reference of hypel_forest_columns_f32, hypel_forest_split_random and hypel_forest_split_apply_thr.
 
 Reference.  `ref_*` below: plain Python written from include/hypel.h alone -- np.float32 scalars for d, m and t (one
 rounding per operation), Python ints for the class weights and the sums of squares, Python floats for the two divisions
-and the addition, a literal stable partition.  It shares no code with tests/emu_extra_trees.py and does not import it.
+and the addition.  It shares no code with tests/emu_forest.py and does not import it.  hypel_forest_split_apply_thr is
+the one apply of tests/forest_kernel_cases.py: its reference, runners and tables serve both searches, here as K.CUTS.
 
 Operands, `launch`, `run` and `settle` are those of tests/forest_kernel_cases.py: every pointer is an `Op` at an odd
 offset inside sentinel bytes, every launch runs twice and must write the same bytes, and afterwards every byte of every
@@ -66,52 +67,6 @@ def ref_split_random(xt, ldn, y, weight, n, n_classes, order, active, n_active, 
                 cuts.append((at, lo, hi, t, sum(1 for v in vals if v <= t), count))
 
 
-def ref_split_apply_thr(xt, ldn, y, weight, n, n_classes, order_in, order_out, active, n_active, cand, max_features, f,
-                        score, thr, valid, level, max_depth, node_base, node_capacity, feature, thr_bin, threshold, left,
-                        right, node_tree, node_count, node_weight, value, split_ws, next_active, counter):
-    r, overflow = 0, False
-    for a in range(n_active):
-        tree, start, count, node = (int(v) for v in active[4 * a:4 * a + 4])
-        rows = [int(order_in[start + i]) for i in range(count)]
-        cls = [0] * n_classes
-        for s in rows:
-            cls[int(y[s])] += int(weight[tree * n + s])
-        pick = None
-        for s in range(max_features):
-            at = a * max_features + s
-            if valid[at]:
-                key = (-float(score[at]), int(cand[at]), at)
-                if pick is None or key < pick:
-                    pick = key
-        leaf = count < 2 or sum(1 for v in cls if v > 0) < 2 or pick is None or level >= max_depth
-        node_tree[node], node_count[node], node_weight[node] = tree, count, sum(cls)
-        for k in range(n_classes):
-            value[node * n_classes + k] = float(cls[k]) / float(sum(cls))
-        left[node] = right[node] = thr_bin[node] = -1
-        if leaf:
-            feature[node], threshold[node], split_ws[a] = -1, 0.0, 0
-            continue
-        c, t = pick[1], F32(thr[pick[2]])
-        feature[node], threshold[node] = c, t
-        at = start
-        for side in (True, False):  # the stable partition, literally
-            for s in rows:
-                if bool(F32(xt[c * ldn + s]) <= t) == side:
-                    order_out[at] = s
-                    at += 1
-            if side:
-                n_left = at - start
-        split_ws[a] = n_left
-        lid = node_base + 2 * r
-        if lid + 1 < node_capacity:
-            left[node], right[node] = lid, lid + 1
-            next_active[8 * r:8 * r + 8] = (tree, start, n_left, lid, tree, start + n_left, count - n_left, lid + 1)
-        else:
-            overflow = True
-        r += 1
-    counter[0] = -1 if overflow else 2 * r
-
-
 # ============================================================================================================ 1. columns
 COLUMN_CASES = [(1, 1), (63, 5), (65, 33), (257, 3)]
 
@@ -135,17 +90,6 @@ def run_columns(be, n, f):
 
 
 # ======================================================================================================= 2. split_random
-def with_columns(d, rng, values=None):
-    """the scenario of forest_kernel_cases with raw columns xt [f + 1][ldn] beside its bins (the row past the last
-    column and the row tails are sentinels); no weight is 0 (a segment holds in-bag rows)"""
-    f, n = d["f"], d["n"]
-    xt = sent(F32, (f + 1) * d["ldn"]).reshape(f + 1, d["ldn"])
-    xt[:f, :n] = (rng.standard_normal((f, n)) * 10).astype(F32) if values is None else values
-    d["xt"] = xt
-    assert all((d["weight"][t, rows] > 0).all() for (t, _, _, _), rows in zip(d["active"], d["segs"]))
-    return d
-
-
 def random_ops(d, cand, u):
     mf = cand.shape[1]
     rec = d["n_active"] * mf + 3  # three records past the last stay untouched
@@ -170,7 +114,7 @@ def random_scenario(name):
     rng = np.random.default_rng(sum(name.encode()))
     if counts is None:
         counts = [int(v) for v in rng.integers(2, 9, 600)]
-    d = with_columns(K.scenario(rng, counts, C, w_max=w_max, zero=0), rng)
+    d = K.with_columns(K.scenario(rng, counts, C, w_max=w_max, zero=0), rng)
     if w_max > 9:
         d["weight"][...] = np.maximum(d["weight"], 1 << 14)
     if name == "c3_w9":  # few distinct values: many rows equal to the cut's neighbours, many equal lo
@@ -202,7 +146,7 @@ SPECIAL_COUNTS = [2, 16, 64, 65, 300, 2]
 def special_scenario():
     rng = np.random.default_rng(77)
     d = K.disjoint_scenario(rng, SPECIAL_COUNTS, 2, 7, zero=0)
-    with_columns(d, rng)
+    K.with_columns(d, rng)
     for rows in d["segs"]:
         k = len(rows)
         first = rng.permutation(k)
@@ -250,142 +194,13 @@ def run_random_special(be):
 
 
 # ================================================================================================== 3. split_apply_thr
-def run_apply_thr(be, d, cand, score, thr, valid, level, max_depth, node_base, short=0, tag=""):
-    """One launch; node_capacity = node_base + 2 * (the nodes the reference splits) - short.  Returns the Ops by name."""
-    na, mf = d["n_active"], cand.shape[1]
-    rng = np.random.default_rng(na + mf)
-    d["active"][:, 3] = node_base - na + rng.permutation(na)  # the nodes of this level, not in active-node order
-    order_out = Op("order_out", sent(I32, d["order"].size))
-
-    def args(cap, o):
-        return (Op("xt", d["xt"]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"],
-                Op("order_in", d["order"]), order_out, Op("active", d["active"]), na, Op("cand", cand), mf, d["f"],
-                Op("score", score), Op("thr", thr), Op("valid", valid), level, max_depth, node_base, cap, *o.values())
-
-    dry = K.node_ops(d, node_base + 2 * na, na)
-    ref_split_apply_thr(*[a.want if isinstance(a, Op) else a for a in args(node_base + 2 * na, dry)])
-    order_out.want = order_out.init.copy()
-    cap = node_base + int(dry["counter"].want[0]) - short
-    o = K.node_ops(d, cap, na)
-    run(be, "forest_split_apply_thr", ref_split_apply_thr, *args(cap, o), tag=tag)
-    assert (o["thr_bin"].want[d["active"][:, 3]] == -1).all()  # also of the nodes that split
-    o["order_out"], o["cap"], o["splits"] = order_out, cap, int(dry["counter"].want[0]) // 2
-    return o
-
-
-PART_COUNTS = [2, 63, 64, 65, 255, 256, 257, 513, 1000]
-
-
-def run_partition(be):
-    """counts 2 .. 1000, three nodes each: one row, all but one and a random number of rows go left; left rows lie at
-    or below the cut (some exactly on it), right rows above it (some one ulp above)"""
-    rng = np.random.default_rng(31)
-    counts = [c for c in PART_COUNTS for _ in range(3)]
-    d = with_columns(K.disjoint_scenario(rng, counts, 3, 2, zero=0), rng)
-    na = len(counts)
-    cand = np.stack([rng.permutation(2) for _ in range(na)]).astype(I32)
-    score, thr, valid = np.zeros(na * 2), np.zeros(na * 2, F32), np.zeros(na * 2, I32)
-    want_left = []
-    for a, rows in enumerate(d["segs"]):
-        count = len(rows)
-        n_left = (1, count - 1, int(rng.integers(1, count)))[a % 3]
-        t = F32(rng.standard_normal() * 5)
-        go = rng.permutation(count) < n_left
-        below = np.where(rng.random(count) < 0.3, t, t - np.abs(rng.standard_normal(count)).astype(F32) - F32(1e-3))
-        above = np.where(rng.random(count) < 0.3, np.nextafter(t, F32(np.inf)),
-                         t + np.abs(rng.standard_normal(count)).astype(F32) + F32(1e-3))
-        d["xt"][int(cand[a, a % 2]), rows] = np.where(go, below, above).astype(F32)
-        score[a * 2 + a % 2], thr[a * 2 + a % 2], valid[a * 2 + a % 2] = 1.0 + a, t, 1
-        want_left.append(n_left)
-    o = run_apply_thr(be, d, cand, score, thr, valid, 2, 9, 100, tag="partition")
-    assert list(o["split_ws"].want[:na]) == want_left and o["splits"] == na
-    for (_, start, count, _), rows in zip(d["active"], d["segs"]):
-        assert sorted(o["order_out"].want[start:start + count]) == sorted(rows)
-
-
-LEAF_LEVELS = [(3, 4), (4, 4), (0, 0), (5, 4)]
-
-
-def run_leaf_reasons(be, level, max_depth):
-    """Six nodes: 0 one row; 1 two classes of which one has weight 0 only; 2 no valid slot; 3, 5 split; 4 a valid slot
-    whose score is smaller than an invalid slot's.  At level >= max_depth none splits."""
-    rng = np.random.default_rng(7)
-    d = with_columns(K.disjoint_scenario(rng, [1, 40, 40, 40, 40, 2], 2, 3, zero=0), rng)
-    seg = d["segs"][1]
-    d["weight"][1, seg] = np.where(d["y"][seg] == 1, 0, 5)  # (apply alone: the class of weight 0 is absent)
-    assert (d["y"][seg] == 1).any() and (d["y"][seg] == 0).any()
-    cand = K.draw_cand(rng, 6, 2, 3)
-    score, thr, valid = rng.random(12) + 1, np.full(12, 0.5, F32), np.ones(12, I32)
-    valid[4:6] = 0  # node 2
-    valid[8], score[8], score[9] = 0, 99.0, 0.5  # node 4: the invalid slot's score is ignored
-    for a in (3, 4, 5):
-        rows = d["segs"][a]
-        d["xt"][:3, rows[0]], d["xt"][:3, rows[1]] = 0.5, np.nextafter(F32(0.5), F32(1))
-    o = run_apply_thr(be, d, cand, score, thr, valid, level, max_depth, 20, tag=f"level {level} of {max_depth}")
-    assert o["splits"] == (3 if level < max_depth else 0)
-    nodes = d["active"][:, 3]
-    assert (o["feature"].want[nodes[:3]] == -1).all() and (o["threshold"].want[nodes[:3]] == 0).all()
-    assert o["feature"].want[nodes[4]] == (cand[4, 1] if level < max_depth else -1)
-
-
-def run_slot_ties(be):
-    """mf = 3; per node (columns, scores, valid) -> the column that must win: equal scores with the lower column in a
-    later slot; a three-way tie, the lowest column last; the best score in the last slot and the highest column; an
-    invalid slot with the best score and the lowest column.  Every slot has its own cut, so threshold names the slot."""
-    table = [((4, 2, 0), (5.0, 5.0, 4.0), (1, 1, 1), 2),
-             ((3, 1, 0), (7.0, 7.0, 7.0), (1, 1, 1), 0),
-             ((0, 1, 4), (1.0, 2.0, 3.0), (1, 1, 1), 4),
-             ((0, 3, 2), (9.0, 5.0, 5.0), (0, 1, 1), 2)]
-    rng = np.random.default_rng(11)
-    d = with_columns(K.disjoint_scenario(rng, [50] * len(table), 2, 5, zero=0), rng)
-    for rows in d["segs"]:  # every cut of the table has rows on both sides
-        d["xt"][:5, rows[0]], d["xt"][:5, rows[1]] = -100.0, 100.0
-    cand = np.array([t[0] for t in table], I32)
-    score = np.array([t[1] for t in table], F64).reshape(-1)
-    valid = np.array([t[2] for t in table], I32).reshape(-1)
-    thr = (np.arange(len(table) * 3) * 0.25 - 1).astype(F32)
-    o = run_apply_thr(be, d, cand, score, thr, valid, 0, 64, 5, tag="slot ties")
-    for a, node in enumerate(d["active"][:, 3]):
-        want = table[a][3]
-        assert int(o["feature"].want[node]) == want
-        assert o["threshold"].want[node] == thr[a * 3 + table[a][0].index(want)]
-
-
-COMPACT_N = [1, 255, 256, 257, 600]
-COMPACT_PATTERNS = ["all", "none", "alternating", "last"]
-
-
-def run_compaction(be, n_active, pattern, short=0):
-    """n_active nodes of two rows; a node of the pattern splits (values 0 and 1, cut 0.5), the others have no valid
-    slot.  short = 1: node_capacity is one too small -- the last child has no room, counter = -1"""
-    rng = np.random.default_rng(n_active)
-    d = with_columns(K.disjoint_scenario(rng, [2] * n_active, 2, 1, zero=0), rng)
-    split = {"all": np.ones(n_active, bool), "none": np.zeros(n_active, bool),
-             "alternating": np.arange(n_active) % 2 == 0, "last": np.arange(n_active) == n_active - 1}[pattern]
-    for rows in d["segs"]:
-        d["xt"][0, rows] = rng.permutation(2)
-    cand = np.zeros((n_active, 1), I32)
-    score, thr, valid = np.where(split, 1.5, 0.0), np.where(split, 0.5, 0.0).astype(F32), split.astype(I32)
-    tag = f"compaction {n_active} {pattern} short {short}"
-    o = run_apply_thr(be, d, cand, score, thr, valid, 1, 8, 1000, short=short, tag=tag)
-    assert o["splits"] == split.sum()
-    if short and split.any():
-        last = d["active"][np.flatnonzero(split)[-1], 3]
-        assert o["counter"].want[0] == -1 and o["left"].want[last] == -1 and o["right"].want[last] == -1
-        written = 8 * (o["splits"] - 1)
-        assert (o["next_active"].want[written:].view(np.uint8) == K.FILL).all()
-        assert (o["next_active"].want[:written] >= 0).all()
-    else:
-        assert o["counter"].want[0] == 2 * split.sum()
-
-
 def run_random_then_apply(be, name):
     """the tables hypel_forest_split_random wrote through hypel_forest_split_apply_thr: every training row lands on the
     side it was counted on"""
     d, cand, args = run_random(be, name)
     rec = d["n_active"] * cand.shape[1]
-    o = run_apply_thr(be, d, cand, args[13].got[:rec], args[14].got[:rec], args[15].got[:rec], 0, 64,
-                      d["n_active"] + 10, tag=name)
+    o = K.run_apply(be, K.CUTS, d, cand, args[13].got[:rec], args[14].got[:rec], args[15].got[:rec], 0, 64,
+                    d["n_active"] + 10, tag=name)
     assert o["splits"] > d["n_active"] // 2
     return o
 
@@ -400,7 +215,7 @@ def refusal_calls():
     def columns(label, ld=8, ldn=8):
         calls.append((label, "forest_columns_f32", (Op("x", x), ld, 8, 5, Op("xt", sent(F32, 5 * 8)), ldn)))
 
-    d = with_columns(K.scenario(rng, [8, 8], 2, zero=0), rng)
+    d = K.with_columns(K.scenario(rng, [8, 8], 2, zero=0), rng)
     cand = K.draw_cand(rng, 2, 2, d["f"])
     u = rng.random((2, 2), dtype=F32)
 

@@ -1,10 +1,10 @@
 """TEST INFRASTRUCTURE shared by tests/test_gpu_forest_diag.py (the HIP kernels, through the C-ABI) and
-tests/test_forest_diag_emu.py (the numpy emulation, tests/emu_forest_diag.py): case tables and a brute-force reference of
+tests/test_forest_diag_emu.py (the numpy emulation, tests/emu_forest.py): case tables and a brute-force reference of
 hypel_forest_oob_rows, hypel_forest_permuted_hits and hypel_forest_importances_f64.
 
-Reference.  `ref_*` below: plain Python written from include/hypel.h alone -- the recursive walk of
+Reference.  `ref_*` below: plain Python written from include/hypel.h alone -- the recursive walk and the vote of
 tests/forest_kernel_cases.py, Python floats (IEEE double, one rounding per operation) for every vote and every importance
-sum, each sum a literal loop in the order the header states.  It shares no code with tests/emu_forest_diag.py and does
+sum, each sum a literal loop in the order the header states.  It shares no code with tests/emu_forest.py and does
 not import it.
 
 Operands, `launch`, `run` and `settle` are those of tests/forest_kernel_cases.py: every pointer is an `Op` at an odd
@@ -23,24 +23,12 @@ BLOCK = 256  # the chunk of nodes a workgroup of hypel_forest_importances_f64 ta
 
 
 # =============================================================================================== the reference (hypel.h)
-def ref_vote(rec, tree_off, leaf_value, n_classes, read, voting):
-    """(means, votes, first maximum) over the trees of `voting`, in tree order"""
-    acc, votes = [0.0] * n_classes, 0
-    for t in voting:
-        row, _ = K.walk(rec, int(tree_off[t]), read)
-        votes += 1
-        for k in range(n_classes):
-            acc[k] = acc[k] + float(leaf_value[row * n_classes + k])
-    mean = [v / float(votes) for v in acc] if votes else [0.0] * n_classes
-    return mean, votes, min(k for k in range(n_classes) if mean[k] == max(mean))
-
-
 def ref_oob_rows(x, ld, n, f, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes, class_labels, weight,
                  ldw, out, proba, votes):
     rec = nodes.view(FOREST_NODE_DTYPE)[:n_nodes]
     for i in range(n):
         voting = [t for t in range(n_trees) if not int(weight[t * ldw + i]) > 0]
-        mean, nv, win = ref_vote(rec, tree_off, leaf_value, n_classes, lambda c: x[i * ld + c], voting)
+        mean, nv, win, _ = K.vote(rec, tree_off, leaf_value, n_classes, lambda c: x[i * ld + c], voting)
         proba[i * n_classes:(i + 1) * n_classes] = mean
         votes[i] = nv
         out[i] = win if class_labels is None else class_labels[win]
@@ -54,7 +42,7 @@ def ref_permuted_hits(x, ld, n, f, tree_off, n_trees, nodes, n_nodes, leaf_value
             for i in range(n):
                 p = int(partner[r * n + i])
                 read = lambda c: x[(p if c % group_mod == g else i) * ld + c]  # noqa: E731
-                if ref_vote(rec, tree_off, leaf_value, n_classes, read, range(n_trees))[2] == int(y[i]):
+                if K.vote(rec, tree_off, leaf_value, n_classes, read, range(n_trees))[2] == int(y[i]):
                     hits[(g - g0) * n_repeats + r] += 1
 
 
@@ -161,7 +149,7 @@ def run_hits(be, n, n_classes, n_trees, n_repeats, group_mod, g0, n_groups):
     rng, model, x = model_and_rows(9000 * n + n_repeats, n, n_classes, n_trees)
     rec, tree_off, leaves = model
     ld = F + 3
-    win = [ref_vote(rec, tree_off, leaves.reshape(-1), n_classes, lambda c: x[i, c], range(n_trees))[2] for i in range(n)]
+    win = [K.vote(rec, tree_off, leaves.reshape(-1), n_classes, lambda c: x[i, c], range(n_trees))[2] for i in range(n)]
     y = np.where(rng.random(n) < 0.7, win, rng.integers(0, n_classes, n)).astype(I32)
     identity = n_repeats >= 3
     partner = np.stack([np.arange(n)] * identity + [rng.permutation(n) for _ in range(n_repeats - identity)]).astype(I32)
@@ -181,6 +169,16 @@ def run_hits(be, n, n_classes, n_trees, n_repeats, group_mod, g0, n_groups):
         if not tested:
             assert (added[g - g0] == baseline).all()
     return added, baseline
+
+
+def run_hits_tree_order(be):
+    """three stumps whose class sums depend on the order of the fp64 additions (the last of K.TIE_MODELS): every row is
+    a hit in tree order, none in the reverse"""
+    rows, winner = K.TIE_MODELS[-1]
+    args = (Op("x", K.padded_rows(np.zeros((3, 1), np.float32), 2)), 2, 3, 1, *model_ops(K.stump_model(rows)),
+            Op("y", np.full(3, winner, I32)), Op("partner", np.arange(3, dtype=I32)), 1, 1, 0, 1, Op("hits", np.zeros(1, I32)))
+    run(be, "forest_permuted_hits", ref_permuted_hits, *args, tag="tree order")
+    assert args[17].want[0] == 3
 
 
 # ================================================================================================== 3. importances

@@ -179,9 +179,26 @@ def ref_split_hist(bins, ldn, y, weight, n, n_classes, order, active, n_active, 
                     assert float(exact[1]) / float(exact[2]) + float(exact[3]) / float(exact[4]) == best[0], (a, s)
 
 
-def ref_split_apply(bins, ldn, y, weight, n, n_classes, order_in, order_out, active, n_active, cand, max_features, f,
-                    score, best_bin, valid, edges, level, max_depth, node_base, node_capacity, feature, thr_bin, threshold,
-                    left, right, node_tree, node_count, node_weight, value, split_ws, next_active, counter):
+class Search:
+    """What tells hypel_forest_split_apply (BINS) and hypel_forest_split_apply_thr (CUTS) apart; the rest is one algorithm.
+    For the call: kernel; table, the scenario's feature-major operand in front of the common ones (a row goes left where
+    its value <= the winning slot's cut); cut, the per-slot table between score and valid, of dtype; extra, the operands
+    behind valid.  For the reference: number(v), what the side test compares; tie(cut), a slot's keys after (score,
+    column); write(c, t, *extra) -> (thr_bin, threshold) of a split node.  For the scenarios: cut_out, the node array that
+    names the winning slot's cut; max_zero, the largest fraction of zero weights (a segment of the cuts holds in-bag rows
+    only); prepare(d, rng), what a scenario needs beside its bins; lo / hi, values left / right of every cut of a table;
+    above(t), the lowest value right of t; none / unit / leaf, the cut of an invalid slot, one between the values 0 and
+    1, and the one of run_leaf_reasons; tie_cuts, the cuts of SLOT_TIES; scatter(rng, count, n_left) -> (a drawn cut,
+    values of which n_left lie at or below it)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def ref_split_apply(S, table, ldn, y, weight, n, n_classes, order_in, order_out, active, n_active, cand, max_features, f,
+                    score, cut, valid, *rest):
+    (level, max_depth, node_base, node_capacity, feature, thr_bin, threshold, left, right, node_tree, node_count,
+     node_weight, value, split_ws, next_active, counter) = rest[len(S.extra):]
     r, overflow = 0, False
     for a in range(n_active):
         tree, start, count, node = (int(v) for v in active[4 * a:4 * a + 4])
@@ -193,7 +210,7 @@ def ref_split_apply(bins, ldn, y, weight, n, n_classes, order_in, order_out, act
         for s in range(max_features):
             at = a * max_features + s
             if valid[at]:
-                key = (-float(score[at]), int(cand[at]), int(best_bin[at]))
+                key = (-float(score[at]), int(cand[at]), *S.tie(cut[at]), at)
                 if pick is None or key < pick:
                     pick = key
         leaf = count < 2 or sum(1 for v in cls if v > 0) < 2 or pick is None or level >= max_depth
@@ -204,12 +221,13 @@ def ref_split_apply(bins, ldn, y, weight, n, n_classes, order_in, order_out, act
         if leaf:
             feature[node], thr_bin[node], threshold[node], split_ws[a] = -1, -1, 0.0, 0
             continue
-        c, t = pick[1], pick[2]
-        feature[node], thr_bin[node], threshold[node] = c, t, edges[c * E + t]
+        c, t = pick[1], S.number(cut[pick[-1]])
+        feature[node] = c
+        thr_bin[node], threshold[node] = S.write(c, t, *rest[:len(S.extra)])
         at = start
         for side in (True, False):  # the stable partition, literally
             for s in rows:
-                if (int(bins[c * ldn + s]) <= t) == side:
+                if bool(S.number(table[c * ldn + s]) <= t) == side:
                     order_out[at] = s
                     at += 1
             if side:
@@ -233,15 +251,16 @@ def walk(nodes, at, read, depth=0):
     return walk(nodes, int(lo) if np.float32(read(int(feature))) <= np.float32(threshold) else int(hi), read, depth + 1)
 
 
-def vote(nodes, tree_off, n_trees, leaf_value, n_classes, read):
-    acc, deepest = [0.0] * n_classes, 0
-    for t in range(n_trees):  # tree order, one fp64 addition per tree and class
+def vote(nodes, tree_off, leaf_value, n_classes, read, voting):
+    """(means, votes, first maximum, the deepest walk) over the trees of `voting`, in tree order"""
+    acc, votes, deepest = [0.0] * n_classes, 0, 0
+    for t in voting:  # tree order, one fp64 addition per voting tree and class
         row, depth = walk(nodes, int(tree_off[t]), read)
-        deepest = max(deepest, depth)
+        votes, deepest = votes + 1, max(deepest, depth)
         for k in range(n_classes):
             acc[k] = acc[k] + float(leaf_value[row * n_classes + k])
-    mean = [v / float(n_trees) for v in acc]
-    return mean, min(k for k in range(n_classes) if mean[k] == max(mean)), deepest
+    mean = [v / float(votes) for v in acc] if votes else [0.0] * n_classes
+    return mean, votes, min(k for k in range(n_classes) if mean[k] == max(mean)), deepest
 
 
 def ref_predict_rows(x, ld, n, f, tree_off, n_trees, nodes, n_nodes, leaf_value, n_leaves, n_classes, class_labels,
@@ -249,7 +268,7 @@ def ref_predict_rows(x, ld, n, f, tree_off, n_trees, nodes, n_nodes, leaf_value,
     """depths: a list that receives, per row, the length of its longest walk"""
     rec = nodes.view(FOREST_NODE_DTYPE)[:n_nodes]
     for i in range(n):
-        mean, win, deepest = vote(rec, tree_off, n_trees, leaf_value, n_classes, lambda c: x[i * ld + c])
+        mean, _, win, deepest = vote(rec, tree_off, leaf_value, n_classes, lambda c: x[i * ld + c], range(n_trees))
         if depths is not None:
             depths.append(deepest)
         label = win if class_labels is None else class_labels[win]
@@ -474,26 +493,66 @@ def edges_table(rng, f):
     return np.sort((rng.standard_normal((f, E)) * 50).astype(F32), 1)
 
 
-def run_apply(be, d, cand, score, best_bin, valid, level, max_depth, node_base, short=0, tag=""):
+def with_columns(d, rng, values=None):
+    """a scenario with raw columns xt [f + 1][ldn] beside its bins (the row past the last column and the row tails are
+    sentinels); no weight is 0 (a segment holds in-bag rows)"""
+    f, n = d["f"], d["n"]
+    xt = sent(F32, (f + 1) * d["ldn"]).reshape(f + 1, d["ldn"])
+    xt[:f, :n] = (rng.standard_normal((f, n)) * 10).astype(F32) if values is None else values
+    d["xt"] = xt
+    assert all((d["weight"][t, rows] > 0).all() for (t, _, _, _), rows in zip(d["active"], d["segs"]))
+    return d
+
+
+def scatter_bins(rng, count, n_left):
+    t = int(rng.integers(0, 255))
+    go = rng.permutation(count) < n_left
+    return t, np.where(go, rng.integers(0, t + 1, count), rng.integers(t + 1, 256, count))
+
+
+def scatter_cuts(rng, count, n_left):
+    """left rows lie at or below the cut (some exactly on it), right rows above it (some one ulp above)"""
+    t = F32(rng.standard_normal() * 5)
+    go = rng.permutation(count) < n_left
+    below = np.where(rng.random(count) < 0.3, t, t - np.abs(rng.standard_normal(count)).astype(F32) - F32(1e-3))
+    above = np.where(rng.random(count) < 0.3, np.nextafter(t, F32(np.inf)),
+                     t + np.abs(rng.standard_normal(count)).astype(F32) + F32(1e-3))
+    return t, np.where(go, below, above).astype(F32)
+
+
+BINS = Search(kernel="forest_split_apply", table="bins", cut="best_bin", dtype=I32, extra=("edges",), number=int,
+              tie=lambda t: (int(t),), write=lambda c, t, edges: (t, edges[c * E + t]), cut_out="thr_bin", max_zero=1.0,
+              prepare=lambda d, rng: d.update(edges=edges_table(rng, d["f"])), lo=0, hi=255, above=lambda t: t + 1,
+              none=-1, unit=0, leaf=100, tie_cuts=[1, 9, 0, 0, 9, 200, 3, 250, 3, 5, 5, 5, 7, 8, 6], scatter=scatter_bins)
+CUTS = Search(kernel="forest_split_apply_thr", table="xt", cut="thr", dtype=F32, extra=(), number=F32, tie=lambda t: (),
+              write=lambda c, t: (-1, t), cut_out="threshold", max_zero=0.0, prepare=with_columns, lo=-100.0, hi=100.0,
+              above=lambda t: np.nextafter(F32(t), F32(np.inf)), none=0.0, unit=0.5, leaf=0.5,
+              tie_cuts=np.arange(15) * 0.25 - 1, scatter=scatter_cuts)
+
+
+def run_apply(be, S, d, cand, score, cut, valid, level, max_depth, node_base, short=0, tag=""):
     """One launch; node_capacity = node_base + 2 * (the nodes the reference splits) - short.  Returns the Ops by name."""
     na, mf = d["n_active"], cand.shape[1]
     rng = np.random.default_rng(na + mf)
     d["active"][:, 3] = node_base - na + rng.permutation(na)  # the nodes of this level, not in active-node order
     order_out = Op("order_out", sent(I32, d["order"].size))
+    ref = lambda *a: ref_split_apply(S, *a)  # noqa: E731
 
     def args(cap, o):
-        return (Op("bins", d["bins"]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"],
+        return (Op(S.table, d[S.table]), d["ldn"], Op("y", d["y"]), Op("weight", d["weight"]), d["n"], d["C"],
                 Op("order_in", d["order"]), order_out, Op("active", d["active"]), na, Op("cand", cand), mf, d["f"],
-                Op("score", score), Op("best_bin", best_bin), Op("valid", valid), Op("edges", d["edges"]), level,
+                Op("score", score), Op(S.cut, cut), Op("valid", valid), *[Op(k, d[k]) for k in S.extra], level,
                 max_depth, node_base, cap, *o.values())
 
     dry = node_ops(d, node_base + 2 * na, na)
-    ref_split_apply(*[a.want if isinstance(a, Op) else a for a in args(node_base + 2 * na, dry)])
+    ref(*[a.want if isinstance(a, Op) else a for a in args(node_base + 2 * na, dry)])
     order_out.want = order_out.init.copy()
     cap = node_base + int(dry["counter"].want[0]) - short
     o = node_ops(d, cap, na)
-    a = args(cap, o)
-    run(be, "forest_split_apply", ref_split_apply, *a, tag=tag)
+    run(be, S.kernel, ref, *args(cap, o), tag=tag)
+    thr_bin = o["thr_bin"].want[d["active"][:, 3]]
+    binned = (o["feature"].want[d["active"][:, 3]] >= 0) & (S.cut_out == "thr_bin")
+    assert (thr_bin[~binned] == -1).all() and (thr_bin[binned] >= 0).all()  # -1: a leaf, and every node of the cuts
     o["order_out"], o["cap"], o["splits"] = order_out, cap, int(dry["counter"].want[0]) // 2
     return o
 
@@ -520,24 +579,27 @@ def disjoint_scenario(rng, counts, n_classes, f, **kw):
     return d
 
 
-def run_partition(be):
+def apply_scenario(S, rng, counts, n_classes, f, zero=0.2):
+    d = disjoint_scenario(rng, counts, n_classes, f, zero=min(zero, S.max_zero))
+    S.prepare(d, rng)
+    return d
+
+
+def run_partition(be, S):
+    """counts 2 .. 1000, three nodes each: one row, all but one and a random number of rows go left (S.scatter)"""
     rng = np.random.default_rng(31)
     counts = [c for c in PART_COUNTS for _ in range(3)]
-    d = disjoint_scenario(rng, counts, 3, 2, zero=0.1)
-    d["edges"] = edges_table(rng, 2)
+    d = apply_scenario(S, rng, counts, 3, 2, zero=0.1)
     na = len(counts)
     cand = np.stack([rng.permutation(2) for _ in range(na)]).astype(I32)
-    score, best, valid = np.zeros(na * 2), np.full(na * 2, -1, I32), np.zeros(na * 2, I32)
+    score, cut, valid = np.zeros(na * 2), np.full(na * 2, S.none, S.dtype), np.zeros(na * 2, I32)
     want_left = []
     for a, rows in enumerate(d["segs"]):
-        count = len(rows)
-        n_left = (1, count - 1, int(rng.integers(1, count)))[a % 3]
-        t = int(rng.integers(0, 255))
-        go = rng.permutation(count) < n_left
-        d["bins"][int(cand[a, a % 2]), rows] = np.where(go, rng.integers(0, t + 1, count), rng.integers(t + 1, 256, count))
-        score[a * 2 + a % 2], best[a * 2 + a % 2], valid[a * 2 + a % 2] = 1.0 + a, t, 1
+        n_left = (1, len(rows) - 1, int(rng.integers(1, len(rows))))[a % 3]
+        t, d[S.table][int(cand[a, a % 2]), rows] = S.scatter(rng, len(rows), n_left)
+        score[a * 2 + a % 2], cut[a * 2 + a % 2], valid[a * 2 + a % 2] = 1.0 + a, t, 1
         want_left.append(n_left)
-    o = run_apply(be, d, cand, score, best, valid, 2, 9, 100, tag="partition")
+    o = run_apply(be, S, d, cand, score, cut, valid, 2, 9, 100, tag="partition")
     assert list(o["split_ws"].want[:na]) == want_left and o["splits"] == na
     for (_, start, count, _), rows in zip(d["active"], d["segs"]):
         assert sorted(o["order_out"].want[start:start + count]) == sorted(rows)
@@ -546,69 +608,74 @@ def run_partition(be):
 LEAF_LEVELS = [(3, 4), (4, 4), (0, 0), (5, 4)]
 
 
-def run_leaf_reasons(be, level, max_depth):
+def run_leaf_reasons(be, S, level, max_depth):
     """Six nodes: 0 one row; 1 two classes of which one has weight 0 only; 2 no valid slot; 3, 5 split; 4 a valid slot
     whose score is smaller than an invalid slot's.  At level < max_depth nodes 3, 4 and 5 split; at level >= max_depth
     none does and the level is the only reason for 3, 4 and 5."""
     rng = np.random.default_rng(7)
-    d = disjoint_scenario(rng, [1, 40, 40, 40, 40, 2], 2, 3)
-    d["edges"] = edges_table(rng, 3)
+    d = apply_scenario(S, rng, [1, 40, 40, 40, 40, 2], 2, 3)
     seg = d["segs"][1]
-    d["weight"][1, seg] = np.where(d["y"][seg] == 1, 0, 5)
+    d["weight"][1, seg] = np.where(d["y"][seg] == 1, 0, 5)  # (apply alone: with the cuts such a class would be absent)
     assert (d["y"][seg] == 1).any() and (d["y"][seg] == 0).any()
     cand = draw_cand(rng, 6, 2, 3)
-    score, best, valid = rng.random(12) + 1, np.full(12, 100, I32), np.ones(12, I32)
+    score, cut, valid = rng.random(12) + 1, np.full(12, S.leaf, S.dtype), np.ones(12, I32)
     valid[4:6] = 0  # node 2
     valid[8], score[8], score[9] = 0, 99.0, 0.5  # node 4: the invalid slot's score is ignored
     for a in (3, 4, 5):
         rows = d["segs"][a]
-        d["bins"][:3, rows[0]], d["bins"][:3, rows[1]] = 100, 101
-    o = run_apply(be, d, cand, score, best, valid, level, max_depth, 20, tag=f"level {level} of {max_depth}")
+        d[S.table][:3, rows[0]], d[S.table][:3, rows[1]] = S.leaf, S.above(S.leaf)
+    o = run_apply(be, S, d, cand, score, cut, valid, level, max_depth, 20, tag=f"level {level} of {max_depth}")
     assert o["splits"] == (3 if level < max_depth else 0)
     nodes = d["active"][:, 3]
-    assert (o["feature"].want[nodes[:3]] == -1).all() and o["feature"].want[nodes[4]] == (cand[4, 1] if level < max_depth else -1)
+    assert (o["feature"].want[nodes[:3]] == -1).all() and (o["threshold"].want[nodes[:3]] == 0).all()
+    assert o["feature"].want[nodes[4]] == (cand[4, 1] if level < max_depth else -1)
 
 
-def run_slot_ties(be):
-    """mf = 3; per node (columns, scores, bins, valid) -> the column that must win:
-    0: equal scores, the lower column in a later slot;  1: a three-way tie at the top score, the lowest column last;
-    2: equal score -- the lower column wins although its bin is the higher;  3: the best score in the last slot and the
-    highest column;  4: an invalid slot with the best score and the lowest column"""
-    table = [((4, 2, 0), (5.0, 5.0, 4.0), (1, 9, 0), (1, 1, 1), 2),
-             ((3, 1, 0), (7.0, 7.0, 7.0), (0, 9, 200), (1, 1, 1), 0),
-             ((4, 1, 2), (6.5, 6.5, 1.0), (3, 250, 3), (1, 1, 1), 1),
-             ((0, 1, 4), (1.0, 2.0, 3.0), (5, 5, 5), (1, 1, 1), 4),
-             ((0, 3, 2), (9.0, 5.0, 5.0), (7, 8, 6), (0, 1, 1), 2)]
+# mf = 3; per node (columns, scores, valid) -> the column that must win; the slots' cuts are S.tie_cuts, all different
+# within a node of the cuts.  0: equal scores, the lower column in a later slot;  1: a three-way tie at the top score,
+# the lowest column last;  2: equal score -- the lower column wins although (BINS) its bin is the higher;  3: the best
+# score in the last slot and the highest column;  4: an invalid slot with the best score and the lowest column
+SLOT_TIES = [((4, 2, 0), (5.0, 5.0, 4.0), (1, 1, 1), 2),
+             ((3, 1, 0), (7.0, 7.0, 7.0), (1, 1, 1), 0),
+             ((4, 1, 2), (6.5, 6.5, 1.0), (1, 1, 1), 1),
+             ((0, 1, 4), (1.0, 2.0, 3.0), (1, 1, 1), 4),
+             ((0, 3, 2), (9.0, 5.0, 5.0), (0, 1, 1), 2)]
+
+
+def run_slot_ties(be, S):
+    """SLOT_TIES: the winner's column is the node's feature, and the node's thr_bin (BINS) or threshold (CUTS) names
+    the winning slot"""
     rng = np.random.default_rng(11)
-    d = disjoint_scenario(rng, [50] * len(table), 2, 5)
-    d["edges"] = edges_table(rng, 5)
-    for rows in d["segs"]:  # every boundary of the table has rows on both sides
-        d["bins"][:5, rows[0]], d["bins"][:5, rows[1]] = 0, 255
-    cand = np.array([t[0] for t in table], I32)
-    score = np.array([t[1] for t in table], F64).reshape(-1)
-    best, valid = (np.array([t[k] for t in table], I32).reshape(-1) for k in (2, 3))
-    o = run_apply(be, d, cand, score, best, valid, 0, 64, 5, tag="slot ties")
-    assert [int(o["feature"].want[node]) for node in d["active"][:, 3]] == [t[4] for t in table]
+    d = apply_scenario(S, rng, [50] * len(SLOT_TIES), 2, 5)
+    for rows in d["segs"]:  # every cut of the table has rows on both sides
+        d[S.table][:5, rows[0]], d[S.table][:5, rows[1]] = S.lo, S.hi
+    cand = np.array([t[0] for t in SLOT_TIES], I32)
+    score = np.array([t[1] for t in SLOT_TIES], F64).reshape(-1)
+    valid = np.array([t[2] for t in SLOT_TIES], I32).reshape(-1)
+    cut = np.asarray(S.tie_cuts).astype(S.dtype)
+    o = run_apply(be, S, d, cand, score, cut, valid, 0, 64, 5, tag="slot ties")
+    for a, ((cols, _, _, winner), node) in enumerate(zip(SLOT_TIES, d["active"][:, 3])):
+        assert int(o["feature"].want[node]) == winner
+        assert o[S.cut_out].want[node] == cut[3 * a + cols.index(winner)]
 
 
 COMPACT_N = [1, 255, 256, 257, 600]
 COMPACT_PATTERNS = ["all", "none", "alternating", "last"]
 
 
-def run_compaction(be, n_active, pattern, short=0):
-    """n_active nodes of two rows; a node of the pattern splits (bins 0 and 1, boundary 0), the others have no valid
-    slot.  short = 1: node_capacity is one too small -- the last child has no room, counter = -1"""
+def run_compaction(be, S, n_active, pattern, short=0):
+    """n_active nodes of two rows; a node of the pattern splits (values 0 and 1, the cut S.unit), the others have no
+    valid slot.  short = 1: node_capacity is one too small -- the last child has no room, counter = -1"""
     rng = np.random.default_rng(n_active)
-    d = disjoint_scenario(rng, [2] * n_active, 2, 1, zero=0)
-    d["edges"] = edges_table(rng, 1)
+    d = apply_scenario(S, rng, [2] * n_active, 2, 1, zero=0)
     split = {"all": np.ones(n_active, bool), "none": np.zeros(n_active, bool),
              "alternating": np.arange(n_active) % 2 == 0, "last": np.arange(n_active) == n_active - 1}[pattern]
     for rows in d["segs"]:
-        d["bins"][0, rows] = rng.permutation(2)
+        d[S.table][0, rows] = rng.permutation(2)
     cand = np.zeros((n_active, 1), I32)
-    score, best, valid = np.where(split, 1.5, 0.0), np.where(split, 0, -1).astype(I32), split.astype(I32)
+    score, cut, valid = np.where(split, 1.5, 0.0), np.where(split, S.unit, S.none).astype(S.dtype), split.astype(I32)
     tag = f"compaction {n_active} {pattern} short {short}"
-    o = run_apply(be, d, cand, score, best, valid, 1, 8, 1000, short=short, tag=tag)
+    o = run_apply(be, S, d, cand, score, cut, valid, 1, 8, 1000, short=short, tag=tag)
     assert o["splits"] == split.sum()
     if short and split.any():
         last = d["active"][np.flatnonzero(split)[-1], 3]
@@ -624,7 +691,7 @@ def run_hist_then_apply(be, name):
     d, cand, args = run_hist(be, name)
     rec = d["n_active"] * cand.shape[1]
     d["edges"] = edges_table(np.random.default_rng(5), d["f"])
-    o = run_apply(be, d, cand, args[12].got[:rec], args[13].got[:rec], args[14].got[:rec], 0, 64, 10, tag=name)
+    o = run_apply(be, BINS, d, cand, args[12].got[:rec], args[13].got[:rec], args[14].got[:rec], 0, 64, 10, tag=name)
     assert o["splits"] > 0
 
 

@@ -1,5 +1,5 @@
 """CPU: hypelcnn_amd.classic.forest.ExtraTreesForest and `classic_ml_trainer --estimator extra_trees` on the numpy
-emulation of the extra-trees entry points (tests/emu_extra_trees.py): purity, seeds, a brute-force fit that replays the
+emulation of the extra-trees entry points (tests/emu_forest.py): purity, seeds, a brute-force fit that replays the
 documented draw order, the trainer, and the accuracy against scikit-learn's ExtraTreesClassifier recorded by
 tests/golden/make_reference_extra_trees.py.  tests/test_gpu_extra_trees.py holds the device to this emulation bit for
 bit."""
@@ -11,7 +11,7 @@ import pytest
 
 from hypelcnn_amd.classic import forest as P
 from hypelcnn_amd.classify import classic_ml_trainer as T
-from tests import emu_extra_trees, emu_forest, emu_scene  # noqa: F401 -- attach the emulations to EmuBackend
+from tests import emu_forest, emu_scene  # noqa: F401 -- attach the emulations to EmuBackend
 from tests import extra_trees_cases as XC
 from tests import forest_cases as FC
 from tests import svm_cases as S

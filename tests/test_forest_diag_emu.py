@@ -1,17 +1,14 @@
 """CPU: every case table of tests/forest_diag_cases.py through the numpy emulation of the forest diagnostics
-(tests/emu_forest_diag.py) against the brute-force reference of the case module -- two renditions of include/hypel.h that
+(tests/emu_forest.py) against the brute-force reference of the case module -- two renditions of include/hypel.h that
 share no code.  Then defects planted in a copy of the emulation (a wrong tree filter, the division by n_trees instead of
 the votes, the node order of the importance sum reversed, a group taken by division instead of the remainder) must all be
 rejected."""
-import inspect
-
 import numpy as np
 import pytest
 
-from tests import emu_forest  # noqa: F401 -- the serving twins the shared helpers call
-from tests import emu_forest_diag
 from tests import forest_diag_cases as D
 from tests.emu_backend import EmuBackend
+from tests.emu_forest import mutant  # (the import attaches the emulation to EmuBackend)
 
 
 @pytest.fixture(scope="module")
@@ -61,21 +58,13 @@ def test_tables_cover_what_they_claim():
 
 
 # ------------------------------------------------------------------------------------------------------ planted defects
-def mutant(old, new):
-    """EmuBackend with the entry points of a copy of tests/emu_forest_diag.py in which `old` reads `new`"""
-    src = inspect.getsource(emu_forest_diag).split("\nfor _name, _fn in")[0]
-    assert src.count(old) == 1, (old, src.count(old))
-    ns = {"__name__": "emu_forest_diag_mutant"}
-    exec(compile(src.replace(old, new), "<emu_forest_diag mutant>", "exec"), ns)
-    return type("Mutant", (EmuBackend,), {k[1:]: v for k, v in ns.items() if k.startswith("_k_forest_")})()
-
-
 def test_the_unchanged_copy_passes():
     be = mutant("~(in_bag > 0)", "~(in_bag > 0)")
     assert be.k_forest_oob_rows.__func__ is not EmuBackend.k_forest_oob_rows
     D.run_oob(be, 65, 2, 1)
     D.run_hits(be, *D.HIT_CASES[3])
     D.run_importances(be, 64, True)
+    D.run_hits_tree_order(be)
 
 
 DEFECTS = {
@@ -92,6 +81,18 @@ DEFECTS = {
                           lambda be: D.run_hits(be, *D.HIT_CASES[3])),
     "hits overwritten": (("h[g - g0, r] += int(", "h[g - g0, r] = int("), lambda be: D.run_hits(be, *D.HIT_CASES[2])),
 }
+# the walk and the vote are shared with serving (tests/test_forest_kernel_cases_emu.py plants the same three there):
+# (change, what rejects it out of bag, what rejects it in the permuted hits)
+WALK_DEFECTS = {
+    "reverse tree order in the fp64 sum": (("for t in range(ends.shape[0]):", "for t in reversed(range(ends.shape[0])):"),
+                                           lambda be: D.run_oob(be, 64, 32, 3), D.run_hits_tree_order),
+    "threshold compare < instead of <=": (("feature[at]) <= threshold[at]", "feature[at]) < threshold[at]"),
+                                          lambda be: D.run_oob(be, 63, 2, 3), lambda be: D.run_hits(be, *D.HIT_CASES[2])),
+    "last-maximum vote": (("np.argmax(mean, 1)", "mean.shape[1] - 1 - np.argmax(mean[:, ::-1], 1)"),
+                          lambda be: D.run_oob(be, 63, 2, 3), lambda be: D.run_hits(be, *D.HIT_CASES[2])),
+}
+for _name, (_change, _oob, _hits) in WALK_DEFECTS.items():
+    DEFECTS[f"{_name} (out-of-bag)"], DEFECTS[f"{_name} (permuted hits)"] = (_change, _oob), (_change, _hits)
 
 
 @pytest.mark.parametrize("name", list(DEFECTS))

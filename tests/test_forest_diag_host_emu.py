@@ -1,6 +1,6 @@
 """CPU: ForestClassifier.out_of_bag, feature_importances and permutation_importance and the trainer's --forest_oob,
 --forest_importances and --forest_permutation_repeats on the numpy emulation of the three entry points
-(tests/emu_forest_diag.py), against scikit-learn 1.7.2's RandomForestClassifier(oob_score=True) recorded by
+(tests/emu_forest.py), against scikit-learn 1.7.2's RandomForestClassifier(oob_score=True) recorded by
 tests/golden/make_reference_forest_diag.py and against a host loop over the existing predict.
 tests/test_gpu_forest_diag.py runs the same checks on the device."""
 import warnings
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from hypelcnn_amd.classic import forest as P
-from tests import emu_extra_trees, emu_forest, emu_forest_diag, emu_scene  # noqa: F401 -- attach the emulations
+from tests import emu_forest, emu_scene  # noqa: F401 -- attach the emulations
 from tests import forest_cases as FC
 from tests import forest_diag_checks as H
 from tests.emu_backend import EmuBackend

@@ -3,15 +3,14 @@
 share no code, so a disagreement means one of them misreads the header.  Then the checks are shown to be live: defects
 planted in a copy of the emulation (the bin search, the tie rules, the partition, the sums of squares, the vote, the
 order of the fp64 sum) and writes one element outside each output must all be rejected."""
-import inspect
 import re
 
 import numpy as np
 import pytest
 
-from tests import emu_forest
 from tests import forest_kernel_cases as K
 from tests.emu_backend import EmuBackend
+from tests.emu_forest import mutant  # (the import attaches the emulation to EmuBackend)
 
 
 @pytest.fixture(scope="module")
@@ -30,24 +29,24 @@ def test_split_hist(emu, name):
 
 
 def test_split_apply_partition(emu):
-    K.run_partition(emu)
+    K.run_partition(emu, K.BINS)
 
 
 @pytest.mark.parametrize("level,max_depth", K.LEAF_LEVELS)
 def test_split_apply_leaf_reasons(emu, level, max_depth):
-    K.run_leaf_reasons(emu, level, max_depth)
+    K.run_leaf_reasons(emu, K.BINS, level, max_depth)
 
 
 def test_split_apply_slot_ties(emu):
-    K.run_slot_ties(emu)
+    K.run_slot_ties(emu, K.BINS)
 
 
 @pytest.mark.parametrize("n_active", K.COMPACT_N)
 def test_split_apply_compaction(emu, n_active):
     for pattern in K.COMPACT_PATTERNS:
-        K.run_compaction(emu, n_active, pattern)
-    K.run_compaction(emu, n_active, "alternating", short=1)
-    K.run_compaction(emu, n_active, "last", short=1)
+        K.run_compaction(emu, K.BINS, n_active, pattern)
+    K.run_compaction(emu, K.BINS, n_active, "alternating", short=1)
+    K.run_compaction(emu, K.BINS, n_active, "last", short=1)
 
 
 @pytest.mark.parametrize("name", ["c2_mf1", "heavy_c32", "special"])
@@ -87,20 +86,11 @@ def test_tables_cover_what_they_claim():
 
 
 # ------------------------------------------------------------------------------------------------------ planted defects
-def mutant(old, new, count=1):
-    """EmuBackend with the forest entry points of a copy of tests/emu_forest.py in which `old` reads `new`"""
-    src = inspect.getsource(emu_forest).split("\nfor _name, _fn in")[0]  # (without the lines that attach to EmuBackend)
-    assert src.count(old) == count, (old, src.count(old))
-    ns = {"__name__": "emu_forest_mutant"}
-    exec(compile(src.replace(old, new), "<emu_forest mutant>", "exec"), ns)
-    return type("Mutant", (EmuBackend,), {k[1:]: v for k, v in ns.items() if k.startswith("_k_forest_")})()
-
-
 def test_the_unchanged_copy_passes():
     be = mutant("side=\"left\"", "side=\"left\"")
     assert be.k_forest_bin_u8.__func__ is not EmuBackend.k_forest_bin_u8
     K.run_bins(be, 3, 256)
-    K.run_slot_ties(be)
+    K.run_slot_ties(be, K.BINS)
     K.run_predict_ties(be)
 
 
@@ -115,20 +105,22 @@ DEFECTS = {
     "rows of weight 0 make a side non-empty": (("nl, nr = left.sum(1), right.sum(1)",
                                                 "nl, nr = np.maximum(left.sum(1), 1), np.maximum(right.sum(1), 1)"),
                                                lambda be: K.run_hist(be, "special")),
-    "slot order on a slot tie": (("key=lambda k: (-sc[a, k], cd[a, k], bb[a, k])", "key=lambda k: (-sc[a, k], k)"),
-                                 lambda be: K.run_slot_ties(be)),
+    "slot order on a slot tie": (("key=lambda k: (-sc[a, k], cd[a, k]) + tie(a, k)", "key=lambda k: (-sc[a, k], k)"),
+                                 lambda be: K.run_slot_ties(be, K.BINS)),
     "unstable partition": (("np.concatenate([rows[go_left], rows[~go_left]])",
-                            "np.concatenate([rows[go_left][::-1], rows[~go_left]])"), lambda be: K.run_partition(be)),
-    "level > max_depth": (("or level >= max_depth", "or level > max_depth"), lambda be: K.run_leaf_reasons(be, 4, 4)),
+                            "np.concatenate([rows[go_left][::-1], rows[~go_left]])"), lambda be: K.run_partition(be, K.BINS)),
+    "partition by < instead of <=": (("go_left = table[c][rows] <= cut[a, s]", "go_left = table[c][rows] < cut[a, s]"),
+                                     lambda be: K.run_partition(be, K.BINS)),
+    "level > max_depth": (("or level >= max_depth", "or level > max_depth"), lambda be: K.run_leaf_reasons(be, K.BINS, 4, 4)),
     "a child may take node_capacity": (("if lid + 1 < node_capacity:", "if lid + 1 <= node_capacity:"),
-                                       lambda be: K.run_compaction(be, 257, "alternating", short=1)),
-    "last-maximum vote (rows)": (("np.argmax(mean, 1)", "mean.shape[1] - 1 - np.argmax(mean[:, ::-1], 1)", 2),
+                                       lambda be: K.run_compaction(be, K.BINS, 257, "alternating", short=1)),
+    "last-maximum vote (rows)": (("np.argmax(mean, 1)", "mean.shape[1] - 1 - np.argmax(mean[:, ::-1], 1)"),
                                  lambda be: K.run_predict_ties(be)),
-    "last-maximum vote (scene)": (("np.argmax(mean, 1)", "mean.shape[1] - 1 - np.argmax(mean[:, ::-1], 1)", 2),
+    "last-maximum vote (scene)": (("np.argmax(mean, 1)", "mean.shape[1] - 1 - np.argmax(mean[:, ::-1], 1)"),
                                   lambda be: K.run_scene(be, 3, 2, 2, 65)),
-    "reverse tree order in the fp64 sum": (("for t in range(n_trees):", "for t in reversed(range(n_trees)):"),
+    "reverse tree order in the fp64 sum": (("for t in range(ends.shape[0]):", "for t in reversed(range(ends.shape[0])):"),
                                            lambda be: K.run_predict_ties(be)),
-    "threshold compare < instead of <=": (("v <= threshold[at]", "v < threshold[at]"),
+    "threshold compare < instead of <=": (("feature[at]) <= threshold[at]", "feature[at]) < threshold[at]"),
                                           lambda be: K.run_predict_threshold(be)),
     "lidar read for casi": (("e, which = code >> 1, code & 1", "e, which = code >> 1, 1 - (code & 1)"),
                             lambda be: K.run_scene(be, 3, 2, 2, 65)),
@@ -171,8 +163,8 @@ def outside(op):
 POKE_CASES = {
     "bins": lambda be: K.run_bins(be, 3, 256),
     "split_hist": lambda be: K.run_hist(be, "one_node"),
-    "leaf_reasons": lambda be: K.run_leaf_reasons(be, 3, 4),
-    "compaction": lambda be: K.run_compaction(be, 5, "alternating", short=1),
+    "leaf_reasons": lambda be: K.run_leaf_reasons(be, K.BINS, 3, 4),
+    "compaction": lambda be: K.run_compaction(be, K.BINS, 5, "alternating", short=1),
     "predict_rows": lambda be: K.run_predict(be, 1, 1, 1),
     "predict_scene": lambda be: K.run_scene(be, 3, 2, 2, 1),
 }

@@ -1,5 +1,5 @@
 """-m gpu: hypelcnn_amd.classic.forest.ExtraTreesForest on the device, held BIT FOR BIT to the numpy emulation of the
-same entry points (tests/emu_extra_trees.py) running the same host code with the same seeded stream: the feature-major
+same entry points (tests/emu_forest.py) running the same host code with the same seeded stream: the feature-major
 copy, every level's (score, thr, valid) table, the grown node arrays, labels, probabilities and scene rasters.  Eight
 trees per case."""
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from hypelcnn_amd.classic import forest as P
-from tests import emu_extra_trees, emu_forest, emu_scene  # noqa: F401 -- attach the emulations to EmuBackend
+from tests import emu_forest, emu_scene  # noqa: F401 -- attach the emulations to EmuBackend
 from tests import extra_trees_cases as XC
 from tests import forest_cases as FC
 from tests.emu_backend import EmuBackend

@@ -10,6 +10,7 @@ reference left.  All comparisons are equalities of bytes or integers."""
 import pytest
 
 from tests import extra_trees_kernel_cases as X
+from tests import forest_kernel_cases as K
 
 pytestmark = pytest.mark.gpu
 
@@ -38,24 +39,24 @@ def test_x2_split_random_special_columns(hip):
 
 
 def test_x3_split_apply_thr_partition(hip):
-    X.run_partition(hip)
+    K.run_partition(hip, K.CUTS)
 
 
-@pytest.mark.parametrize("level,max_depth", X.LEAF_LEVELS)
+@pytest.mark.parametrize("level,max_depth", K.LEAF_LEVELS)
 def test_x3_split_apply_thr_leaf_reasons(hip, level, max_depth):
-    X.run_leaf_reasons(hip, level, max_depth)
+    K.run_leaf_reasons(hip, K.CUTS, level, max_depth)
 
 
 def test_x3_split_apply_thr_slot_ties(hip):
-    X.run_slot_ties(hip)
+    K.run_slot_ties(hip, K.CUTS)
 
 
-@pytest.mark.parametrize("n_active", X.COMPACT_N)
+@pytest.mark.parametrize("n_active", K.COMPACT_N)
 def test_x3_split_apply_thr_compaction(hip, n_active):
-    for pattern in X.COMPACT_PATTERNS:
-        X.run_compaction(hip, n_active, pattern)
-    X.run_compaction(hip, n_active, "alternating", short=1)
-    X.run_compaction(hip, n_active, "last", short=1)
+    for pattern in K.COMPACT_PATTERNS:
+        K.run_compaction(hip, K.CUTS, n_active, pattern)
+    K.run_compaction(hip, K.CUTS, n_active, "alternating", short=1)
+    K.run_compaction(hip, K.CUTS, n_active, "last", short=1)
 
 
 @pytest.mark.parametrize("name", ["600_nodes", "c32_mff"])

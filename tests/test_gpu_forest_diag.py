@@ -11,7 +11,7 @@ files, and the three methods of a grown ForestClassifier and a grown ExtraTreesF
 emulation bit for bit."""
 import pytest
 
-from tests import emu_extra_trees, emu_forest, emu_forest_diag, emu_scene  # noqa: F401 -- attach the emulations
+from tests import emu_forest, emu_scene  # noqa: F401 -- attach the emulations
 from tests import forest_cases as FC
 from tests import forest_diag_cases as D
 from tests import forest_diag_checks as H

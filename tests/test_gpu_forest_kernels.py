@@ -35,25 +35,25 @@ def test_f2_split_hist(hip, name):
 
 def test_f3_split_apply_partition(hip):
     """counts 2 .. 1000 with one row, all but one and a random number going left: the order element by element"""
-    K.run_partition(hip)
+    K.run_partition(hip, K.BINS)
 
 
 @pytest.mark.parametrize("level,max_depth", K.LEAF_LEVELS)
 def test_f3_split_apply_leaf_reasons(hip, level, max_depth):
-    K.run_leaf_reasons(hip, level, max_depth)
+    K.run_leaf_reasons(hip, K.BINS, level, max_depth)
 
 
 def test_f3_split_apply_slot_ties(hip):
-    K.run_slot_ties(hip)
+    K.run_slot_ties(hip, K.BINS)
 
 
 @pytest.mark.parametrize("n_active", K.COMPACT_N)
 def test_f3_split_apply_compaction(hip, n_active):
     """all, none, every other and only the last node split; node_capacity exact, and one too small (counter = -1)"""
     for pattern in K.COMPACT_PATTERNS:
-        K.run_compaction(hip, n_active, pattern)
-    K.run_compaction(hip, n_active, "alternating", short=1)
-    K.run_compaction(hip, n_active, "last", short=1)
+        K.run_compaction(hip, K.BINS, n_active, pattern)
+    K.run_compaction(hip, K.BINS, n_active, "alternating", short=1)
+    K.run_compaction(hip, K.BINS, n_active, "last", short=1)
 
 
 @pytest.mark.parametrize("name", ["c2_mf1", "heavy_c32", "special"])
