@@ -2,6 +2,9 @@
 tests/emu_backend.EmuBackend on import.  An executable specification of each kernel's contract, written from the
 header and from libsvm's published algorithm (Fan, Chen, Lin 2005; Chang and Lin, "LIBSVM", section 4) -- buffers have
 the device's dtypes, the arithmetic inside a kernel runs in float64."""
+import inspect
+import sys
+
 import numpy as np
 
 from hypelcnn_amd.backend import SVM_MAX_ITER_LIMIT, SVM_PAIR_DTYPE
@@ -133,12 +136,13 @@ def _k_svm_kernel_apply_f32(self, g, ld, rows, cols, kind, gamma, coef0, degree,
     rn = None if row_norms is None else _arr(row_norms, np.float64)[:rows]
     cn = None if col_norms is None else _arr(col_norms, np.float64)[:cols]
     assert kind != RBF or (rn is not None and cn is not None)
-    m[...] = kernel_values(m, kind, gamma, coef0, degree, rn, cn).astype(np.float32)
+    with np.errstate(over="ignore"):  # (beyond FLT_MAX: +-inf, as the device's conversion)
+        m[...] = kernel_values(m, kind, gamma, coef0, degree, rn, cn).astype(np.float32)
 
 
 def _k_svm_smo_ovo(self, k, ldk, pairs, n_pairs, l_max, c, tol, max_iter, alpha_y, rho, obj, n_iter, status, ws):
     assert 0 < max_iter <= SVM_MAX_ITER_LIMIT, "the iteration cap is bounded"
-    tab = pairs.t.numpy()[pairs.off:].view(SVM_PAIR_DTYPE)[:n_pairs]
+    tab = pairs.t.numpy()[pairs.off:pairs.off + n_pairs * SVM_PAIR_DTYPE.itemsize].view(SVM_PAIR_DTYPE)
     kf = _arr(k)
     for p, rec in enumerate(tab):
         a0, na, b0, nb, off = (int(rec[f]) for f in ("a0", "na", "b0", "nb", "out_off"))
@@ -163,6 +167,16 @@ def _k_svm_vote(self, dec, ld, rows, n_classes, class_labels, points, out, raste
     else:
         pts = _arr(points, np.int32)[: 2 * rows].reshape(rows, 2)
         o[pts[:, 1].astype(np.int64) * raster_w + pts[:, 0]] = lab
+
+
+def mutant(old, new, count=1):
+    """EmuBackend with the entry points of a copy of this module in which `old` (found `count` times) reads `new`; the
+    grid-search twins (tests/emu_svm_grid.py) stay as they are"""
+    src = inspect.getsource(sys.modules[__name__]).split("\nfor _name, _fn in")[0]  # (without the attaching lines)
+    assert src.count(old) == count, (old, src.count(old))
+    ns = {"__name__": "emu_svm_mutant"}
+    exec(compile(src.replace(old, new), "<emu_svm mutant>", "exec"), ns)
+    return type("Mutant", (EmuBackend,), {k[1:]: v for k, v in ns.items() if k.startswith("_k_svm_")})()
 
 
 for _name, _fn in list(globals().items()):

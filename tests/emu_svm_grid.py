@@ -16,6 +16,8 @@ def job_rows(rec):
 def _k_svm_kernel_planes_f32(self, g, ld, rows, cols, kind, gammas, n_gamma, row_norms, col_norms, out, plane_stride):
     assert kind == RBF, "rbf only"
     assert plane_stride >= rows * ld
+    g_at, o_at = g.ptr(), out.ptr()
+    assert o_at + 4 * ((n_gamma - 1) * plane_stride + rows * ld) <= g_at or g_at + 4 * rows * ld <= o_at, "out of place"
     m = _mat(g, ld, rows, cols)
     before = m.copy()
     rn, cn = _arr(row_norms, np.float64)[:rows], _arr(col_norms, np.float64)[:cols]
@@ -34,7 +36,7 @@ def _k_svm_kernel_planes_f32(self, g, ld, rows, cols, kind, gammas, n_gamma, row
 
 def _k_svm_smo_grid(self, k, ldk, jobs, order, n_jobs, l_max, tol, max_iter, alpha_y, rho, obj, n_iter, status, ws):
     assert 0 < max_iter <= SVM_MAX_ITER_LIMIT, "the iteration cap is bounded"
-    tab = jobs.t.numpy()[jobs.off:].view(SVM_JOB_DTYPE)[:n_jobs]
+    tab = jobs.t.numpy()[jobs.off:jobs.off + n_jobs * SVM_JOB_DTYPE.itemsize].view(SVM_JOB_DTYPE)
     issue = np.arange(n_jobs) if order is None else _arr(order, np.int32)[:n_jobs]
     assert sorted(issue.tolist()) == list(range(n_jobs)), "order is a permutation of the jobs"
     kf = _arr(k)
@@ -70,7 +72,7 @@ def _k_svm_scatter_coef_f32(self, alpha_y, rho, pairs, n_pairs, n_c, cell_stride
 
 def _k_svm_vote_score(self, dec, ld, rows, n_classes, n_cells, npp, truth, correct):
     n_pairs = n_classes * (n_classes - 1) // 2
-    assert 2 <= n_classes <= 256 and npp >= n_pairs and ld >= n_cells * npp
+    assert 2 <= n_classes <= 255 and npp >= n_pairs and ld >= n_cells * npp
     d = _mat(dec, ld, rows, n_cells * npp)
     t = _arr(truth, np.int32)[:rows]
     c = _arr(correct, np.int32)
