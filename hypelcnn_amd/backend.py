@@ -65,6 +65,9 @@ ACT_MAX_BINS = abi.const("HYPEL_ACT_MAX_BINS")  # bins of hypel_view_histogram_f
 FOREST_EDGE_ROWS, FOREST_MAX_EDGES, FOREST_MAX_CLASSES, FOREST_MAX_DEPTH = (
     abi.const("HYPEL_FOREST_" + k) for k in ("EDGE_ROWS", "MAX_EDGES", "MAX_CLASSES", "MAX_DEPTH"))
 FOREST_NODE_DTYPE = abi.struct("hypel_forest_node_t")  # a leaf has left = -1 - (its row of the leaf table)
+# hypel_pca_*: most bands, pixels per float32 accumulator, side of a scatter tile, most blocks of a fit pass
+PCA_MAX_BANDS, PCA_CHUNK, PCA_TILE, PCA_MAX_BLOCKS = (abi.const("HYPEL_PCA_" + k)
+                                                      for k in ("MAX_BANDS", "CHUNK", "TILE", "MAX_BLOCKS"))
 TIFF_SEG_DTYPE = abi.struct("hypel_tiff_seg_t")  # byte offsets and lengths
 TIFF_LZW, TIFF_PACKBITS = abi.const("HYPEL_TIFF_LZW"), abi.const("HYPEL_TIFF_PACKBITS")  # codecs of hypel_tiff_unpack
 

@@ -29,6 +29,15 @@ Differences from the reference, all on purpose:
    --svc_grid_c / --svc_grid_gamma take lo:hi:n decades (defaults: the reference's -2:10:13 and -9:3:13),
    --svc_grid_refit refits on the best cell and serves --fullscene from that estimator.  --hyperparamopt itself stays
    refused: its contract in the reference is scikit-learn's own GridSearchCV object, which this project does not return;
+ - what every published SVM / forest baseline of these scenes also reports, a PCA over the band axis in front of the
+   estimator, is two NEW flags, valid with all four estimators and every other flag: --pca_components K (a count, or a
+   fraction below 1: the share of the variance to keep; 0, the default: off) and --pca_whiten.  The PCA
+   (hypelcnn_amd.classic.decomposition.BandPCA) is fitted once per process on the interior of the loader's
+   scene, before the episodes; every episode's patches are projected pixel by pixel with the LiDAR channels passed
+   through, --fullscene is served from the projected scene, and the band axis of the forest diagnostics then means
+   components.  pca_<loader>.json (n_components, n_samples, bands, whiten, explained_variance,
+   explained_variance_ratio) and pca_<loader>.npz (mean_, components_, explained_variance_) are written beside the
+   result files.  With --pca_components 0 nothing changes: not a launch, not a file, not a byte of output;
  - --fullscene writes result_raw.tif / result_colorized.tif under --output_path, not the reference's hard-wired ".."
    (:111); patches are cut on the device (hypel_gather_patches_f32) and predicted in chunks sized from free memory,
    independent of --batch_size; the forest walks its trees straight on the padded scene where the data set has one
@@ -39,6 +48,7 @@ import json
 import os
 import sys
 import time
+import types
 
 import numpy
 
@@ -85,6 +95,27 @@ def add_parse_cmds_for_app(parser):
     parser.add_argument("--svc_grid_gamma", type=str, default="-9:3:13", help="gamma decades lo:hi:n")
     parser.add_argument("--svc_grid_refit", nargs="?", const=True, type=type_ensure_strtobool, default=False,
                         help="If true, refits on the best cell; --fullscene then uses that estimator.")
+    parser.add_argument("--pca_components", nargs="?", type=parse_pca_components, default=0,
+                        help="Band PCA in front of the estimator: components kept (an integer), or the share of the "
+                             "variance to keep (a fraction below 1); 0: off")
+    parser.add_argument("--pca_whiten", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, scales the kept components to unit variance (with --pca_components).")
+
+
+def parse_pca_components(text):
+    """'0' (off), an integer >= 1 (components) or a fraction in (0, 1) (share of the variance)"""
+    try:
+        value = int(text)
+    except ValueError:
+        try:
+            value = float(text)
+        except ValueError:
+            value = -1.0
+        if not 0.0 < value < 1.0:
+            raise argparse.ArgumentTypeError(f"{text!r}: 0, a count of components or a fraction below 1") from None
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"{text!r}: 0, a count of components or a fraction below 1")
+    return value
 
 
 def create_estimator(flags, backend=None, run_index=0):
@@ -157,12 +188,15 @@ def print_output(algorithm_params, average_accuracy, conf_matrix, kappa, overall
         json.dump(algorithm_params, params_file)
 
 
-def perform_full_scene_classification(data_path, loader_name, neighborhood, estimator, output_path):
-    """reference :83-115: every pixel of the scene, row-major, one (x, y) target each."""
+def perform_full_scene_classification(data_path, loader_name, neighborhood, estimator, output_path, pca=None):
+    """reference :83-115: every pixel of the scene, row-major, one (x, y) target each.  pca: the fitted BandPCA of
+    --pca_components; the estimator then sees the projected scene."""
     import torch
     backend = estimator._backend()
     loader = get_loader_from_name(loader_name, data_path)
     data_set = loader.load_data(neighborhood, False)
+    if pca is not None:
+        data_set = pca.transform_scene(data_set)
     scene_shape = data_set.get_scene_shape()
     ys, xs = numpy.meshgrid(numpy.arange(scene_shape[0]), numpy.arange(scene_shape[1]), indexing="ij")
     targets = numpy.stack([xs.reshape(-1), ys.reshape(-1), numpy.zeros(xs.size, dtype=int)], axis=1)
@@ -176,6 +210,34 @@ def perform_full_scene_classification(data_path, loader_name, neighborhood, esti
     imwrite(os.path.join(output_path, "result_colorized.tif"),
             create_colored_image(scene_as_image, loader.get_samples_color_list()))
     return scene_as_image
+
+
+def fit_band_pca(flags, backend=None):
+    """--pca_components: one BandPCA per process, fitted on the interior of the loader's scene (it does not depend on
+    the split), written as pca_<loader>.json (what was kept and how much of the variance it explains) and
+    pca_<loader>.npz (mean_, components_, explained_variance_) next to the result files."""
+    from hypelcnn_amd.classic.decomposition import BandPCA
+    pca = BandPCA(flags.pca_components, whiten=flags.pca_whiten, backend=backend)
+    start_time = time.time()
+    pca.fit_scene(get_loader_from_name(flags.loader_name, flags.path).load_data(flags.neighborhood, False))
+    print("Completed band PCA: %d of %d bands, %.5f of the variance(%.3f sec)" % (
+        pca.n_components_, pca.n_features_in_, pca.explained_variance_ratio_.sum(), time.time() - start_time))
+    os.makedirs(flags.base_log_path, exist_ok=True)
+    with open(os.path.join(flags.base_log_path, f"pca_{flags.loader_name}.json"), "w") as pca_file:
+        json.dump({"n_components": pca.n_components_, "n_samples": pca.n_samples_, "bands": pca.n_features_in_,
+                   "whiten": pca.whiten, "explained_variance": pca.explained_variance_.tolist(),
+                   "explained_variance_ratio": pca.explained_variance_ratio_.tolist()}, pca_file)
+    numpy.savez(os.path.join(flags.base_log_path, f"pca_{flags.loader_name}.npz"), mean_=pca.mean_,
+                components_=pca.components_, explained_variance_=pca.explained_variance_)
+    return pca
+
+
+def project_patches(pca, sample_set):
+    """[n, p, p, C + lidar] patches -> [n, p, p, k + lidar]: every patch pixel is a row, the LiDAR channels pass through"""
+    data = numpy.ascontiguousarray(sample_set.data, dtype=numpy.float32)
+    n, p, _, channels = data.shape
+    rows = pca.transform(data.reshape(n * p * p, channels), pass_cols=channels - pca.n_features_in_)
+    return types.SimpleNamespace(data=rows.reshape(n, p, p, rows.shape[1]), labels=sample_set.labels)
 
 
 def forest_diagnostics_asked(flags):
@@ -295,11 +357,14 @@ def main(argv=None, backend=None):
         raise ValueError(f"{', '.join(forest_diagnostics_asked(flags))}: diagnostics of a forest (--estimator forest or "
                          f"extra_trees), not of --estimator {flags.estimator}")
     results = []
+    pca = fit_band_pca(flags, backend) if flags.pca_components else None
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)
         training, _, validation, _, _, _, _ = InMemoryImporter().read_data_set(
             loader_name=flags.loader_name, path=flags.path, test_data_ratio=0, train_data_ratio=0.1,
             neighborhood=flags.neighborhood, normalize=False)
+        if pca is not None:
+            training, validation = project_patches(pca, training), project_patches(pca, validation)
         start_time = time.time()
         estimator = create_estimator(flags, backend, run_index)
         estimator.fit(flatten_data(training.data), training.labels)
@@ -319,7 +384,7 @@ def main(argv=None, backend=None):
         scene = None
         if flags.fullscene:
             scene = perform_full_scene_classification(flags.path, flags.loader_name, flags.neighborhood, estimator,
-                                                      flags.output_path)
+                                                      flags.output_path, pca)
         results.append((estimator, predicted, conf_matrix, (overall_accuracy, average_accuracy, kappa), scene))
     return results
 

@@ -1165,6 +1165,49 @@ int hypel_view_range_f32(const float* src, int64_t rows, int64_t ld, int32_t col
 int hypel_view_histogram_f32(const float* src, int64_t rows, int64_t ld, int32_t cols, const double* edges,
                              int32_t n_bins, int64_t* counts, int64_t* outside, hypel_stream_t stream);
 
+/* ---- band PCA (classic/decomposition.py: BandPCA -- sklearn.decomposition.PCA over the band axis of a resident scene;
+ * csrc/pca.hip) ----------------------------------------------------------------------------------------------------------
+ * A VIEW is h rows of w pixels of c float32 bands with band stride 1: band b of pixel (y, x) is
+ * x[y * stride_y + x * stride_x + b] (element strides >= c; the origin comes through the pointer, 4-byte aligned only).
+ * That is the interior of a padded scene [hp][wp][C] (x = scene + n * (wp + 1) * C, stride_y = wp * C, stride_x = C) as
+ * well as a plain row matrix (h = 1, stride_x = ld).  h, w >= 1, h * w <= 2^40, 1 <= c <= HYPEL_PCA_MAX_BANDS, strides
+ * <= 2^40; anything else is refused, as are outputs or workspaces that overlap an input or each other.  Pixel p of a view
+ * is (p / w, p % w); pixels are cut into chunks of HYPEL_PCA_CHUNK in that order.  No floating-point atomics anywhere:
+ * partials go to a workspace and are added in a fixed order, so two calls on the same input give the same bits.
+ *
+ * hypel_pca_band_sums_f64: sums[b] = sum over the pixels of x_b in double (a float32 is exact in double; the error is
+ *   that of n double additions).  Block g of G = min(chunks, HYPEL_PCA_MAX_BLOCKS) adds chunks g, g + G, ...; the G
+ *   partials of a band are added by one block in a fixed order (strided shares, then a halving tree).  ws: G * c
+ *   doubles, ws_doubles says how many there are.
+ * hypel_pca_scatter_f64: scatter[i * c + j] = sum over the pixels of (x_i - mean_i) * (x_j - mean_j), the full symmetric
+ *   [c][c] matrix (scatter[i][j] and scatter[j][i] are the same bits).  mean: device float32 [c].  Centred at load in
+ *   float32 (one rounding per value); the products on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, an fmaf chain: every
+ *   product exact, one rounding per addition); ONE float32 accumulator takes one chunk and no more, the chunk partials
+ *   are added in double: in the order of the chunks inside a block, then in the order of the blocks.  The output is cut
+ *   into tiles of HYPEL_PCA_TILE x HYPEL_PCA_TILE, T = nt * (nt + 1) / 2 of them on or above the diagonal (nt =
+ *   ceil(c / HYPEL_PCA_TILE)); G = min(chunks, HYPEL_PCA_MAX_BLOCKS / T) blocks per tile.  ws: G * T * HYPEL_PCA_TILE^2
+ *   doubles (at most HYPEL_PCA_MAX_BLOCKS * HYPEL_PCA_TILE^2 = 32 MiB), ws_doubles says how many there are.  A band
+ *   that equals its mean in every pixel has a row and a column of exact zeros.
+ * hypel_pca_project_f32: row r = pixel r of the view; out[r * ldo + j] = sum_b (x[r][b] - mean[b]) * weights[b * k + j]
+ *   for j < k, and out[r * ldo + k + j] = x[r][c + j] for j < pass (trailing input floats of the pixel copied through, bit
+ *   for bit; both strides >= c + pass).  weights: [c][k] row-major float32, 1 <= k <= c (whitening is folded into it by
+ *   the host); ldo >= k + pass; columns of out beyond k + pass are not written.  Centred at load (not x W - mean W, which
+ *   cancels); every output is ONE chain acc = fmaf(x_b - mean_b, W_bj, acc) over b = 0 .. c - 1 from 0, so the same
+ *   pixel gives the same bits in any row, tail or grid pass.  A block owns 64 rows; at most
+ *   HYPEL_PCA_PROJECT_MAX_BLOCKS blocks walk the rows.  The ranges of x and out must not overlap. */
+#define HYPEL_PCA_MAX_BANDS 512
+#define HYPEL_PCA_CHUNK 1024
+#define HYPEL_PCA_TILE 64
+#define HYPEL_PCA_MAX_BLOCKS 1024
+#define HYPEL_PCA_PROJECT_MAX_BLOCKS 4096
+int hypel_pca_band_sums_f64(const float* x, int64_t h, int64_t w, int32_t c, int64_t stride_y, int64_t stride_x,
+                            double* sums, double* ws, int64_t ws_doubles, hypel_stream_t stream);
+int hypel_pca_scatter_f64(const float* x, int64_t h, int64_t w, int32_t c, int64_t stride_y, int64_t stride_x,
+                          const float* mean, double* scatter, double* ws, int64_t ws_doubles, hypel_stream_t stream);
+int hypel_pca_project_f32(const float* x, int64_t h, int64_t w, int32_t c, int64_t stride_y, int64_t stride_x,
+                          int32_t pass, const float* mean, const float* weights, int32_t k, float* out, int64_t ldo,
+                          hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
