@@ -25,6 +25,10 @@ def _band(h, w, bands, b):
     return lambda fill: fill((h, w, bands))[:, :, b]  # a view: read in place through its strides
 
 
+def _band_transposed(h, w, bands, b):
+    return lambda fill: fill((w, h, bands))[:, :, b].T  # a band of a [w][h][bands] store: sx = h * bands > sy = bands
+
+
 def _zero_block(h, w, rows, cols):
     def make(fill):
         a = fill((h, w))
@@ -79,6 +83,7 @@ CASES = {
     "scales_4_1": (_plain(13, 17), 4, _plain(9, 11), 1),
     "strided_bands": (_band(20, 24, 5, 3), 1, _band(6, 7, 3, 2), 1),
     "strided_bands_scaled": (_band(10, 12, 5, 3), 3, _band(6, 7, 3, 2), 2),
+    "transposed_band": (_band_transposed(29, 37, 5, 3), 1, _band_transposed(9, 11, 3, 2), 3),
     "zero_block": (_zero_block(20, 24, slice(3, 13), slice(5, 17)), 1, _plain(4, 5), 1),
     "all_zero_image": (_all_zero(12, 15), 1, _plain(4, 5), 1),
     "ties_periodic": (_periodic(14, 19, 3, 4), 1, _plain(5, 6), 1),

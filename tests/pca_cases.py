@@ -47,9 +47,10 @@ def factor(n):
 
 
 def layouts(x):
-    """The same pixels as (name, float32 buffer, origin in floats, h, w, stride_y, stride_x): a plain row matrix, and the
+    """The same pixels as (name, float32 buffer, origin in floats, h, w, stride_y, stride_x): a plain row matrix, the
     interior of a padded scene [h + 4][w + 4][C] (neighbourhood 2, C odd >= c) that starts one float into its buffer --
-    the origin is 4-byte aligned only and stride_y != w * stride_x."""
+    the origin is 4-byte aligned only and stride_y != w * stride_x -- and the interior of the same scene stored
+    [w + 4][h + 4][C]: stride_y < stride_x, consecutive pixels of a row lie a whole stored line apart."""
     n, c = x.shape
     yield "plain", x.reshape(-1).copy(), 0, 1, n, n * c, c
     h, w = factor(n)
@@ -58,6 +59,10 @@ def layouts(x):
     scene[2:2 + h, 2:2 + w, :c] = x.reshape(h, w, c)
     buf = np.concatenate([np.full(1, np.nan, np.float32), scene.reshape(-1)])
     yield "padded", buf, 1 + 2 * (w + 4 + 1) * cs, h, w, (w + 4) * cs, cs
+    scene = np.full((w + 4, h + 4, cs), np.float32(np.nan))
+    scene[2:2 + w, 2:2 + h, :c] = x.reshape(h, w, c).transpose(1, 0, 2)
+    buf = np.concatenate([np.full(1, np.nan, np.float32), scene.reshape(-1)])
+    yield "transposed", buf, 1 + 2 * (h + 4 + 1) * cs, h, w, cs, (h + 4) * cs
 
 
 def guarded(be, count, dtype):

@@ -41,7 +41,8 @@ def test_more_splits_than_column_chunks(be):
 
 
 @pytest.mark.parametrize("name,kind", [("strided_bands", "int"), ("strided_bands_scaled", "uniform"),
-                                       ("scales_5_2", "uniform"), ("ties_periodic", "int")])
+                                       ("scales_5_2", "uniform"), ("ties_periodic", "int"),
+                                       ("transposed_band", "int"), ("transposed_band", "uniform")])
 def test_wrapper_on_host_arrays_and_device_tensors(be, name, kind):
     case = M.case(name, kind)
     found = dm.match_template(be, case.image, case.template, case.image_scale, case.template_scale, keep_scores=True)

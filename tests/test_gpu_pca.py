@@ -30,7 +30,7 @@ def bits(a):
 
 
 def fit_case(be, x):
-    """both layouts, each twice: equal bits between the runs and between the layouts, the bounds on each -> error shares"""
+    """every layout, each twice: equal bits between the runs and between the layouts, the bounds on each -> error shares"""
     worst = (0.0, 0.0)
     first = None
     for _, buf, origin, h, w, sy, sx in PC.layouts(x):
