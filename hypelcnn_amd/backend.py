@@ -68,6 +68,9 @@ FOREST_NODE_DTYPE = abi.struct("hypel_forest_node_t")  # a leaf has left = -1 - 
 # hypel_pca_*: most bands, pixels per float32 accumulator, side of a scatter tile, most blocks of a fit pass
 PCA_MAX_BANDS, PCA_CHUNK, PCA_TILE, PCA_MAX_BLOCKS = (abi.const("HYPEL_PCA_" + k)
                                                       for k in ("MAX_BANDS", "CHUNK", "TILE", "MAX_BLOCKS"))
+# hypel_morph_*: largest radius of a structuring element, most blocks of a launch, the raster kernels' tile, shapes, ops
+MORPH_MAX_RADIUS, MORPH_MAX_BLOCKS, MORPH_TILE_W, MORPH_TILE_H, MORPH_DISK, MORPH_SQUARE, MORPH_ERODE, MORPH_DILATE = (
+    abi.const("HYPEL_MORPH_" + k) for k in ("MAX_RADIUS", "MAX_BLOCKS", "TILE_W", "TILE_H", "DISK", "SQUARE", "ERODE", "DILATE"))
 TIFF_SEG_DTYPE = abi.struct("hypel_tiff_seg_t")  # byte offsets and lengths
 TIFF_LZW, TIFF_PACKBITS = abi.const("HYPEL_TIFF_LZW"), abi.const("HYPEL_TIFF_PACKBITS")  # codecs of hypel_tiff_unpack
 

@@ -38,6 +38,16 @@ Differences from the reference, all on purpose:
    components.  pca_<loader>.json (n_components, n_samples, bands, whiten, explained_variance,
    explained_variance_ratio) and pca_<loader>.npz (mean_, components_, explained_variance_) are written beside the
    result files.  With --pca_components 0 nothing changes: not a launch, not a file, not a byte of output;
+ - the step the same baselines put AFTER the PCA, the extended morphological profile ("PCA -> EMP -> SVM / RF"), is
+   four NEW flags, valid with all four estimators and every other flag: --emp_radii 2,4,6,8 (absent or empty: off),
+   --emp_shape disk|square, --emp_plain (plain openings and closings instead of those by reconstruction) and --emp_lidar
+   true|false (default true: the LiDAR channels are profiled as further bases).  The profile
+   (hypelcnn_amd.classic.morphology.MorphologicalProfile) is computed once per process on the interior of the
+   loader's scene, after the PCA if there is one.  A profile is no per-pixel function, so patches are not transformed:
+   the loader's load_samples(0.1, 0) targets -- the call InMemoryImporter.read_data_set makes -- are cut from the profiled
+   scene on the device, --fullscene classifies that same scene, and the band axis of the forest diagnostics then means
+   profile channels.  emp_<loader>.json (radii, shape, by_reconstruction, include_lidar, bases, channels, sweeps per
+   level, seconds) is written beside the result files.  Without --emp_radii nothing changes;
  - --fullscene writes result_raw.tif / result_colorized.tif under --output_path, not the reference's hard-wired ".."
    (:111); patches are cut on the device (hypel_gather_patches_f32) and predicted in chunks sized from free memory,
    independent of --batch_size; the forest walks its trees straight on the padded scene where the data set has one
@@ -100,6 +110,24 @@ def add_parse_cmds_for_app(parser):
                              "variance to keep (a fraction below 1); 0: off")
     parser.add_argument("--pca_whiten", nargs="?", const=True, type=type_ensure_strtobool, default=False,
                         help="If true, scales the kept components to unit variance (with --pca_components).")
+    parser.add_argument("--emp_radii", nargs="?", const=(), type=parse_emp_radii, default=(),
+                        help="Extended morphological profile behind the PCA (if any): the radii of the structuring "
+                             "elements, strictly increasing, e.g. 2,4,6,8; absent or empty: off")
+    parser.add_argument("--emp_shape", nargs="?", type=str, default="disk", choices=("disk", "square"),
+                        help="Structuring element of the profile (with --emp_radii)")
+    parser.add_argument("--emp_plain", nargs="?", const=True, type=type_ensure_strtobool, default=False,
+                        help="If true, plain openings and closings instead of those by reconstruction (with --emp_radii).")
+    parser.add_argument("--emp_lidar", nargs="?", const=True, type=type_ensure_strtobool, default=True,
+                        help="If true (the default), the LiDAR channels are profiled as further bases; if false they pass "
+                             "through untouched (with --emp_radii).")
+
+
+def parse_emp_radii(text):
+    """'' (off) or integers separated by commas; the range and the order are MorphologicalProfile's to check"""
+    try:
+        return tuple(int(part) for part in text.split(",") if part.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: radii as integers separated by commas, e.g. 2,4,6,8") from None
 
 
 def parse_pca_components(text):
@@ -188,15 +216,20 @@ def print_output(algorithm_params, average_accuracy, conf_matrix, kappa, overall
         json.dump(algorithm_params, params_file)
 
 
-def perform_full_scene_classification(data_path, loader_name, neighborhood, estimator, output_path, pca=None):
+def perform_full_scene_classification(data_path, loader_name, neighborhood, estimator, output_path, pca=None,
+                                      profiled=None):
     """reference :83-115: every pixel of the scene, row-major, one (x, y) target each.  pca: the fitted BandPCA of
-    --pca_components; the estimator then sees the projected scene."""
+    --pca_components; the estimator then sees the projected scene.  profiled: the scene --emp_radii computed (after the
+    PCA, if any), which is then classified as it is."""
     import torch
     backend = estimator._backend()
     loader = get_loader_from_name(loader_name, data_path)
-    data_set = loader.load_data(neighborhood, False)
-    if pca is not None:
-        data_set = pca.transform_scene(data_set)
+    if profiled is not None:
+        data_set = profiled
+    else:
+        data_set = loader.load_data(neighborhood, False)
+        if pca is not None:
+            data_set = pca.transform_scene(data_set)
     scene_shape = data_set.get_scene_shape()
     ys, xs = numpy.meshgrid(numpy.arange(scene_shape[0]), numpy.arange(scene_shape[1]), indexing="ij")
     targets = numpy.stack([xs.reshape(-1), ys.reshape(-1), numpy.zeros(xs.size, dtype=int)], axis=1)
@@ -238,6 +271,42 @@ def project_patches(pca, sample_set):
     n, p, _, channels = data.shape
     rows = pca.transform(data.reshape(n * p * p, channels), pass_cols=channels - pca.n_features_in_)
     return types.SimpleNamespace(data=rows.reshape(n, p, p, rows.shape[1]), labels=sample_set.labels)
+
+
+def compute_profile(flags, backend=None, pca=None):
+    """--emp_radii: one MorphologicalProfile per process, of the loader's scene behind the PCA (if any); written as
+    emp_<loader>.json next to the result files.  -> (the profile, the profiled scene, the loader it came from)"""
+    from hypelcnn_amd.classic.morphology import MorphologicalProfile
+    profile = MorphologicalProfile(flags.emp_radii, shape=flags.emp_shape, by_reconstruction=not flags.emp_plain,
+                                   include_lidar=flags.emp_lidar, backend=backend)
+    loader = get_loader_from_name(flags.loader_name, flags.path)
+    data_set = loader.load_data(flags.neighborhood, False)
+    start_time = time.time()
+    if pca is not None:
+        data_set = pca.transform_scene(data_set)
+    scene = profile.transform_scene(data_set)
+    channels = scene.get_casi_band_count()
+    levels = 2 * len(profile.radii) + 1
+    profile._backend().synchronize()
+    seconds = time.time() - start_time
+    print("Completed morphological profile: %d bases x %d levels = %d channels, %d sweeps(%.3f sec)" % (
+        channels // levels, levels, channels, sum(profile.sweeps_.values()), seconds))
+    os.makedirs(flags.base_log_path, exist_ok=True)
+    with open(os.path.join(flags.base_log_path, f"emp_{flags.loader_name}.json"), "w") as emp_file:
+        json.dump({"radii": list(profile.radii), "shape": profile.shape, "by_reconstruction": profile.by_reconstruction,
+                   "include_lidar": profile.include_lidar, "bases": channels // levels, "channels": channels,
+                   "sweeps": profile.sweeps_, "seconds": seconds}, emp_file)
+    return profile, scene, loader
+
+
+def cut_profiled_patches(scene, targets, backend):
+    """target rows [x, y, class] -> their patches, cut from the profiled scene on the device (what
+    InMemoryImporter._get_data_with_labels does on the host for a raw scene)"""
+    import torch
+    arrays = SceneArrays()
+    arrays.feed(scene, targets, backend)
+    patches, _ = arrays.gather(torch.arange(len(targets), device=backend.device))
+    return types.SimpleNamespace(data=patches.cpu().numpy(), labels=numpy.asarray(targets)[:, 2].astype(numpy.uint8))
 
 
 def forest_diagnostics_asked(flags):
@@ -358,13 +427,21 @@ def main(argv=None, backend=None):
                          f"extra_trees), not of --estimator {flags.estimator}")
     results = []
     pca = fit_band_pca(flags, backend) if flags.pca_components else None
+    profile, profiled, profiled_loader = compute_profile(flags, backend, pca) if flags.emp_radii else (None, None, None)
     for run_index in range(flags.split_count):
         print("Starting episode#%d" % run_index)
-        training, _, validation, _, _, _, _ = InMemoryImporter().read_data_set(
-            loader_name=flags.loader_name, path=flags.path, test_data_ratio=0, train_data_ratio=0.1,
-            neighborhood=flags.neighborhood, normalize=False)
-        if pca is not None:
-            training, validation = project_patches(pca, training), project_patches(pca, validation)
+        if profile is not None:
+            # a profile is no per-pixel function: the patches are cut from the profiled scene, at the targets
+            # InMemoryImporter.read_data_set would have cut from the raw one
+            sample_set = profiled_loader.load_samples(0.1, 0)
+            training = cut_profiled_patches(profiled, sample_set.training_targets, profile._backend())
+            validation = cut_profiled_patches(profiled, sample_set.validation_targets, profile._backend())
+        else:
+            training, _, validation, _, _, _, _ = InMemoryImporter().read_data_set(
+                loader_name=flags.loader_name, path=flags.path, test_data_ratio=0, train_data_ratio=0.1,
+                neighborhood=flags.neighborhood, normalize=False)
+            if pca is not None:
+                training, validation = project_patches(pca, training), project_patches(pca, validation)
         start_time = time.time()
         estimator = create_estimator(flags, backend, run_index)
         estimator.fit(flatten_data(training.data), training.labels)
@@ -384,7 +461,7 @@ def main(argv=None, backend=None):
         scene = None
         if flags.fullscene:
             scene = perform_full_scene_classification(flags.path, flags.loader_name, flags.neighborhood, estimator,
-                                                      flags.output_path, pca)
+                                                      flags.output_path, pca, profiled)
         results.append((estimator, predicted, conf_matrix, (overall_accuracy, average_accuracy, kappa), scene))
     return results
 

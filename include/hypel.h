@@ -1208,6 +1208,54 @@ int hypel_pca_project_f32(const float* x, int64_t h, int64_t w, int32_t c, int64
                           int32_t pass, const float* mean, const float* weights, int32_t k, float* out, int64_t ldo,
                           hypel_stream_t stream);
 
+/* ---- grey-scale morphology (classic/morphology.py: MorphologicalProfile -- openings and closings by reconstruction of
+ * a resident scene's channels, the extended morphological profile; csrc/morph.hip) ---------------------------------------
+ * ORDER.  Every comparison is an unsigned compare of KEYS: a float32 with bit pattern u has the key
+ * k = (u >> 31) ? ~u : (u | 0x80000000), and u = (k >> 31) ? (k & 0x7fffffff) : ~k gives it back exactly.  That is one
+ * total order on all 2^32 patterns: -0 < +0, -inf below every finite value, +inf above, the NaNs at the two ends by
+ * their sign bit.  All arithmetic is integer min / max on keys, every output is a bit copy of an input, nothing depends
+ * on an evaluation order, and two calls on the same input give the same bits.  No floating-point atomics.
+ * A key IMAGE is dense [h][w][c] uint32 (channel c of pixel (y, x) at (y * w + x) * c + ch); every channel is an
+ * image of its own to the operators.  h, w >= 1, c >= 1, h, w < 2^31, h * w * c <= 2^40; anything else is refused, as
+ * are null pointers and an output that overlaps an input.  A launch runs at most HYPEL_MORPH_MAX_BLOCKS blocks, each of
+ * which walks (tile, channel) pairs or elements with the stride of the grid.
+ *
+ * hypel_morph_keys_u32: keys[(y * w + x) * c + ch] = key of x[y * stride_y + x * stride_x + ch] -- the VIEW of the band
+ *   PCA above (element strides >= c, origin 4-byte aligned only), so the interior of a padded scene is read in place.
+ * hypel_morph_erode_dilate_u32: dst = the minimum (op HYPEL_MORPH_ERODE) or maximum (HYPEL_MORPH_DILATE) of src over the
+ *   structuring element of `radius` 0 .. HYPEL_MORPH_MAX_RADIUS: HYPEL_MORPH_DISK the offsets dx^2 + dy^2 <= radius^2
+ *   (radius 1: the 4-neighbour cross), HYPEL_MORPH_SQUARE |dx|, |dy| <= radius; radius 0 copies.  Offsets outside the
+ *   raster are ignored (erosion is padded with the largest key, dilation with the smallest); a radius larger than the
+ *   raster is legal.  A block owns a tile of HYPEL_MORPH_TILE_W x HYPEL_MORPH_TILE_H pixels of one channel and holds
+ *   it with its halo in LDS; the element is evaluated as one row span per dy.
+ * hypel_morph_reconstruct_sweep_u32: one sweep of the reconstruction of `mask` from `marker_in`, by dilation (op
+ *   HYPEL_MORPH_DILATE: the limit of m <- min(dilate3x3(m), mask) from m = min(marker, mask), 8-connectivity) or by erosion
+ *   (HYPEL_MORPH_ERODE, the dual: max, erode3x3).  Per launch, for dilation (dual for erosion), pointwise:
+ *   marker_out >= min(marker_in, mask); marker_out <= the limit; marker_out == marker_in exactly when marker_in is the
+ *   limit; *changed is set to 1 exactly when they differ, and is never cleared.  A block iterates its tile (the same tile
+ *   as above, one channel) to stability in LDS against the one-pixel halo of min(marker_in, mask) it loaded, so a launch
+ *   carries a front across a tile, not a pixel.  marker_out must not overlap marker_in or mask (ping-pong buffers;
+ *   marker_in and mask may be the same).
+ * hypel_morph_profile_store_f32: the float32 of keys[y][x][b] goes to channel chan_offset + b * chan_step of the padded
+ *   stack out [h + 2 pad][w + 2 pad][out_c], at (y + pad, x + pad) AND at every padding pixel that reflects onto (y, x)
+ *   under numpy.pad(mode="symmetric") (index i < 0 reads -1 - i, i >= n reads 2 n - 1 - i): every padded pixel of the c
+ *   channels is written once, no other channel of out is touched.  0 <= pad <= min(h, w) (one reflection), chan_step >= 1,
+ *   chan_offset >= 0, chan_offset + (c - 1) * chan_step < out_c. */
+#define HYPEL_MORPH_MAX_RADIUS 32
+#define HYPEL_MORPH_MAX_BLOCKS 1024
+#define HYPEL_MORPH_TILE_W 64
+#define HYPEL_MORPH_TILE_H 16
+enum { HYPEL_MORPH_DISK = 0, HYPEL_MORPH_SQUARE = 1 };
+enum { HYPEL_MORPH_ERODE = 0, HYPEL_MORPH_DILATE = 1 };
+int hypel_morph_keys_u32(const float* x, int64_t h, int64_t w, int32_t c, int64_t stride_y, int64_t stride_x,
+                         uint32_t* keys, hypel_stream_t stream);
+int hypel_morph_erode_dilate_u32(const uint32_t* src, int64_t h, int64_t w, int32_t c, int32_t radius, int32_t shape,
+                                 int32_t op, uint32_t* dst, hypel_stream_t stream);
+int hypel_morph_reconstruct_sweep_u32(const uint32_t* marker_in, const uint32_t* mask, int64_t h, int64_t w, int32_t c,
+                                      int32_t op, uint32_t* marker_out, int32_t* changed, hypel_stream_t stream);
+int hypel_morph_profile_store_f32(const uint32_t* keys, int64_t h, int64_t w, int32_t c, int32_t pad, float* out,
+                                  int32_t out_c, int32_t chan_offset, int32_t chan_step, hypel_stream_t stream);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ---------------------------------------- */
 int hypel_graph_begin_capture(hypel_stream_t stream);
 int hypel_graph_end_capture(hypel_stream_t stream, void** graph_exec_out);
